@@ -9,6 +9,7 @@ slm/sample_esmdiff.py:137-233).  Inputs (tokens, weights) are resident in HBM wh
 
     python bench.py [--gpus N --steps K --warmup W]        (N > 1 without a launcher: re-executes itself under
                                                             torch.distributed.run, one rank per GPU, still ONE JSON line)
+    python bench.py ... --dump-outputs DIR                 (also writes the last timed step's ids to DIR/ids.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  Extra objects:
@@ -33,6 +34,7 @@ if str(ROOT) not in sys.path:
 import torch  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0   # MI355X dense bf16 MFMA (MI355X_MICROARCH.md: ~2.5 PF dense)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
 
 
 def flops_forward_per_sample(L: int, cfg) -> float:
@@ -313,6 +315,29 @@ def roofline_report(args, cfg, B, L, n_fwd_sample, prof_dom, prof):
     return rep
 
 
+def dump_outputs(out_dir: Path, arrays: dict, seed: int = 0) -> dict:
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32 (the ids are exact in it).  When the arrays together
+    exceed DUMP_LIMIT_BYTES, each keeps a fixed, seeded sample of its rows (same shapes -> same rows) and the row indices go
+    to <name>_rows.npy.  Returns what was written, for the result line."""
+    import numpy as np
+    out_dir.mkdir(parents=True, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    rec = {"dir": str(out_dir), "files": {}}
+    for name, a in arrays.items():
+        a = a.detach().cpu().to(torch.float32)
+        if total > DUMP_LIMIT_BYTES:
+            row_bytes = a[0].numel() * 4 + 8                   # the row and its float64 index
+            keep = max(1, min(a.shape[0], int(DUMP_LIMIT_BYTES * a.numel() * 4 / total) // row_bytes))
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], keep, replace=False))
+            a = a[torch.from_numpy(rows)]
+            np.save(out_dir / f"{name}_rows.npy", rows.astype(np.float64))
+            rec["files"][f"{name}_rows.npy"] = list(rows.shape)
+        np.save(out_dir / f"{name}.npy", a.numpy())
+        rec["files"][f"{name}.npy"] = list(a.shape)
+    rec["sampled"] = total > DUMP_LIMIT_BYTES
+    return rec
+
+
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: run this same command line under torch.distributed.run, one rank per
     GPU of this node (rendezvous on 127.0.0.1, a free port), and hand its exit code back.  Rank 0 of the child prints the ONE
@@ -370,7 +395,13 @@ def main():
     ap.add_argument("--spawn", action="store_true",
                     help="go through the launcher path (torch.distributed.run, process group, RCCL gather) even at --gpus 1: the "
                          "multi-GPU code path on a one-GPU box")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (the sampled ids of all ranks, "
+                         "[samples, L_tok]) as DIR/ids.npy in float32, at most 64 MB (a fixed, seeded sample of rows beyond that): "
+                         "the same arguments give the same inputs, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # A number from this script is only as good as its environment: the launch-skipping debug switch makes
     # results wrong by construction — refuse to measure with it (the product library refuses too); every ESMDIFF_* variable and
@@ -545,6 +576,11 @@ def main():
     sync()
     t1 = time.perf_counter()
     power_rec = power.stop()
+    # the last timed step's ids, taken now: the untimed passes below reuse the engine's and the gather's buffers
+    dump_rec = None
+    if args.dump_outputs and rank == 0:
+        last_ids = torch.cat(gathered, 0).view(torch.int16) if use_dist else ids
+        dump_rec = dump_outputs(Path(args.dump_outputs), {"ids": last_ids}, seed=args.seed)
     # per-rank breakdown (no extra synchronisation inside the region: stream events, read after it)
     if stub:
         sample_ms = [1e3 * (b - a) for a, b, _ in phase_marks]
@@ -834,6 +870,8 @@ def main():
                     "(one reader + one broadcast of the 5.5 GB checkpoint) + create_s, outside the timed region"}
         out["config"]["precision"] = args.precision
         out["config"]["head_precision"] = args.head_precision
+        if dump_rec is not None:
+            out["dump_outputs"] = dump_rec
         if stub:
             out["roofline"] = None
             out["note"] = "stand-in engine on CPU over gloo: launch / process-group / reporting path only, not a measurement"

@@ -413,6 +413,12 @@ def g8_merge_pdb():
 
 
 if __name__ == "__main__":
+    # Record on MKL's CPU-independent code path: torch's float32 exp / log run on MKL's vector math, whose default path
+    # depends on the CPU (tests/recorded_math.py).  MKL reads the setting when it starts, hence a fresh process.
+    if os.environ.get("MKL_CBWR") != "COMPATIBLE":
+        import subprocess
+        sys.exit(subprocess.call([sys.executable, str(Path(__file__).resolve()), *sys.argv[1:]],
+                                   env=dict(os.environ, MKL_CBWR="COMPATIBLE")))
     if sys.argv[1:] == ["g1b"]:          # later addition: only this fixture (the others are unchanged)
         g1b_schedules_other()
         sys.exit(0)

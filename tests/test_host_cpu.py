@@ -9,9 +9,12 @@ import numpy as np
 import pytest
 import torch
 
+from tests.recorded_math import recorded_math
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
+@recorded_math
 def test_schedule_matches_reference_goldens(golden_dir):
     from esmdiff_amd.schedule import CosineNoise, LogLinearNoise, ddpm_schedule, timestep_embedding
     g = np.load(golden_dir / "g1_schedules.npz")

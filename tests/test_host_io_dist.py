@@ -554,6 +554,39 @@ def test_bench_self_spawns_ranks_world2_gloo_stub():
     assert isinstance(out["timed_region"], str) and "all_gather" in out["timed_region"]
 
 
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_dump_outputs_stub(tmp_path, gpus):
+    """`--dump-outputs DIR` writes the ids the LAST timed step returned — all ranks' samples, float32 — and nothing of the
+    untimed passes: the stand-in's ids are a pure function of (seed, global sample, position), so the file pins the step
+    (seed = --seed + steps - 1: --steps timed steps ran) and the gather.  The same arguments give the same file."""
+    from tests.standin_engine import StandinEngine
+    B, R, steps, seed = 3, 10, 3, 5
+    outs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = _run_bench(["--gpus", str(gpus), "--stub-engine", "--tiny", "--steps", str(steps), "--warmup", "1",
+                          "--samples-per-gpu", str(B), "--residues", str(R), "--seed", str(seed), "--dump-outputs", str(d)])
+        assert out["steps"] == steps and out["ms_per_step"] > 0
+        assert out["dump_outputs"]["files"] == {"ids.npy": [B * gpus, R + 2]} and not out["dump_outputs"]["sampled"]
+        outs.append(np.load(d / "ids.npy"))
+    want = StandinEngine.ids(B * gpus, R + 2, seed + steps - 1, 0).numpy().astype(np.float32)
+    assert outs[0].dtype == np.float32 and np.array_equal(outs[0], want) and np.array_equal(outs[1], outs[0])
+
+
+def test_bench_dump_outputs_cap(tmp_path, monkeypatch):
+    """Beyond the size cap the dump keeps a fixed, seeded sample of rows (indices beside it), within the cap."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    ids = torch.arange(200 * 12, dtype=torch.int64).reshape(200, 12)
+    rec = bench.dump_outputs(tmp_path / "a", {"ids": ids}, seed=0)
+    bench.dump_outputs(tmp_path / "b", {"ids": ids}, seed=0)
+    rows, got = np.load(tmp_path / "a" / "ids_rows.npy"), np.load(tmp_path / "a" / "ids.npy")
+    assert rec["sampled"] and rows.dtype == np.float64 and got.dtype == np.float32 and len(rows) == len(got) > 1
+    assert np.array_equal(got, ids.numpy()[rows.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "ids_rows.npy"))
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "a").iterdir()) <= 4000        # payload without the .npy headers
+
+
 def test_bench_fails_fast_and_refuses_debug_switches(monkeypatch):
     """`--gpus N` with fewer visible GPUs ends in seconds with one line (no launcher started); ESMDIFF_DEBUG_SKIP in the
     environment — the launch-skipping switch of -DED_DEBUG builds — makes bench.py refuse to measure at all."""

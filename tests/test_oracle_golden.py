@@ -11,6 +11,7 @@ import torch
 
 from oracle import c_oracle
 from oracle import sampler_ref as R
+from tests.recorded_math import recorded_math
 from tests.standin_net import StandinNet, standin_sigma_embedder_state
 
 torch.set_num_threads(1)
@@ -22,6 +23,7 @@ def _ulp_diff(a, b):
     return np.abs(a - b)
 
 
+@recorded_math
 def test_g1_schedules(golden_dir):
     g = np.load(golden_dir / "g1_schedules.npz")
     for T in (5, 25, 50):
@@ -38,6 +40,7 @@ def test_g1_schedules(golden_dir):
     assert abs(float(g["loglinear_mc_t_T25"][1]) - 0.95904040) < 1e-6
 
 
+@recorded_math
 def test_g1b_other_schedules(golden_dir):
     """The schedules `get_noise` can also build (noise_utils.py:75-90, :138-185), recorded from the reference at the sampler's
     T = 25 grid: oracle restatement and the product classes, bit for bit."""
@@ -73,6 +76,7 @@ def test_g1b_other_schedules(golden_dir):
         S.get_noise("sigmoid")
 
 
+@recorded_math
 def test_g2_timestep_embedding(golden_dir):
     g = np.load(golden_dir / "g2_timestep.npz")
     sig = torch.from_numpy(g["sigma"])
