@@ -57,6 +57,7 @@ EXPORTS = [
     "esmdiff_get_embeddings", "esmdiff_set_final_skip", "esmdiff_gemm_f16", "esmdiff_ddpm_step_margin", "esmdiff_forward_logits_sigmas", "esmdiff_set_small_batch_splitk",
     "esmdiff_ddpm_step_rows", "esmdiff_logit_error_stats", "esmdiff_get_build_info", "esmdiff_describe_plan", "esmdiff_set_option",
     "esmdiff_get_sequence_logits", "esmdiff_gibbs_step_rows", "esmdiff_shared_forward_batch",
+    "esmdiff_attention_f16", "esmdiff_qk_norm_rope", "esmdiff_add_layernorm", "esmdiff_geom_attention",
 ]
 OPT_STREAMS, OPT_DUAL_MIN_TOKENS = 1, 2      # esmdiff_option
 
@@ -114,6 +115,10 @@ def lib():
     L.esmdiff_branch_linear_layernorm.argtypes = [vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, ctypes.POINTER(i32), vp]
     L.esmdiff_layernorm_bf16.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.esmdiff_attention_bf16.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
+    L.esmdiff_attention_f16.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
+    L.esmdiff_qk_norm_rope.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    L.esmdiff_add_layernorm.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp]
+    L.esmdiff_geom_attention.argtypes = [vp, i32, vp, vp, vp, c_f32p, c_f32p, vp, i32, i32, i32, vp]
     L.esmdiff_set_profiling.argtypes = [vp, i32]
     L.esmdiff_get_profile.argtypes = [vp, c_f32p, ctypes.POINTER(i32)]
     L.esmdiff_set_frames.argtypes = [vp, vp, vp, vp, i32, i32, vp]

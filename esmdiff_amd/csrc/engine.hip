@@ -315,6 +315,12 @@ void prof_collect(esmdiff_engine* e) {
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// softplus of the geometric attention's per-head scales (F.softplus, threshold 20), in place: engine create and
+// esmdiff_geom_attention both go through here
+void softplus_host(float* v, int n) {
+  for (int i = 0; i < n; ++i) v[i] = v[i] > 20.f ? v[i] : log1pf(expf(v[i]));
+}
+
 int check_bl(esmdiff_engine* e, int B, int L) {
   if (B <= 0 || L <= 0) return fail(e, ESMDIFF_E_INVALID, "B=%d L=%d must be positive", B, L);
   if (B > e->cfg.max_batch || L > e->cfg.max_len)
@@ -1026,7 +1032,7 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     std::vector<float> hw(VH);
     for (float* p : {e->g_wrot, e->g_wdist}) {  // softplus once, on the host
       hipMemcpy(hw.data(), p, VH * 4, hipMemcpyDeviceToHost);
-      for (float& v : hw) v = v > 20.f ? v : log1pf(expf(v));
+      softplus_host(hw.data(), VH);
       hipMemcpy(p, hw.data(), VH * 4, hipMemcpyHostToDevice);
     }
     e->has_geom = true;
@@ -1684,6 +1690,76 @@ int esmdiff_attention_bf16(esmdiff_engine* e, const void* qkv, const float* q_ln
   HIP_TRY(e, launch_qk_norm_rope((const bf16_t*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, e->q, e->k, B, L,
                                  e->cfg.n_heads, (hipStream_t)stream));
   HIP_TRY(e, launch_attention(e->q, e->k, (const bf16_t*)qkv, (bf16_t*)ctx, B, L, e->cfg.n_heads, (hipStream_t)stream));
+  return 0;
+}
+
+int esmdiff_attention_f16(esmdiff_engine* e, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* ctx,
+                          int32_t B, int32_t L, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (!qkv || !q_ln_w || !k_ln_w || !ctx) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (!e->f16) return fail(e, ESMDIFF_E_INVALID, "esmdiff_attention_f16 needs an f16 engine");
+  if (int r = check_bl(e, B, L)) return r;
+  HIP_TRY(e, ed16::launch_qk_norm_rope((const bf16_t*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, e->q, e->k, B, L,
+                                       e->cfg.n_heads, (hipStream_t)stream));
+  HIP_TRY(e, ed16::launch_attention(e->q, e->k, (const bf16_t*)qkv, (bf16_t*)ctx, B, L, e->cfg.n_heads, (hipStream_t)stream));
+  return 0;
+}
+
+int esmdiff_qk_norm_rope(esmdiff_engine* e, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* q, void* k,
+                         int32_t B, int32_t L, int32_t H, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (!qkv || !q_ln_w || !k_ln_w || !q || !k) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (e->strict) return fail(e, ESMDIFF_E_INVALID, "esmdiff_qk_norm_rope needs a bf16 or f16 engine (this one is float32)");
+  if (H <= 0 || H > 32) return fail(e, ESMDIFF_E_INVALID, "H=%d: 1 .. 32 heads of 64", H);
+  if (int r = check_bl(e, B, L)) return r;   // the rotary tables hold max_len positions
+  HIP_TRY(e, e->f16 ? ed16::launch_qk_norm_rope((const bf16_t*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, (bf16_t*)q,
+                                                (bf16_t*)k, B, L, H, (hipStream_t)stream)
+                    : ed::launch_qk_norm_rope((const bf16_t*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, (bf16_t*)q,
+                                              (bf16_t*)k, B, L, H, (hipStream_t)stream));
+  return 0;
+}
+
+int esmdiff_add_layernorm(int32_t dtype, float* x, const void* delta, const void* delta2, int32_t write_x, const float* w,
+                          const float* b, void* y, int32_t M, int32_t D, void* stream) {
+  if (!x || !w || !y) return fail(nullptr, ESMDIFF_E_INVALID, "add_layernorm: null pointer");
+  if (dtype != 0 && dtype != 1) return fail(nullptr, ESMDIFF_E_INVALID, "add_layernorm: dtype %d (0 bf16, 1 f16)", dtype);
+  if (M <= 0 || D <= 0) return fail(nullptr, ESMDIFF_E_INVALID, "add_layernorm: M=%d D=%d must be positive", M, D);
+  const hipError_t s = dtype ? ed16::launch_add_layernorm_bf16(x, (const bf16_t*)delta, (const bf16_t*)delta2, write_x, w, b,
+                                                               (bf16_t*)y, M, D, (hipStream_t)stream)
+                             : ed::launch_add_layernorm_bf16(x, (const bf16_t*)delta, (const bf16_t*)delta2, write_x, w, b,
+                                                             (bf16_t*)y, M, D, (hipStream_t)stream);
+  if (s != hipSuccess) return fail(nullptr, s == hipErrorInvalidValue ? ESMDIFF_E_INVALID : ESMDIFF_E_HIP, "add_layernorm: %s", hipGetErrorString(s));
+  return 0;
+}
+
+int esmdiff_geom_attention(const void* P, int32_t dtype, const float* rot, const float* trans, const uint8_t* has_frame,
+                           const float* rotation_scale, const float* distance_scale, void* out, int32_t B, int32_t L,
+                           int32_t VH, void* stream) {
+  if (!P || !rot || !trans || !has_frame || !rotation_scale || !distance_scale || !out)
+    return fail(nullptr, ESMDIFF_E_INVALID, "geom_attention: null pointer");
+  if (dtype < 0 || dtype > 2) return fail(nullptr, ESMDIFF_E_INVALID, "geom_attention: dtype %d (0 bf16, 1 f16, 2 f32)", dtype);
+  if (B <= 0 || L <= 0 || VH <= 0) return fail(nullptr, ESMDIFF_E_INVALID, "geom_attention: B=%d L=%d VH=%d must be positive", B, L, VH);
+  if (L > 3200) return fail(nullptr, ESMDIFF_E_INVALID, "geom_attention: L=%d exceeds the kernel's 150 KB of LDS (L <= 3200)", L);
+  std::vector<float> hw(2 * (size_t)VH);
+  std::copy(rotation_scale, rotation_scale + VH, hw.begin());
+  std::copy(distance_scale, distance_scale + VH, hw.begin() + VH);
+  softplus_host(hw.data(), 2 * VH);
+  float* dw = nullptr;
+  if (hipMalloc(&dw, hw.size() * sizeof(float)) != hipSuccess) return fail(nullptr, ESMDIFF_E_HIP, "geom_attention: hipMalloc failed");
+  const hipStream_t st = (hipStream_t)stream;
+  hipError_t s = hipMemcpyAsync(dw, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice, st);
+  if (s == hipSuccess) {
+    if (dtype == 2)
+      s = ed::launch_geom_attention_f32((const float*)P, rot, trans, has_frame, dw, dw + VH, (float*)out, B, L, VH, st);
+    else if (dtype == 1)
+      s = ed16::launch_geom_attention((const bf16_t*)P, rot, trans, has_frame, dw, dw + VH, (bf16_t*)out, B, L, VH, st);
+    else
+      s = ed::launch_geom_attention((const bf16_t*)P, rot, trans, has_frame, dw, dw + VH, (bf16_t*)out, B, L, VH, st);
+  }
+  const hipError_t s2 = hipStreamSynchronize(st);   // synchronous: the scale buffer and the host copy die here
+  if (s == hipSuccess) s = s2;
+  hipFree(dw);
+  if (s != hipSuccess) return fail(nullptr, s == hipErrorInvalidValue ? ESMDIFF_E_INVALID : ESMDIFF_E_HIP, "geom_attention: %s", hipGetErrorString(s));
   return 0;
 }
 

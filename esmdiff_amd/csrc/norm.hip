@@ -295,7 +295,7 @@ hipError_t launch_add_partials_layernorm_bf16(float* x, const GemmPartials& P, i
 hipError_t launch_add_layernorm_bf16(float* x, const bf16_t* delta, const bf16_t* delta2, int write_x, const float* w,
                                      const float* b, bf16_t* y, int M, int D, hipStream_t stream) {
   if (M <= 0) return hipSuccess;
-  if (D % 256 != 0 || D > 2048) return hipErrorInvalidValue;
+  if (D <= 0 || D % 256 != 0 || D > 2048) return hipErrorInvalidValue;   // D = 0 would reach the 2048-wide case below
   dim3 grid((M + 3) / 4), block(256);
 #define ED_ALN(N) \
   hipLaunchKernelGGL(add_layernorm_kernel<N>, grid, block, 0, stream, x, delta, delta2, w, b, y, M, write_x)

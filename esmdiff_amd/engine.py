@@ -466,12 +466,27 @@ class Engine:
         return out
 
     def attention(self, qkv: torch.Tensor, q_ln_w: torch.Tensor, k_ln_w: torch.Tensor, B: int, L: int) -> torch.Tensor:
+        """q/k LayerNorm + rotary + attention of a qkv GEMM output: esmdiff_attention_bf16 for a bfloat16 qkv,
+        esmdiff_attention_f16 (f16 engines) for a float16 one."""
         D = self.cfg.d_model
-        assert qkv.dtype == torch.bfloat16 and qkv.shape == (B * L, 3 * D) and qkv.is_contiguous()
-        ctx = torch.empty(B * L, D, dtype=torch.bfloat16, device=self.device)
-        self._chk(self._lib.esmdiff_attention_bf16(self._h, _ptr(qkv), _ptr(q_ln_w.float().contiguous()),
-                                                   _ptr(k_ln_w.float().contiguous()), _ptr(ctx), B, L, _stream()))
+        assert qkv.dtype in (torch.bfloat16, torch.float16) and qkv.shape == (B * L, 3 * D) and qkv.is_contiguous()
+        ctx = torch.empty(B * L, D, dtype=qkv.dtype, device=self.device)
+        fn = self._lib.esmdiff_attention_bf16 if qkv.dtype == torch.bfloat16 else self._lib.esmdiff_attention_f16
+        self._chk(fn(self._h, _ptr(qkv), _ptr(q_ln_w.float().contiguous()), _ptr(k_ln_w.float().contiguous()), _ptr(ctx),
+                     B, L, _stream()))
         return ctx
+
+    def qk_norm_rope(self, qkv: torch.Tensor, q_ln_w: torch.Tensor, k_ln_w: torch.Tensor, B: int, L: int, H: int):
+        """The q/k LayerNorm + rotary kernel alone in the engine's 16-bit build (esmdiff_qk_norm_rope): qkv [B*L, 3*H*64]
+        -> (q, k) [B*L, H*64], q pre-scaled by log2(e)/8."""
+        D = H * 64
+        assert qkv.dtype == (torch.float16 if self.precision == "f16" else torch.bfloat16)
+        assert qkv.shape == (B * L, 3 * D) and qkv.is_contiguous() and q_ln_w.numel() == k_ln_w.numel() == D
+        q = torch.empty(B * L, D, dtype=qkv.dtype, device=self.device)
+        k = torch.empty_like(q)
+        self._chk(self._lib.esmdiff_qk_norm_rope(self._h, _ptr(qkv), _ptr(q_ln_w.float().contiguous()),
+                                                 _ptr(k_ln_w.float().contiguous()), _ptr(q), _ptr(k), B, L, H, _stream()))
+        return q, k
 
 
 class StructureDecoder:
@@ -735,3 +750,45 @@ def layernorm_bf16(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]) 
                                            _ptr(None if b is None else b.float().contiguous()), _ptr(y), M, D,
                                            _stream()))
     return y
+
+
+def add_layernorm(dtype: torch.dtype, x: torch.Tensor, delta: Optional[torch.Tensor], delta2: Optional[torch.Tensor],
+                  write_x: bool, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
+    """The fused residual add + LayerNorm (esmdiff_add_layernorm): v = (x + delta) + delta2 (either may be None), x = v in
+    place when write_x; returns LayerNorm(v) * w (+ b).  dtype torch.bfloat16 runs the ed build, torch.float16 the ed16
+    build; the deltas and the result are of that type."""
+    _require_gpu()
+    M, D = x.shape
+    assert dtype in (torch.bfloat16, torch.float16) and x.dtype == torch.float32 and x.is_contiguous()
+    for t in (delta, delta2):
+        assert t is None or (t.dtype == dtype and t.shape == (M, D) and t.is_contiguous())
+    y = torch.empty(M, D, dtype=dtype, device=x.device)
+    N.check(N.lib().esmdiff_add_layernorm(0 if dtype == torch.bfloat16 else 1, _ptr(x), _ptr(delta), _ptr(delta2),
+                                          int(bool(write_x)), _ptr(w.float().contiguous()),
+                                          _ptr(None if b is None else b.float().contiguous()), _ptr(y), M, D, _stream()))
+    return y
+
+GEOM_DTYPES = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}
+
+
+def geom_attention(P: torch.Tensor, rot: torch.Tensor, trans: torch.Tensor, has_frame: torch.Tensor,
+                   rotation_scale, distance_scale) -> torch.Tensor:
+    """Block 0's geometric attention alone (esmdiff_geom_attention, synchronous): P [B, L, 15*VH] proj output (bfloat16,
+    float16 or float32 selects the build), frames rot [B, L, 3, 3], trans [B, L, 3], has_frame [B, L]; the per-head scales
+    are the RAW parameters (softplus is applied inside).  Returns [B, L, 3*VH] in P's dtype."""
+    _require_gpu()
+    B, L, C = P.shape
+    VH = C // 15
+    assert C == 15 * VH and P.dtype in GEOM_DTYPES and P.is_contiguous()
+    assert rot.shape == (B, L, 3, 3) and trans.shape == (B, L, 3) and has_frame.shape == (B, L)
+    r = rot.to(device=P.device, dtype=torch.float32).contiguous()
+    t = trans.to(device=P.device, dtype=torch.float32).contiguous()
+    m = has_frame.to(device=P.device, dtype=torch.uint8).contiguous()
+    ws = [torch.as_tensor(v, dtype=torch.float32).cpu().contiguous() for v in (rotation_scale, distance_scale)]
+    assert all(v.numel() == VH for v in ws)
+    out = torch.empty(B, L, 3 * VH, dtype=P.dtype, device=P.device)
+    f32p = ctypes.POINTER(ctypes.c_float)
+    N.check(N.lib().esmdiff_geom_attention(_ptr(P), GEOM_DTYPES[P.dtype], _ptr(r), _ptr(t), _ptr(m),
+                                           ctypes.cast(ws[0].data_ptr(), f32p), ctypes.cast(ws[1].data_ptr(), f32p),
+                                           _ptr(out), B, L, VH, _stream()))
+    return out

@@ -77,6 +77,30 @@ int esmdiff_layernorm_bf16(const float* x, const float* w, const float* b, void*
 int esmdiff_attention_bf16(esmdiff_engine* eng, const void* qkv, const float* q_ln_w, const float* k_ln_w,
                            void* ctx, int32_t B, int32_t L, void* stream);
 
+/* esmdiff_attention_bf16 for f16 engines (precision = ESMDIFF_PRECISION_F16): qkv and ctx are IEEE half; refuses other engines. */
+int esmdiff_attention_f16(esmdiff_engine* eng, const void* qkv, const float* q_ln_w, const float* k_ln_w,
+                          void* ctx, int32_t B, int32_t L, void* stream);
+
+/* The q/k LayerNorm + rotary kernel alone, in the engine's 16-bit build (bf16 or f16; float32 engines are refused) with its
+ * rotary tables: qkv [B*L, 3*H*64] -> q, k [B*L, H*64] token-major, q pre-scaled by log2(e)/8.  H (1 .. 32) is explicit and
+ * independent of the engine's n_heads; L <= max_len. */
+int esmdiff_qk_norm_rope(esmdiff_engine* eng, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* q, void* k,
+                         int32_t B, int32_t L, int32_t H, void* stream);
+
+/* Fused residual add + LayerNorm (csrc/norm.hip): v = (x + delta) + delta2 (16-bit [M,D] each, either may be NULL); x = v
+ * when write_x; y [M,D] = LayerNorm(v) * w (+ b), eps 1e-5.  dtype 0: bf16 delta / y (namespace ed), 1: f16 (ed16).
+ * M > 0, D % 256 == 0, 0 < D <= 2048. */
+int esmdiff_add_layernorm(int32_t dtype, float* x, const void* delta, const void* delta2, int32_t write_x, const float* w,
+                          const float* b, void* y, int32_t M, int32_t D, void* stream);
+
+/* Block 0's geometric attention alone (csrc/geom.hip): P [B*L, 15*VH] (proj output) + frames rot f32 [B*L, 9], trans f32
+ * [B*L, 3], has_frame u8 [B*L] -> out [B*L, 3*VH].  dtype 0: P / out bf16, 1: f16, 2: f32 (the strict path's build).
+ * rotation_scale / distance_scale [VH] [host] are the RAW per-head parameters; softplus is applied as at engine create.
+ * 0 < L <= 3200 (the kernel's LDS request).  Synchronous. */
+int esmdiff_geom_attention(const void* P, int32_t dtype, const float* rot, const float* trans, const uint8_t* has_frame,
+                           const float* rotation_scale, const float* distance_scale, void* out, int32_t B, int32_t L,
+                           int32_t VH, void* stream);
+
 /* Accumulated per-section device time of the esmdiff_forward_logits/ddpm_sample calls since profiling was
  * enabled: esmdiff_set_profiling(eng, 1) brackets every launch with HIP events on the launch stream (no sync);
  * mode 2 brackets only the dominant kernel (FFN-up GEMM, section 6), cheap enough for a timed region; 0 = off. sections: 0 embed, 1 layernorm, 2 gemm_qkv,

@@ -104,6 +104,48 @@ class GeometricAttentionRef(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# The same arithmetic between proj and out_proj as one function of its inputs, in any dtype (float64 for the kernel
+# tests), split in two so that tests can plant errors between the stages.  GeometricAttentionRef.forward keeps its own
+# statement (goldens depend on its exact float32 arithmetic); tests/test_geom_cpu.py holds the two together.
+def geom_rotate_parts(p, rot, trans, heads=None):
+    """p (B, L, 15*H) proj output, rot (B, L, 3, 3), trans (B, L, 3) -> q_rot, k_rot, value, q_dist, k_dist, each
+    (B, h, L, 3) in the global frame, for the heads `heads` (a sequence of head indices; all when None)."""
+    B, L, C = p.shape
+    H = C // 15
+    h = torch.arange(H, device=p.device) if heads is None else torch.as_tensor(heads, device=p.device)
+    idx = 3 * h[:, None] + torch.arange(3, device=p.device)                        # (h, 3)
+    R = rot.to(p.dtype)
+    out = []
+    for block in range(5):                                                         # q_rot | k_rot | value | q_dist | k_dist
+        v = torch.einsum("blij,blhj->bhli", R, p[..., block * 3 * H + idx])
+        if block >= 3:
+            v = v + trans.to(p.dtype)[:, None]
+        out.append(v)
+    return tuple(out)
+
+
+def geom_attend(q_rot, k_rot, value, q_dist, k_dist, rot, mask, w_rot, w_dist, key_mask=None):
+    """Softmax over the framed keys (key_mask, default mask) of softplus'd-scale logits, back into each query's frame,
+    frameless queries zeroed -> (B, L, h*3).  w_rot / w_dist: (h,) already softplus'd."""
+    B, nh, L, _ = q_rot.shape
+    km = mask if key_mask is None else key_mask
+    rotation_term = q_rot @ k_rot.transpose(-1, -2) / math.sqrt(3)
+    distance_term = (q_dist[:, :, :, None] - k_dist[:, :, None]).norm(dim=-1) / math.sqrt(3)
+    logits = rotation_term * w_rot[None, :, None, None] - distance_term * w_dist[None, :, None, None]
+    logits = logits.masked_fill(~km[:, None, None, :], torch.finfo(logits.dtype).min)
+    out = torch.softmax(logits, dim=-1) @ value                                    # (B, h, L, 3), global frame
+    out = torch.einsum("blji,bhlj->blhi", rot.to(out.dtype), out)                  # R^T
+    return out.reshape(B, L, nh * 3).masked_fill(~mask[..., None], 0.0)
+
+
+def geom_attention_core(p, rot, trans, mask, w_rot, w_dist, heads=None):
+    """Everything of GeometricAttentionRef between proj and out_proj: p (B, L, 15*H) -> out (B, L, 3*h) in p's dtype.
+    w_rot / w_dist: the per-head scales AFTER softplus, (H,); heads: optional subset of head indices."""
+    parts = geom_rotate_parts(p, rot, trans, heads)
+    h = slice(None) if heads is None else torch.as_tensor(heads, device=p.device)
+    return geom_attend(*parts, rot, mask, w_rot.to(p.dtype)[h], w_dist.to(p.dtype)[h])
+
+# ---------------------------------------------------------------------------------------------------------------
 # RMSD after rigid alignment — the quantity north_star states the decode bar in ("decoded backbone RMSD within 1e-4 A").
 # Restates /root/reference/slm/utils/geo_utils.py: _find_rigid_alignment :91-122 (Kabsch through the SVD of the
 # covariance, R = V U^T, no reflection fix — the reference has none) and squared_deviation :58-88.  PINNED: reproduces

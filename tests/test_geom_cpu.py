@@ -94,3 +94,32 @@ def test_frameless_residues_neither_give_nor_receive():
     assert torch.equal(pre[:, 4], torch.zeros(1, 24))    # zeroed before out_proj (mask_and_zero_frameless)
     keep = [i for i in range(L) if i != 4]
     assert float((y2[:, keep] - y[:, keep]).abs().max()) < 1e-6   # nobody attends to it
+
+
+def test_geom_attention_core_equals_the_module():
+    """oracle.geom_ref.geom_attention_core (the statement the kernel tests compare against, in float64 there) is the module's
+    arithmetic between proj and out_proj: in float32 it reproduces forward's `out` to 1e-6 relative, frameless rows included."""
+    torch.manual_seed(0)
+    B, L, H = 3, 37, 16
+    m = geom_ref.GeometricAttentionRef(64, H)
+    with torch.no_grad():
+        m.rotation_scale_per_head.normal_(0, 0.5)
+        m.distance_scale_per_head.normal_(0, 0.5)
+        m.distance_scale_per_head[3] = 25.0                        # softplus's threshold branch
+    xyz = _backbone(B, L, 5)
+    xyz[:, 0] = float("nan")
+    xyz[:, 10:14] = float("inf")
+    xyz[2] = float("nan")                                           # a sample without frames
+    rot, trans, mask = build_affine3d_from_coordinates(xyz)
+    s = torch.randn(B, L, 64)
+    with torch.no_grad():
+        _, p, out = m(s, rot, trans, mask, return_parts=True)
+        w_rot = torch.nn.functional.softplus(m.rotation_scale_per_head)
+        w_dist = torch.nn.functional.softplus(m.distance_scale_per_head)
+        core = geom_ref.geom_attention_core(p, rot, trans, mask, w_rot, w_dist)
+        some = geom_ref.geom_attention_core(p.double(), rot, trans, mask, w_rot, w_dist, heads=[3, 7])
+    assert core.dtype == torch.float32 and core.shape == out.shape
+    assert float((core - out).abs().max()) <= 1e-6 * float(out.abs().max())
+    assert torch.equal(core[2], torch.zeros_like(core[2])) and torch.equal(core[:, 0], torch.zeros_like(core[:, 0]))
+    sel = out.view(B, L, H, 3)[:, :, [3, 7]].reshape(B, L, 6).double()
+    assert some.dtype == torch.float64 and float((some - sel).abs().max()) <= 1e-5 * float(sel.abs().max())

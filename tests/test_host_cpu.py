@@ -60,7 +60,8 @@ def test_library_exports_every_declared_symbol():
     assert exported == declared, exported ^ declared
     # the drop-in surface (esmdiff_hip.h) holds no per-kernel test entry point; those live in esmdiff_hip_test.h
     for name in ("esmdiff_gemm_bf16", "esmdiff_gemm_split", "esmdiff_split_rows", "esmdiff_layernorm_bf16", "esmdiff_attention_bf16",
-                 "esmdiff_branch_linear_layernorm", "esmdiff_set_profiling"):
+                 "esmdiff_branch_linear_layernorm", "esmdiff_set_profiling", "esmdiff_attention_f16", "esmdiff_qk_norm_rope",
+                 "esmdiff_add_layernorm", "esmdiff_geom_attention"):
         assert name not in re.findall(r"\b(esmdiff_[a-z0-9_]+)\s*\(", surface), name
     for name in ("esmdiff_ddpm_sample", "esmdiff_forward_logits", "esmdiff_ddpm_step", "esmdiff_gibbs_step", "esmdiff_engine_create",
                  "esmdiff_gibbs_step_rows", "esmdiff_ddpm_step_rows"):
