@@ -19,11 +19,15 @@ typedef _Float16 ed_half_t;
 #define ED_HALF_IS_F16 1
 #define ED_MFMA_32x32x16_ASM "v_mfma_f32_32x32x16_f16"
 #define ED_MFMA_32x32x16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
+#define ED_MFMA_16x16x32_ASM "v_mfma_f32_16x16x32_f16"
+#define ED_MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
 #else
 typedef __bf16 ed_half_t;
 #define ED_HALF_IS_F16 0
 #define ED_MFMA_32x32x16_ASM "v_mfma_f32_32x32x16_bf16"
 #define ED_MFMA_32x32x16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
+#define ED_MFMA_16x16x32_ASM "v_mfma_f32_16x16x32_bf16"
+#define ED_MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
 #endif
 typedef __attribute__((ext_vector_type(2))) ed_half_t ed_half2;
 typedef __attribute__((ext_vector_type(4))) ed_half_t ed_half4;

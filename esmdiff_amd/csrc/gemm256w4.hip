@@ -21,9 +21,14 @@
 //              3 of K-tile t (A pieces) and k-step 0 of K-tile t+1 (W pieces).
 //   tiles      persistent; the DMA stream runs across tile boundaries exactly as the K-tile indices continue (v = nk is
 //              K-tile 0 of the workgroup's next tile).  Needs an even number of K-tiles (K % 128 == 0).
+// The above is the SPLIT kernels' loop.  The bf16 / f16 kernels run the same tile, LDS image and DMA stream on
+// v_mfma_f32_16x16x32 (ED_W4_MFMA16, below): 8 x 8 accumulators of 16 x 16, k-steps of K = 32, the barrier between the two
+// k-steps of a K-tile.  Same cycles per FLOP and the same results bit for bit; the chip holds a higher clock on that shape
+// under the package power cap.
 #include <stdlib.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "ed_half.h"
 #include "kernels.h"
@@ -97,6 +102,23 @@ constexpr int dma_first_count() {  // instructions of a K-tile issued in k-step 
   int c = 0;
   for (int n = 0; n < 16; ++n) c += dma_idx(3, n) >= 0 ? 1 : 0;
   return c;
+}
+// Main-loop MFMA shape of the bf16 / f16 kernels (SPLIT == 0; the SPLIT kernels always run the 32x32x16_f16 loop above):
+//   ED_W4_MFMA16 1  v_mfma_f32_16x16x32: a k-step is K = 32 = 8 x 8 MFMAs of 16 cycles, a K-tile is two k-steps.  Same FLOP
+//                   per cycle and the same LDS bytes per FLOP as the 32x32x16 loop, but the chip holds a higher clock on this
+//                   shape under the power cap (EXPERIMENTS R7.1)
+//   ED_W4_MFMA16 0  the 32x32x16 loop (A/B builds)
+#ifndef ED_W4_MFMA16
+#define ED_W4_MFMA16 1
+#endif
+// 16x16x32 gap plan: fragment read behind MFMA n of a k-step (16 reads of the next k-step, one per two MFMAs over the first
+// half), and LDS-DMA instruction behind MFMA n of k-step 1 (16 per K-tile, one per four MFMAs: the same 64-cycle spacing as
+// plan 0 of the 32x32x16 loop; the whole of the next k-step 0 = 1024 matrix cycles is the landing slack)
+constexpr int m16_read(int n) { return (n < 32 && !(n & 1)) ? n >> 1 : -1; }
+constexpr int m16_dma(int n) { return (n & 3) == 1 ? n >> 2 : -1; }
+template <typename F, int... N>
+__device__ __forceinline__ void unroll_seq(F&& f, std::integer_sequence<int, N...>) {
+  (f(std::integral_constant<int, N>{}), ...);
 }
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
@@ -314,6 +336,189 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const bf16_t* __restr
 
   bool have_k0 = false;
   const uint32_t lhi = lane >> 5, lrow = lane & 31;
+
+  // ---- the 16x16x32 main loop and epilogue (ED_W4_MFMA16, SPLIT == 0).  Same LDS image, DMA stream, barriers per K-tile and
+  // tile walk as above; the wave tile is 8 x 8 accumulators of 16 x 16.  A fragment is one ds_read_b128 per lane: 16 rows x
+  // K = 32, lane l holds row l & 15, k = 8 (l >> 4) .. +7.  The DMA's chunk swizzle (row >> 1) & 7 keeps these reads free
+  // of bank conflicts too: each 16-lane group of a ds_read_b128 meets 16 distinct 16-byte bank quads. -----------------------
+  constexpr bool M16 = ED_W4_MFMA16 && SPLIT == 0;
+  const int frow16 = lane & 15, lq = lane >> 4, fsw16 = (frow16 >> 1) & 7;
+  uint32_t offA16[2], offB16[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    const uint32_t lo = frow16 * 128 + (((ks * 4 + lq) ^ fsw16) << 4);
+    offA16[ks] = lds_base + (wm * 2) * HALF_BYTES + lo;
+    offB16[ks] = lds_base + ((2 + wn) * 2) * HALF_BYTES + lo;
+  }
+  struct OpSet16 {
+    bf16x8 a[8], b[8];
+  };
+  OpSet16 X16, Y16;
+  f32x4 acc16[8][8];  // [i: A row block][j: W column block]; the TRANSPOSED 16x16 block: lane = output row, 4 columns
+#define W4_MFMA16(acc_, b_, a_, FIRST_)                                                                            \
+  do {                                                                                                             \
+    if (W4_ABL(4)) asm volatile("" : "+a"(acc_) : "v"(b_), "v"(a_));                                               \
+    else if constexpr (FIRST_) asm volatile(ED_MFMA_16x16x32_ASM " %0, %1, %2, 0" : "=a"(acc_) : "v"(b_), "v"(a_)); \
+    else asm volatile(ED_MFMA_16x16x32_ASM " %0, %1, %2, %0" : "+a"(acc_) : "v"(b_), "v"(a_));                      \
+  } while (0)
+#define W4_WAIT16(s_)                                                                                               \
+  asm volatile("s_waitcnt lgkmcnt(0)"                                                                               \
+               : "+v"(s_.a[0]), "+v"(s_.a[1]), "+v"(s_.a[2]), "+v"(s_.a[3]), "+v"(s_.a[4]), "+v"(s_.a[5]), "+v"(s_.a[6]), \
+                 "+v"(s_.a[7]), "+v"(s_.b[0]), "+v"(s_.b[1]), "+v"(s_.b[2]), "+v"(s_.b[3]), "+v"(s_.b[4]), "+v"(s_.b[5]), \
+                 "+v"(s_.b[6]), "+v"(s_.b[7]))
+  // fragment r (0..7: A row block r, 8..15: W column block r - 8) of k-step ks, stage buf, into set S
+  auto read_frag16 = [&](OpSet16& S, auto R, auto KS, auto BUF) {
+    constexpr int r = decltype(R)::value, ks = decltype(KS)::value, buf = decltype(BUF)::value;
+    const uint32_t addr = r < 8 ? offA16[ks] : offB16[ks];
+    bf16x8& dst = r < 8 ? S.a[r & 7] : S.b[r & 7];
+    W4_DSR(dst, addr, buf * HALF_BYTES + (r & 7) * 2048);
+  };
+  // One k-step: 64 MFMAs on set C (j = W block outer, i = A block inner, as the 32x32x16 loop); the 16 reads of the next
+  // k-step (NKS of stage NBUF) into set Nx; DMA: the 16 LDS-DMA instructions of K-tile dma_v into stage DMA_BUF.
+  auto kstep16 = [&](OpSet16& C, OpSet16& Nx, auto NKS, auto NBUF, auto DMA, auto DMA_BUF, auto DMA_NEXT, int dma_v,
+                     auto FIRST) {
+    unroll_seq([&](auto NC) {
+      constexpr int n = decltype(NC)::value, j_ = n >> 3, i_ = n & 7;
+      constexpr int d = decltype(DMA)::value ? m16_dma(n) : -1;
+      if constexpr (d >= 0) dma1(DMA_NEXT, d, decltype(DMA_BUF)::value, dma_v, 1);   // s_mov m0 (the MFMA is its wait state)
+      W4_MFMA16(acc16[i_][j_], C.b[j_], C.a[i_], decltype(FIRST)::value);
+      if constexpr (m16_read(n) >= 0) read_frag16(Nx, std::integral_constant<int, m16_read(n)>{}, NKS, NBUF);
+      if constexpr (d >= 0) dma1(DMA_NEXT, d, decltype(DMA_BUF)::value, dma_v, 2);
+    }, std::make_integer_sequence<int, 64>{});
+  };
+  // One K-tile at stage P.  Entry: X16 holds the fragments of (t, k-step 0).  The LDS-DMA of k-step 1 refills stage P with
+  // K-tile v (of the workgroup's next tile if NXT).
+  auto ktile16 = [&](auto P, auto NXT, int v, auto FIRST) {
+    using Q = std::integral_constant<int, 1 - decltype(P)::value>;
+    kstep16(X16, Y16, I1{}, P, TF{}, P, NXT, v, FIRST);
+    W4_WAIT16(Y16);                                    // ... and stage P is fully read by this wave
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the next K-tile (stage Q) has landed
+    __builtin_amdgcn_s_barrier();
+    // k-step 1: fragments of (t + 1, k-step 0) from stage Q (after the tile's last K-tile: the next tile's K-tile 0, or
+    // unused) + the LDS-DMA of K-tile v into stage P
+    kstep16(Y16, X16, I0{}, Q{}, TT{}, P, NXT, v, TF{});
+    W4_WAIT16(X16);
+  };
+  auto tile16 = [&]() {
+    if (!have_k0) {  // first tile of this workgroup: K-tiles 0 and 1
+#pragma unroll
+      for (int idx = 0; idx < 16; ++idx) dma1(TF{}, idx, 0, 0);
+#pragma unroll
+      for (int idx = 0; idx < 16; ++idx) dma1(TF{}, idx, 1, 1);
+      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      unroll_seq([&](auto R) { read_frag16(X16, R, I0{}, I0{}); }, std::make_integer_sequence<int, 16>{});
+      W4_WAIT16(X16);
+    }  // else: the previous tile's K loop streamed K-tiles 0 and 1 and read (K-tile 0, k-step 0) into X16
+    ktile16(I0{}, TF{}, 2, TT{});                      // first k-step writes the accumulators (C = 0)
+    ktile16(I1{}, TF{}, 3, TF{});
+    for (int t = 2; t < nk - 2; t += 2) {              // steady state: no condition anywhere
+      ktile16(I0{}, TF{}, t + 2, TF{});
+      ktile16(I1{}, TF{}, t + 3, TF{});
+    }
+    ktile16(I0{}, TT{}, 0, TF{});                      // the last two K-tiles stream the next tile's K-tiles 0 and 1
+    ktile16(I1{}, TT{}, 1, TF{});
+    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // the last MFMAs' results before the compiler's accvgpr reads
+
+    // ---- epilogue: lane = output row m, 4 consecutive columns 4 lq .. of each 16-column block.  For 16-bit outputs
+    // v_permlane16_swap pairs two blocks (lane groups 0 / 2 take 8 columns of the first, 1 / 3 of the second): one 16-byte
+    // store per lane and block pair, as many as the 32x32x16 epilogue's.
+    auto swap_rows = [](uint32_t& lo_keep, uint32_t& hi_keep) {
+      const auto r = __builtin_amdgcn_permlane16_swap(lo_keep, hi_keep, false, false);
+      lo_keep = r[0];
+      hi_keep = r[1];
+    };
+    const int pair_col = (lq & 1) * 16 + (lq >> 1) * 8;   // first column of this lane's 8 in a 32-column block pair
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (W4_ABL(16)) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) asm volatile("" ::"a"(acc16[i][j]));
+        continue;
+      }
+      const int m = m0 + wm * 128 + i * 16 + frow16;
+      const bool live = m < M && !(W4_ABL(8) && alpha != 12345.f);
+      if constexpr (EPI == ESMDIFF_EPI_SWIGLU_BF16) {
+        // W rows interleaved gate / up in blocks of 32: in 64-column group jp, gate blocks 4 jp + b pair with up blocks 4 jp + 2 + b
+#pragma unroll
+        for (int jp = 0; jp < 2; ++jp) {
+          uint32_t p[2][2];
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            float h[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) h[e] = silu_mul(acc16[i][4 * jp + b][e], acc16[i][4 * jp + 2 + b][e]);
+            p[b][0] = pack_bf16x2(h[0], h[1]);
+            p[b][1] = pack_bf16x2(h[2], h[3]);
+          }
+          swap_rows(p[0][0], p[1][0]);
+          swap_rows(p[0][1], p[1][1]);
+          bf16_t* o = reinterpret_cast<bf16_t*>(out) + (int64_t)m * ldc + (n0 + wn * 128 + jp * 64) / 2 + pair_col;
+          if (live) *reinterpret_cast<uint4*>(o) = make_uint4(p[0][0], p[0][1], p[1][0], p[1][1]);
+        }
+      } else if constexpr (EPI == ESMDIFF_EPI_BF16 || EPI == ESMDIFF_EPI_BIAS_GELU_BF16) {
+#pragma unroll
+        for (int jp = 0; jp < 4; ++jp) {
+          const int nb = n0 + wn * 128 + jp * 32;
+          uint32_t p[2][2];
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            float h[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) h[e] = acc16[i][2 * jp + b][e];
+            if constexpr (EPI == ESMDIFF_EPI_BF16) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) h[e] *= alpha;
+            } else {
+              const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + nb + b * 16 + lq * 4);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) h[e] = gelu_erf(h[e] + bb[e]);
+            }
+            p[b][0] = pack_bf16x2(h[0], h[1]);
+            p[b][1] = pack_bf16x2(h[2], h[3]);
+          }
+          swap_rows(p[0][0], p[1][0]);
+          swap_rows(p[0][1], p[1][1]);
+          bf16_t* o = reinterpret_cast<bf16_t*>(out) + (int64_t)m * ldc + nb + pair_col;
+          if (live) *reinterpret_cast<uint4*>(o) = make_uint4(p[0][0], p[0][1], p[1][0], p[1][1]);
+        }
+      } else if constexpr (EPI == ESMDIFF_EPI_RESID_F32) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const f32x4 v = acc16[i][j];
+          if (!live) continue;
+          float* o = reinterpret_cast<float*>(out) + (int64_t)m * ldc + n0 + wn * 128 + j * 16 + lq * 4;
+          f32x4 x = *reinterpret_cast<const f32x4*>(o);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) x[e] += v[e] * alpha;
+          *reinterpret_cast<f32x4*>(o) = x;
+        }
+      }
+    }
+    if constexpr (EPI == ESMDIFF_EPI_BIAS_F32) {
+      // column block outer: one bias load and one column bound (the ragged head: columns >= ldc skipped) per block; in row
+      // order the compiler hoists all eight blocks' bias and bounds out of the row loop and spills
+      // (addresses: the wave's first row as a scalar base + a 32-bit lane offset, 128 x ldc floats)
+      float* const obase = reinterpret_cast<float*>(out) + (int64_t)(m0 + wm * 128) * ldc;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int n = n0 + wn * 128 + j * 16 + lq * 4;
+        if (W4_ABL(16)) continue;
+        const bool col_ok = n + 4 <= ldc;
+        const f32x4 bb = col_ok ? *reinterpret_cast<const f32x4*>(bias + n) : f32x4{};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int r = i * 16 + frow16;
+          f32x4 v = acc16[i][j];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] += bb[e];
+          if (col_ok && m0 + wm * 128 + r < M && !(W4_ABL(8) && alpha != 12345.f))
+            *reinterpret_cast<f32x4*>(obase + (uint32_t)(r * ldc + n)) = v;
+        }
+      }
+    }
+  };
+
   for (int vt = bid; vt < n_tiles; vt += gridDim.x) {
     const int vtn = vt + gridDim.x;
     xnext = __builtin_amdgcn_readfirstlane(vtn < n_tiles ? 1 : 0);
@@ -322,178 +527,182 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const bf16_t* __restr
       tile_origin(vtn, m0n, n0n);
       set_offsets(a_offn, w_offn, m0n, n0n);
     }
-    if (!have_k0) {  // first tile of this workgroup: K-tile 0 and the first half of K-tile 1
+    if constexpr (M16) {
+      tile16();
+    } else {
+      if (!have_k0) {  // first tile of this workgroup: K-tile 0 and the first half of K-tile 1
 #pragma unroll
-      for (int idx = 0; idx < 16; ++idx) dma1(TF{}, idx, 0, 0);
+        for (int idx = 0; idx < 16; ++idx) dma1(TF{}, idx, 0, 0);
 #pragma unroll
-      for (int idx = 0; idx < dma_first_count(); ++idx) dma1(TF{}, idx, 1, 1);
-      if constexpr (dma_first_count() == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else if constexpr (dma_first_count() == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else if constexpr (dma_first_count() == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-      else if constexpr (dma_first_count() == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }  // else: the previous tile's K loop streamed them (and its last barrier made K-tile 0 visible)
-    if (!have_k0) {  // (a following tile finds the fragments of its (K-tile 0, k-step 0) in X: the last k-step of the
-                     // previous tile read them from stage 0, where the stream had already put this tile's K-tile 0)
-      read_frag(X, I0{}, I0{}, I0{});
-      read_frag(X, I1{}, I0{}, I0{});
-      read_frag(X, I2{}, I0{}, I0{});
-      read_frag(X, I3{}, I0{}, I0{});
-      read_frag(X, std::integral_constant<int, 4>{}, I0{}, I0{});
-      read_frag(X, std::integral_constant<int, 5>{}, I0{}, I0{});
-      read_frag(X, std::integral_constant<int, 6>{}, I0{}, I0{});
-      read_frag(X, std::integral_constant<int, 7>{}, I0{}, I0{});
-      W4_WAIT_LGKM0(X);
-    }
-
-    ktile(0, I0{}, TF{}, TF{}, 1, 2, TT{});          // first k-step writes the accumulators (C = 0)
-    ktile(1, I1{}, TF{}, TF{}, 2, 3, TF{});
-    for (int t = 2; t < nk - 2; t += 2) {            // steady state: no condition anywhere
-      ktile(t, I0{}, TF{}, TF{}, t + 1, t + 2, TF{});
-      ktile(t + 1, I1{}, TF{}, TF{}, t + 2, t + 3, TF{});
-    }
-    ktile(nk - 2, I0{}, TF{}, TT{}, nk - 1, 0, TF{});  // k-step 3 starts streaming the next tile's K-tile 0
-    ktile(nk - 1, I1{}, TT{}, TT{}, 0, 1, TF{});        // ... finishes it, and starts its K-tile 1
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // the last MFMAs' results before the compiler's accvgpr reads
-
-    // ---- epilogue: register-direct, as gemm256.hip (each 32x32 accumulator is the transposed output block: a lane
-    // holds one output row and 4 consecutive columns per register group; v_permlane32_swap widens that to 8) -----------
-    auto swap_halves = [](uint32_t& lo_keep, uint32_t& hi_keep) {
-      const auto r = __builtin_amdgcn_permlane32_swap(lo_keep, hi_keep, false, false);
-      lo_keep = r[0];
-      hi_keep = r[1];
-    };
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (W4_ABL(16)) {
-        asm volatile("" ::"a"(acc[i][0]), "a"(acc[i][1]), "a"(acc[i][2]), "a"(acc[i][3]));
-        continue;
+        for (int idx = 0; idx < dma_first_count(); ++idx) dma1(TF{}, idx, 1, 1);
+        if constexpr (dma_first_count() == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else if constexpr (dma_first_count() == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        else if constexpr (dma_first_count() == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+        else if constexpr (dma_first_count() == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+      }  // else: the previous tile's K loop streamed them (and its last barrier made K-tile 0 visible)
+      if (!have_k0) {  // (a following tile finds the fragments of its (K-tile 0, k-step 0) in X: the last k-step of the
+                       // previous tile read them from stage 0, where the stream had already put this tile's K-tile 0)
+        read_frag(X, I0{}, I0{}, I0{});
+        read_frag(X, I1{}, I0{}, I0{});
+        read_frag(X, I2{}, I0{}, I0{});
+        read_frag(X, I3{}, I0{}, I0{});
+        read_frag(X, std::integral_constant<int, 4>{}, I0{}, I0{});
+        read_frag(X, std::integral_constant<int, 5>{}, I0{}, I0{});
+        read_frag(X, std::integral_constant<int, 6>{}, I0{}, I0{});
+        read_frag(X, std::integral_constant<int, 7>{}, I0{}, I0{});
+        W4_WAIT_LGKM0(X);
       }
-      const int m = m0 + wm * 128 + i * 32 + lrow;
-      const bool live = m < M && !(W4_ABL(8) && alpha != 12345.f);
-      if constexpr (SPLIT && EPI == 4) {
-        // F32_SPLIT FFN-up with the SwiGLU fused (W rows interleaved gate / up in blocks of 32, as in the bf16 path): mid =
-        // silu(g) * u in f32, written as f32 [M, FH] (ldc >= FH).  exp and the reciprocal are the hardware's (1 ulp each).
-        // The split row the FFN-down GEMM reads is made from it by split_rows_kernel with the row's OWN power-of-two scale
-        // (r05).  r04 wrote the split row right here with one scale per layer taken from the a-priori bound |mid| <= B^2:
-        // on weights with trained statistics (LayerNorm gains of 30, FFN units with 50x row norm) that bound sits 2^22 ..
-        // 2^33 above the typical element, the f16 pair underflows, and the engine's logits were 100x further from a float64
-        // evaluation than the exact-f32 engine's (profiles/r05_split_vs_f64.txt).
-        const float sc = (rs && m < M) ? rs[m] * alpha : alpha;
+
+      ktile(0, I0{}, TF{}, TF{}, 1, 2, TT{});          // first k-step writes the accumulators (C = 0)
+      ktile(1, I1{}, TF{}, TF{}, 2, 3, TF{});
+      for (int t = 2; t < nk - 2; t += 2) {            // steady state: no condition anywhere
+        ktile(t, I0{}, TF{}, TF{}, t + 1, t + 2, TF{});
+        ktile(t + 1, I1{}, TF{}, TF{}, t + 2, t + 3, TF{});
+      }
+      ktile(nk - 2, I0{}, TF{}, TT{}, nk - 1, 0, TF{});  // k-step 3 starts streaming the next tile's K-tile 0
+      ktile(nk - 1, I1{}, TT{}, TT{}, 0, 1, TF{});        // ... finishes it, and starts its K-tile 1
+      asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // the last MFMAs' results before the compiler's accvgpr reads
+
+      // ---- epilogue: register-direct, as gemm256.hip (each 32x32 accumulator is the transposed output block: a lane
+      // holds one output row and 4 consecutive columns per register group; v_permlane32_swap widens that to 8) -----------
+      auto swap_halves = [](uint32_t& lo_keep, uint32_t& hi_keep) {
+        const auto r = __builtin_amdgcn_permlane32_swap(lo_keep, hi_keep, false, false);
+        lo_keep = r[0];
+        hi_keep = r[1];
+      };
 #pragma unroll
-        for (int jp = 0; jp < 2; ++jp)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float gt = acc[i][2 * jp][g * 4 + e] * sc, up = acc[i][2 * jp + 1][g * 4 + e] * sc;
-              v[e] = gt * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gt * -1.44269504088896341f)) * up;
-            }
-            if (!live) continue;
-            float* o = reinterpret_cast<float*>(out) + (int64_t)m * ldc + (n0 + wn * 128 + jp * 64) / 2 + g * 8 + lhi * 4;
-            *reinterpret_cast<f32x4*>(o) = v;
-          }
-      } else if constexpr (SPLIT) {   // f32 outputs of the split linears: acc * (row scale * weight scale), both powers of two
-        const float sc = (rs && m < M) ? rs[m] * alpha : alpha;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            // no column bound: the launcher requires ldc >= N (a bound check per 8-column group becomes 16 hoisted lane
-            // masks or scalar flags = 32+ SGPRs, the kernel spills, and hipcc's v_readlane reloads land in front of the
-            // inline-asm LDS-DMA that reads them: a VALU-writes-SGPR -> VMEM hazard nobody pads inside asm)
-            const int n = n0 + wn * 128 + j * 32 + g * 8 + lhi * 4;
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[i][j][g * 4 + e] * sc;
-            if (!live) continue;
-            float* o = reinterpret_cast<float*>(out) + (int64_t)m * ldc + n;
-            if constexpr (EPI == ESMDIFF_F32EPI_RESID_DIV) {   // x = x + r / scaling_factor (esm's own expression)
-              f32x4 x = *reinterpret_cast<const f32x4*>(o);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) x[e] = x[e] + v[e] / div;
-              *reinterpret_cast<f32x4*>(o) = x;
-            } else {
-              if constexpr (EPI != ESMDIFF_F32EPI_STORE) {   // 3: the launcher's code for STORE with a bias
-                const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += bb[e];
-              }
-              *reinterpret_cast<f32x4*>(o) = v;
-            }
-          }
-      } else if constexpr (EPI == ESMDIFF_EPI_SWIGLU_BF16) {
-#pragma unroll
-        for (int jp = 0; jp < 2; ++jp) {
-          bf16_t* orow = reinterpret_cast<bf16_t*>(out) + (int64_t)m * ldc + (n0 + wn * 128 + jp * 64) / 2 + lhi * 8;
-#pragma unroll
-          for (int gp = 0; gp < 2; ++gp) {
-            float h[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) h[e] = silu_mul(acc[i][2 * jp][gp * 8 + e], acc[i][2 * jp + 1][gp * 8 + e]);
-            uint32_t p0 = pack_bf16x2(h[0], h[1]), p1 = pack_bf16x2(h[2], h[3]);
-            uint32_t q0 = pack_bf16x2(h[4], h[5]), q1 = pack_bf16x2(h[6], h[7]);
-            swap_halves(p0, q0);
-            swap_halves(p1, q1);
-            if (live) *reinterpret_cast<uint4*>(orow + gp * 16) = make_uint4(p0, p1, q0, q1);
-          }
+      for (int i = 0; i < 4; ++i) {
+        if (W4_ABL(16)) {
+          asm volatile("" ::"a"(acc[i][0]), "a"(acc[i][1]), "a"(acc[i][2]), "a"(acc[i][3]));
+          continue;
         }
-      } else if constexpr (EPI == ESMDIFF_EPI_BF16 || EPI == ESMDIFF_EPI_BIAS_GELU_BF16) {
+        const int m = m0 + wm * 128 + i * 32 + lrow;
+        const bool live = m < M && !(W4_ABL(8) && alpha != 12345.f);
+        if constexpr (SPLIT && EPI == 4) {
+          // F32_SPLIT FFN-up with the SwiGLU fused (W rows interleaved gate / up in blocks of 32, as in the bf16 path): mid =
+          // silu(g) * u in f32, written as f32 [M, FH] (ldc >= FH).  exp and the reciprocal are the hardware's (1 ulp each).
+          // The split row the FFN-down GEMM reads is made from it by split_rows_kernel with the row's OWN power-of-two scale
+          // (r05).  r04 wrote the split row right here with one scale per layer taken from the a-priori bound |mid| <= B^2:
+          // on weights with trained statistics (LayerNorm gains of 30, FFN units with 50x row norm) that bound sits 2^22 ..
+          // 2^33 above the typical element, the f16 pair underflows, and the engine's logits were 100x further from a float64
+          // evaluation than the exact-f32 engine's (profiles/r05_split_vs_f64.txt).
+          const float sc = (rs && m < M) ? rs[m] * alpha : alpha;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int nb = n0 + wn * 128 + j * 32;
-          bf16_t* orow = reinterpret_cast<bf16_t*>(out) + (int64_t)m * ldc + nb + lhi * 8;
+          for (int jp = 0; jp < 2; ++jp)
 #pragma unroll
-          for (int gp = 0; gp < 2; ++gp) {
-            float h[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) h[e] = acc[i][j][gp * 8 + e];
-            if constexpr (EPI == ESMDIFF_EPI_BF16) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) h[e] *= alpha;
-            } else {
-              const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + nb + gp * 16 + lhi * 4);
-              const f32x4 b1 = *reinterpret_cast<const f32x4*>(bias + nb + gp * 16 + 8 + lhi * 4);
+            for (int g = 0; g < 4; ++g) {
+              f32x4 v;
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                h[e] = gelu_erf(h[e] + b0[e]);
-                h[4 + e] = gelu_erf(h[4 + e] + b1[e]);
+                const float gt = acc[i][2 * jp][g * 4 + e] * sc, up = acc[i][2 * jp + 1][g * 4 + e] * sc;
+                v[e] = gt * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gt * -1.44269504088896341f)) * up;
               }
+              if (!live) continue;
+              float* o = reinterpret_cast<float*>(out) + (int64_t)m * ldc + (n0 + wn * 128 + jp * 64) / 2 + g * 8 + lhi * 4;
+              *reinterpret_cast<f32x4*>(o) = v;
             }
-            uint32_t p0 = pack_bf16x2(h[0], h[1]), p1 = pack_bf16x2(h[2], h[3]);
-            uint32_t q0 = pack_bf16x2(h[4], h[5]), q1 = pack_bf16x2(h[6], h[7]);
-            swap_halves(p0, q0);
-            swap_halves(p1, q1);
-            if (live) *reinterpret_cast<uint4*>(orow + gp * 16) = make_uint4(p0, p1, q0, q1);
-          }
-        }
-      } else {  // f32 outputs
+        } else if constexpr (SPLIT) {   // f32 outputs of the split linears: acc * (row scale * weight scale), both powers of two
+          const float sc = (rs && m < M) ? rs[m] * alpha : alpha;
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+          for (int j = 0; j < 4; ++j)
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int n = n0 + wn * 128 + j * 32 + g * 8 + lhi * 4;
-            f32x4 v;
+            for (int g = 0; g < 4; ++g) {
+              // no column bound: the launcher requires ldc >= N (a bound check per 8-column group becomes 16 hoisted lane
+              // masks or scalar flags = 32+ SGPRs, the kernel spills, and hipcc's v_readlane reloads land in front of the
+              // inline-asm LDS-DMA that reads them: a VALU-writes-SGPR -> VMEM hazard nobody pads inside asm)
+              const int n = n0 + wn * 128 + j * 32 + g * 8 + lhi * 4;
+              f32x4 v;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[i][j][g * 4 + e];
-            if (!live) continue;
-            float* o = reinterpret_cast<float*>(out) + (int64_t)m * ldc + n;
-            if constexpr (EPI == ESMDIFF_EPI_RESID_F32) {
-              f32x4 x = *reinterpret_cast<const f32x4*>(o);
+              for (int e = 0; e < 4; ++e) v[e] = acc[i][j][g * 4 + e] * sc;
+              if (!live) continue;
+              float* o = reinterpret_cast<float*>(out) + (int64_t)m * ldc + n;
+              if constexpr (EPI == ESMDIFF_F32EPI_RESID_DIV) {   // x = x + r / scaling_factor (esm's own expression)
+                f32x4 x = *reinterpret_cast<const f32x4*>(o);
 #pragma unroll
-              for (int e = 0; e < 4; ++e) x[e] += v[e] * alpha;
-              *reinterpret_cast<f32x4*>(o) = x;
-            } else {
-              if (n + 4 <= ldc) {
-                const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + n);
+                for (int e = 0; e < 4; ++e) x[e] = x[e] + v[e] / div;
+                *reinterpret_cast<f32x4*>(o) = x;
+              } else {
+                if constexpr (EPI != ESMDIFF_F32EPI_STORE) {   // 3: the launcher's code for STORE with a bias
+                  const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + n);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += bb[e];
+                  for (int e = 0; e < 4; ++e) v[e] += bb[e];
+                }
                 *reinterpret_cast<f32x4*>(o) = v;
               }
             }
+        } else if constexpr (EPI == ESMDIFF_EPI_SWIGLU_BF16) {
+#pragma unroll
+          for (int jp = 0; jp < 2; ++jp) {
+            bf16_t* orow = reinterpret_cast<bf16_t*>(out) + (int64_t)m * ldc + (n0 + wn * 128 + jp * 64) / 2 + lhi * 8;
+#pragma unroll
+            for (int gp = 0; gp < 2; ++gp) {
+              float h[8];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) h[e] = silu_mul(acc[i][2 * jp][gp * 8 + e], acc[i][2 * jp + 1][gp * 8 + e]);
+              uint32_t p0 = pack_bf16x2(h[0], h[1]), p1 = pack_bf16x2(h[2], h[3]);
+              uint32_t q0 = pack_bf16x2(h[4], h[5]), q1 = pack_bf16x2(h[6], h[7]);
+              swap_halves(p0, q0);
+              swap_halves(p1, q1);
+              if (live) *reinterpret_cast<uint4*>(orow + gp * 16) = make_uint4(p0, p1, q0, q1);
+            }
           }
+        } else if constexpr (EPI == ESMDIFF_EPI_BF16 || EPI == ESMDIFF_EPI_BIAS_GELU_BF16) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int nb = n0 + wn * 128 + j * 32;
+            bf16_t* orow = reinterpret_cast<bf16_t*>(out) + (int64_t)m * ldc + nb + lhi * 8;
+#pragma unroll
+            for (int gp = 0; gp < 2; ++gp) {
+              float h[8];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) h[e] = acc[i][j][gp * 8 + e];
+              if constexpr (EPI == ESMDIFF_EPI_BF16) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) h[e] *= alpha;
+              } else {
+                const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + nb + gp * 16 + lhi * 4);
+                const f32x4 b1 = *reinterpret_cast<const f32x4*>(bias + nb + gp * 16 + 8 + lhi * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                  h[e] = gelu_erf(h[e] + b0[e]);
+                  h[4 + e] = gelu_erf(h[4 + e] + b1[e]);
+                }
+              }
+              uint32_t p0 = pack_bf16x2(h[0], h[1]), p1 = pack_bf16x2(h[2], h[3]);
+              uint32_t q0 = pack_bf16x2(h[4], h[5]), q1 = pack_bf16x2(h[6], h[7]);
+              swap_halves(p0, q0);
+              swap_halves(p1, q1);
+              if (live) *reinterpret_cast<uint4*>(orow + gp * 16) = make_uint4(p0, p1, q0, q1);
+            }
+          }
+        } else {  // f32 outputs
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              const int n = n0 + wn * 128 + j * 32 + g * 8 + lhi * 4;
+              f32x4 v;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] = acc[i][j][g * 4 + e];
+              if (!live) continue;
+              float* o = reinterpret_cast<float*>(out) + (int64_t)m * ldc + n;
+              if constexpr (EPI == ESMDIFF_EPI_RESID_F32) {
+                f32x4 x = *reinterpret_cast<const f32x4*>(o);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x[e] += v[e] * alpha;
+                *reinterpret_cast<f32x4*>(o) = x;
+              } else {
+                if (n + 4 <= ldc) {
+                  const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + n);
+#pragma unroll
+                  for (int e = 0; e < 4; ++e) v[e] += bb[e];
+                  *reinterpret_cast<f32x4*>(o) = v;
+                }
+              }
+            }
+        }
       }
     }
 
