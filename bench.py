@@ -10,11 +10,18 @@ slm/sample_esmdiff.py:137-233).  Inputs (tokens, weights) are resident in HBM wh
     python bench.py [--gpus N --steps K --warmup W]        (N > 1 without a launcher: re-executes itself under
                                                             torch.distributed.run, one rank per GPU, still ONE JSON line)
     python bench.py ... --dump-outputs DIR                 (also writes the last timed step's ids to DIR/ids.npy)
+    python bench.py ... --full                             (also every labelled extra leg, after the timed steps)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0).  Extra objects:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; the labelled extra legs run only
+with --full.  Prints ONE JSON line (rank 0).  Extra objects:
   roofline      dominant kernel (FFN-up GEMM, bf16 MFMA): algorithmic FLOP per launch / mean launch duration
                 measured with HIP events on the launch stream inside the timed region.
+With --full only (each leg runs after the timed region and has its own --no-* switch):
+  sections_ms_per_forward, roofline.exclusive
+                one extra untimed single-stream step with per-section HIP events.
+  exact_shortcuts, alt_precisions, certified, certified_gibbs
+                the same workload with the exact shortcuts, at the other precisions and through the certified samplers.
   cpu_baseline  the oracle (torch-CPU float32 restatement, oracle/) timed on this box's host cores on a
                 bounded sample; kind = "port" (the reference's own Python cannot run here: esm==3.0.4 absent).
 """
@@ -235,10 +242,11 @@ def roofline_report(args, cfg, B, L, n_fwd_sample, prof_dom, prof):
                                  follows from a committed rocprof artifact and does not move with bookkeeping
       roofline.union             labelled extra, device level: FFN-up FLOP of ALL streams / the UNION of the launches' busy
                                  intervals on the device timeline (no instant counted twice)
-      roofline.exclusive         labelled extra: the same kernel ALONE on the GPU at the full M (single-stream pass, untimed)"""
+      roofline.exclusive         labelled extra: the same kernel ALONE on the GPU at the full M (single-stream pass, untimed)
+    `prof` is that single-stream pass's profile, None when it did not run: then the figures that need it are left out."""
     M = B * L
     timed = prof_dom["gemm_ffn_up"]["launches"] > 0
-    up = prof_dom["gemm_ffn_up"] if timed else prof["gemm_ffn_up"]
+    up = prof_dom["gemm_ffn_up"] if timed else (prof or {}).get("gemm_ffn_up", {"ms": 0.0, "launches": 0})
     expect = (args.steps if timed else 1) * n_fwd_sample * cfg.n_layers
     parts = max(1, round(up["launches"] / expect))
     flop_up_full = 2.0 * M * cfg.d_model * 2 * cfg.ffn_hidden
@@ -251,16 +259,6 @@ def roofline_report(args, cfg, B, L, n_fwd_sample, prof_dom, prof):
     else:                                                       # no timed events (--no-profile): single-stream sections
         union_ms = up["ms"]
     ach = flop_up * up["launches"] / (union_ms * 1e-3) / 1e12 if union_ms > 0 else 0.0
-    ex = prof["gemm_ffn_up"]
-    ms_ex = ex["ms"] / max(ex["launches"], 1)
-    ach_ex = flop_up_full / (ms_ex * 1e-3) / 1e12 if ms_ex > 0 else 0.0
-    sections = {k: v for k, v in prof.items() if k != "gemm_ffn_up_union"}
-    gemm_ms = sum(sections[s]["ms"] for s in ("gemm_qkv", "gemm_out", "gemm_ffn_up", "gemm_ffn_down", "head"))
-    tot_ms = sum(v["ms"] for v in sections.values())
-    lin_flop_fwd = M * (cfg.n_layers * (2 * cfg.d_model * (3 * cfg.d_model + cfg.d_model + 2 * cfg.ffn_hidden)
-                                        + 2 * cfg.ffn_hidden * cfg.d_model)
-                        + 2 * cfg.d_model * cfg.d_model + 2 * cfg.d_model * cfg.n_structure_heads)
-    n_fwd = n_fwd_sample                                        # the breakdown pass is one step
     # roofline.traffic: the newest profiles/r*_gemm_traffic.json written by tools/pmc_traffic.py (separate rocprofv3 --pmc passes of
     # this kernel at this M) — reported only while the kernel source it was measured on is the source of the library in use
     traffic, traffic_note = None, "no PMC pass on record (tools/pmc_traffic.py measures it on the GPU box)"
@@ -301,15 +299,27 @@ def roofline_report(args, cfg, B, L, n_fwd_sample, prof_dom, prof):
                                        "intervals (engine-side merge of the event intervals; tools/rocprof_summary.py --union "
                                        "recomputes it from a kernel trace)",
                                "union_busy_ms": round(union_ms, 3), "achieved": round(ach, 1), "frac": round(ach / PEAK_BF16_TFLOPS, 4)},
-                     "union_busy_ms": round(union_ms, 3),
-                     "exclusive": {"what": "labelled extra: same kernel alone on the GPU at M=%d (single-stream breakdown pass, HIP events)" % M,
-                                   "launch_ms": round(ms_ex, 4), "achieved": round(ach_ex, 1),
-                                   "frac": round(ach_ex / PEAK_BF16_TFLOPS, 4)},
-                     "all_gemm_tflops": round(lin_flop_fwd * n_fwd / (gemm_ms * 1e-3) / 1e12, 1) if gemm_ms else None},
-        "sections_ms_per_forward": {k: round(v["ms"] / n_fwd, 3) for k, v in sections.items()},
-        "sections_note": "per-launch HIP events of one extra untimed single-stream step; roofline.* is from the timed region",
-        "device_ms_per_forward": round(tot_ms / n_fwd, 3),
+                     "union_busy_ms": round(union_ms, 3)},
     }
+    if prof is not None:
+        ex = prof["gemm_ffn_up"]
+        ms_ex = ex["ms"] / max(ex["launches"], 1)
+        ach_ex = flop_up_full / (ms_ex * 1e-3) / 1e12 if ms_ex > 0 else 0.0
+        sections = {k: v for k, v in prof.items() if k != "gemm_ffn_up_union"}
+        gemm_ms = sum(sections[s]["ms"] for s in ("gemm_qkv", "gemm_out", "gemm_ffn_up", "gemm_ffn_down", "head"))
+        tot_ms = sum(v["ms"] for v in sections.values())
+        lin_flop_fwd = M * (cfg.n_layers * (2 * cfg.d_model * (3 * cfg.d_model + cfg.d_model + 2 * cfg.ffn_hidden)
+                                            + 2 * cfg.ffn_hidden * cfg.d_model)
+                            + 2 * cfg.d_model * cfg.d_model + 2 * cfg.d_model * cfg.n_structure_heads)
+        n_fwd = n_fwd_sample                                    # the breakdown pass is one step
+        rep["roofline"]["exclusive"] = {"what": "labelled extra: same kernel alone on the GPU at M=%d (single-stream breakdown pass, "
+                                                "HIP events)" % M,
+                                        "launch_ms": round(ms_ex, 4), "achieved": round(ach_ex, 1),
+                                        "frac": round(ach_ex / PEAK_BF16_TFLOPS, 4)}
+        rep["roofline"]["all_gemm_tflops"] = round(lin_flop_fwd * n_fwd / (gemm_ms * 1e-3) / 1e12, 1) if gemm_ms else None
+        rep["sections_ms_per_forward"] = {k: round(v["ms"] / n_fwd, 3) for k, v in sections.items()}
+        rep["sections_note"] = "per-launch HIP events of one extra untimed single-stream step; roofline.* is from the timed region"
+        rep["device_ms_per_forward"] = round(tot_ms / n_fwd, 3)
     if passes > 1:   # the figure above counts the ALGORITHMIC product once; the matrix pipes do `passes` times that
         rep["roofline"]["mfma_work_frac"] = round(passes * ach_launch / PEAK_BF16_TFLOPS, 4)
     return rep
@@ -364,13 +374,17 @@ def main():
     ap.add_argument("--residues", type=int, default=256)
     ap.add_argument("--num-steps", type=int, default=25)
     ap.add_argument("--tiny", action="store_true", help="small model (debug only; prints data=debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every labelled extra leg: the untimed breakdown step, the exact "
+                         "shortcuts, the other precisions, the certified samplers and the CPU baseline (each has a --no-* "
+                         "switch below); a plain run does none of them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity_spot*")
     ap.add_argument("--no-profile", action="store_true", help="debug: timed region without the in-stream HIP events")
     ap.add_argument("--no-breakdown", action="store_true",
-                    help="skip the extra UNTIMED single-stream step that produces sections_ms_per_forward and roofline.exclusive: under "
-                         "rocprofv3 every launch of the dominant kernel is then a launch of the timed configuration, so the trace's "
-                         "average for it is directly the figure roofline.frac is computed from")
-    ap.add_argument("--no-step0-sharing", action="store_true", help="skip the second, labelled run with exact step-0 sharing")
+                    help="--full without the extra UNTIMED single-stream step that produces sections_ms_per_forward and "
+                         "roofline.exclusive: under rocprofv3 every launch of the dominant kernel is then a launch of the timed "
+                         "configuration, so the trace's average for it is directly the figure roofline.frac is computed from")
+    ap.add_argument("--no-step0-sharing", action="store_true", help="--full without the labelled run with exact step-0 sharing")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--mode", choices=["ddpm", "gibbs"], default="ddpm",
                     help="gibbs: the CLI's default mode (entropy-ordered unmasking, temperature 1.4, top-p 0.9: "
@@ -386,12 +400,13 @@ def main():
                          "float32-grade paths whose ids equal the float32 chain's")
     ap.add_argument("--head-precision", choices=["bf16", "f32"], default="bf16",
                     help="bf16 engine only: final LayerNorm + output head in float32 grade (esmdiff_config.head_precision)")
-    ap.add_argument("--no-head-f32-leg", action="store_true", help="skip the second, labelled run with the float32-grade head")
+    ap.add_argument("--no-head-f32-leg", action="store_true",
+                    help="--full without the labelled runs at the other precisions (and so without the certified samplers)")
     ap.add_argument("--checkpoint-fanout", choices=["auto", "on", "off"], default="auto",
                     help="load the weights the way a real run does: rank 0 writes the synthetic state dict to a file (untimed), then "
                          "rank 0 READS it and every rank receives the tensors by one broadcast (esmdiff_amd.dist.broadcast_state_dict); "
                          "per_rank reports load_s next to create_s.  auto: on under a launcher (N > 1 or --spawn), off otherwise")
-    ap.add_argument("--alt-steps", type=int, default=5, help="timed steps of every labelled extra leg (alt_precisions, certified); >= 5")
+    ap.add_argument("--alt-steps", type=int, default=5, help="timed steps of every labelled extra leg of --full (alt_precisions, certified); >= 5")
     ap.add_argument("--spawn", action="store_true",
                     help="go through the launcher path (torch.distributed.run, process group, RCCL gather) even at --gpus 1: the "
                          "multi-GPU code path on a one-GPU box")
@@ -604,9 +619,10 @@ def main():
     elapsed = float(elapsed.item())
     prof_dom = eng.get_profile()
     sync_local = (lambda: None) if stub else (lambda: torch.cuda.synchronize(dev))
-    if args.no_breakdown:
-        prof = {k: {"ms": 0.0, "launches": 0} for k in prof_dom}
-    else:
+    # Everything from here to the result line that runs the GPU or the host again is a labelled extra of --full: a plain run
+    # goes straight to the line.
+    prof = None
+    if args.full and not args.no_breakdown:
         eng.set_profiling(1)                                     # one extra, UNTIMED pass for the per-section breakdown
         one_step(2000)
         sync_local()
@@ -618,7 +634,7 @@ def main():
     # noise-removal skip (forward T + 1 only for samples that still hold a MASK); ids are bit-identical to the run above
     # (tests: test_step0_sharing_is_exact, test_final_skip_is_exact).  FLOP accounting uses the rows really executed.
     shared_rec = None
-    if world == 1 and not stub and not args.no_step0_sharing:
+    if args.full and world == 1 and not stub and not args.no_step0_sharing:
         eng.set_step0_sharing(True)
         if args.mode == "ddpm":
             eng.set_final_skip(True)                             # the other exact shortcut (esmdiff_set_final_skip)
@@ -653,7 +669,8 @@ def main():
     # Their logit errors against the oracle are parity_spot_<name>; the id-level figures (flips per draw against the float32
     # chain at configs[1]'s full size) are measured by tests/test_gpu_strict.py and recorded in profiles/r04_parity_strict.json.
     alt_recs, alt_engines = {}, {}
-    if world == 1 and not stub and args.precision == "bf16" and args.head_precision == "bf16" and not args.no_head_f32_leg:
+    if (args.full and world == 1 and not stub and args.precision == "bf16" and args.head_precision == "bf16"
+            and not args.no_head_f32_leg):
         from esmdiff_amd.engine import Engine
         ks = max(5, args.alt_steps)
 
@@ -888,7 +905,7 @@ def main():
                 shared_rec["flop_per_sample_executed"] = flops_forward_per_sample(L, cfg) * shared_rec["forwards_executed_per_sample"]
                 shared_rec["mfma_frac_whole_job"] = round(shared_rec["value"] * shared_rec["flop_per_sample_executed"] / (PEAK_BF16_TFLOPS * 1e12), 4)
                 out["exact_shortcuts"] = shared_rec
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             try:
                 out["cpu_baseline"], spots = cpu_baseline(cfg, sd, L, T, {"value": eng, **alt_engines})
                 out["parity_spot"] = spots.get("value")

@@ -1,6 +1,6 @@
 #!/bin/bash
 # End-of-phase measurement records (run on the GPU box):  bash scratch/profile_round.sh r02c
-# 1. the default bench line (configs[1], with cpu_baseline + parity_spot)          -> gpurun_out/<tag>_bench.json
+# 1. the full bench line (configs[1], with cpu_baseline + parity_spot)             -> $out/<tag>_bench.json
 # 2. rocprofv3 --kernel-trace of configs[1], [3], [4]                               -> gpurun_out/<tag>_cfg{1,3,4}_kernel_stats.txt
 # 3. PMC passes over three launches of the dominant kernel (FFN-up GEMM), one counter group per run, kernel-trace only:
 #    SQ_VALU_MFMA_BUSY_CYCLES + GRBM_GUI_ACTIVE, FETCH_SIZE, WRITE_SIZE at M = 25800 and 12900 -> gpurun_out/<tag>_pmc_*.txt
@@ -8,7 +8,7 @@ tag=${1:-r02}
 out=$PWD/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 R=$OLDPWD
-python $R/bench.py --steps 5 --warmup 1 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python $R/bench.py --steps 5 --warmup 1 --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 prof() {  # name, bench args...
   name=$1; shift
   rm -rf /tmp/prof_$name
@@ -16,12 +16,12 @@ prof() {  # name, bench args...
   db=$(find /tmp/prof_$name -name "*.db" | head -1)
   python $R/tools/rocprof_summary.py $db $out/${tag}_${name}_kernel_stats.txt --lib $R/esmdiff_amd/lib/libesmdiff_hip.so --union "gemm256w4_kernel<2, 0>" > /dev/null
 }
-# (the profiled runs skip the labelled extra legs: one engine, the headline workload only)
+# (the profiled runs skip the labelled extra legs: one engine, the headline workload only; --full for the breakdown step)
 prof cfg1 --no-head-f32-leg --no-step0-sharing --no-breakdown
-prof cfg3 --residues 1024 --samples-per-gpu 32 --no-head-f32-leg --no-step0-sharing
-prof cfg4 --num-steps 50 --inpaint 96:160 --no-head-f32-leg --no-step0-sharing
+prof cfg3 --full --residues 1024 --samples-per-gpu 32 --no-head-f32-leg --no-step0-sharing
+prof cfg4 --full --num-steps 50 --inpaint 96:160 --no-head-f32-leg --no-step0-sharing
 prof cfg1_f16 --precision f16 --no-head-f32-leg --no-step0-sharing --no-breakdown
-prof cfg1_f32split --precision f32_split --steps 1 --warmup 1 --no-step0-sharing
+prof cfg1_f32split --full --precision f32_split --steps 1 --warmup 1 --no-step0-sharing
 for mm in 25800 12900; do
   for grp in "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do
     n=$(echo $grp | cut -d' ' -f1)

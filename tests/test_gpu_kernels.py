@@ -1504,20 +1504,44 @@ def test_engine_error_behaviour(tiny):
     assert out.shape == (1, 5) and int((out == MASK).sum()) == 0
 
 
-def test_bench_line_contract(tmp_path):
-    """bench.py's single JSON line as the driver reads it (small model, seconds): every field of the contract, the roofline
-    and cpu_baseline objects, and that nothing else is printed on stdout."""
+def _bench_line(extra):
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--tiny", "--steps", "2", "--warmup", "1",
-                        "--samples-per-gpu", "6", "--residues", "40"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--samples-per-gpu", "6", "--residues", "40"] + extra, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+# the objects only `bench.py --full` produces: each comes from a run of its own after the timed steps
+FULL_ONLY_KEYS = ("sections_ms_per_forward", "device_ms_per_forward", "exact_shortcuts", "alt_precisions", "certified",
+                  "certified_gibbs", "cpu_baseline", "parity_spot")
+
+
+def test_bench_plain_line_is_lean():
+    """A plain `bench.py` line (small model, seconds): the headline fields and the roofline of the timed region, and none of the
+    figures that take runs of their own — those are `--full`'s."""
+    d = _bench_line([])
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("steps", int), ("warmup", int), ("ms_per_step", float),
+                 ("higher_is_better", bool), ("dtype", str)):
+        assert isinstance(d[k], t), (k, d[k])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["value"] - 6 * 2 / (d["ms_per_step"] * 2e-3)) / d["value"] < 1e-2
+    rf = d["roofline"]
+    assert rf["launches"] > 0 and rf["achieved"] > 0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
+    assert "exclusive" not in rf and "all_gemm_tflops" not in rf
+    assert not [k for k in d if k in FULL_ONLY_KEYS or k.startswith("parity_spot")], sorted(d)
+
+
+def test_bench_line_contract(tmp_path):
+    """`bench.py --full`'s single JSON line as the driver reads it (small model, seconds): every field of the contract, the
+    roofline, breakdown and cpu_baseline objects, and that nothing else is printed on stdout."""
+    d = _bench_line(["--full"])
     for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                  ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict)):
         assert isinstance(d[k], t), (k, d[k])
@@ -1527,6 +1551,7 @@ def test_bench_line_contract(tmp_path):
     rf = d["roofline"]
     assert rf["bound"] in ("hbm", "mfma") and rf["unit"] in ("GB/s", "TFLOP/s") and rf["peak"] > 0
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3 and "traffic" in rf
+    assert "exclusive" in rf and "sections_ms_per_forward" in d
     cb = d["cpu_baseline"]
     assert cb["kind"] in ("port", "reference") and cb["value"] > 0 and cb["cores"] >= 1 and isinstance(cb["sample"], str)
     assert "power" in d                                                     # hwmon sample or null, never missing

@@ -573,6 +573,16 @@ def test_bench_dump_outputs_stub(tmp_path, gpus):
     assert outs[0].dtype == np.float32 and np.array_equal(outs[0], want) and np.array_equal(outs[1], outs[0])
 
 
+def test_bench_full_flag_stub():
+    """`--full` adds the labelled extra legs after the timed steps (on the stand-in engine: the untimed breakdown step) and leaves
+    the headline fields of the line as a plain run gives them."""
+    common = ["--stub-engine", "--tiny", "--steps", "2", "--warmup", "1", "--samples-per-gpu", "3", "--residues", "10"]
+    plain, full = _run_bench(common), _run_bench(common + ["--full"])
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "data", "config"):
+        assert plain[k] == full[k], k
+    assert plain["ms_per_step"] > 0 and full["ms_per_step"] > 0
+
+
 def test_bench_dump_outputs_cap(tmp_path, monkeypatch):
     """Beyond the size cap the dump keeps a fixed, seeded sample of rows (indices beside it), within the cap."""
     import bench
