@@ -58,6 +58,7 @@ EXPORTS = [
     "esmdiff_ddpm_step_rows", "esmdiff_logit_error_stats", "esmdiff_get_build_info", "esmdiff_describe_plan", "esmdiff_set_option",
     "esmdiff_get_sequence_logits", "esmdiff_gibbs_step_rows", "esmdiff_shared_forward_batch",
     "esmdiff_attention_f16", "esmdiff_qk_norm_rope", "esmdiff_add_layernorm", "esmdiff_geom_attention",
+    "esmdiff_set_lengths", "esmdiff_attention_ragged",
 ]
 OPT_STREAMS, OPT_DUAL_MIN_TOKENS = 1, 2      # esmdiff_option
 
@@ -122,6 +123,8 @@ def lib():
     L.esmdiff_set_profiling.argtypes = [vp, i32]
     L.esmdiff_get_profile.argtypes = [vp, c_f32p, ctypes.POINTER(i32)]
     L.esmdiff_set_frames.argtypes = [vp, vp, vp, vp, i32, i32, vp]
+    L.esmdiff_set_lengths.argtypes = [vp, ctypes.POINTER(i32), i32]
+    L.esmdiff_attention_ragged.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(i32), i32, i32, vp]
     L.esmdiff_decoder_create.argtypes = L.esmdiff_engine_create.argtypes
     L.esmdiff_decoder_decode.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]
     f64, f64p = ctypes.c_double, ctypes.POINTER(ctypes.c_double)

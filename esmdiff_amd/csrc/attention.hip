@@ -76,6 +76,9 @@ extern "C" int esmdiff_debug_attn_trace(unsigned long long* out_host) {   // deb
   return (int)hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_attn_trace), sizeof(g_attn_trace));
 }
 #endif
+// Ragged batches (esmdiff_set_lengths): a separate instantiation per budget with a per-sample key length `lens` [B] (device
+// memory); the plain kernels are compiled from the same text with ED_ATTN_RAGGED = 0 and do not change.
+#define ED_ATTN_RAGGED 0
 #define ED_ATTN_NAME attention_kernel_occ3
 #define ED_ATTN_WPE 3
 #include "attention_kernel.inc"
@@ -86,6 +89,19 @@ extern "C" int esmdiff_debug_attn_trace(unsigned long long* out_host) {   // deb
 #include "attention_kernel.inc"
 #undef ED_ATTN_NAME
 #undef ED_ATTN_WPE
+#undef ED_ATTN_RAGGED
+#define ED_ATTN_RAGGED 1
+#define ED_ATTN_NAME attention_kernel_ragged_occ3
+#define ED_ATTN_WPE 3
+#include "attention_kernel.inc"
+#undef ED_ATTN_NAME
+#undef ED_ATTN_WPE
+#define ED_ATTN_NAME attention_kernel_ragged_occ4
+#define ED_ATTN_WPE 4
+#include "attention_kernel.inc"
+#undef ED_ATTN_NAME
+#undef ED_ATTN_WPE
+#undef ED_ATTN_RAGGED
 
 // (ESMDIFF_ATTN_WAVES=-1 only: the occupancy model that was tried and measured slower, see the header)
 // Workgroup width for L tokens: nw = ceil(L/32) query waves per (batch, head) are cut into nWG workgroups of W waves.  A CU
@@ -110,7 +126,7 @@ static int attention_waves(int L, int occ) {
 }
 
 hipError_t launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* qkv, bf16_t* ctx, int B, int L,
-                            int H, hipStream_t stream) {
+                            int H, hipStream_t stream, const int32_t* lens) {
   if (B <= 0 || L <= 0) return hipSuccess;
   static const int forced = [] {
     const char* e = ed_dbg_env("ESMDIFF_ATTN_WAVES");
@@ -125,7 +141,10 @@ hipError_t launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* qkv,
   const int nqb = (nw + W - 1) / W, BH = B * H;
   dim3 grid(8 * nqb * ((BH + 7) / 8)), block(64 * W);
   const size_t lds = (L <= KV_TILE ? 1 : 2) * 2 * KV_BYTES;
-  if (occ == 3) hipLaunchKernelGGL(attention_kernel_occ3, grid, block, lds, stream, q, k, qkv, ctx, L, H, BH, nqb);
+  // (the workgroup width W depends on L only; a query's arithmetic does not depend on W, so a ragged row equals its solo launch)
+  if (lens && occ == 3) hipLaunchKernelGGL(attention_kernel_ragged_occ3, grid, block, lds, stream, q, k, qkv, ctx, L, H, BH, nqb, lens);
+  else if (lens) hipLaunchKernelGGL(attention_kernel_ragged_occ4, grid, block, lds, stream, q, k, qkv, ctx, L, H, BH, nqb, lens);
+  else if (occ == 3) hipLaunchKernelGGL(attention_kernel_occ3, grid, block, lds, stream, q, k, qkv, ctx, L, H, BH, nqb);
   else hipLaunchKernelGGL(attention_kernel_occ4, grid, block, lds, stream, q, k, qkv, ctx, L, H, BH, nqb);
   return hipGetLastError();
 }

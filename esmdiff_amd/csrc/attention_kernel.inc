@@ -1,8 +1,13 @@
 // attention_kernel.inc — body of the flash-style attention kernel; included by attention.hip once per register budget
-// (ED_ATTN_NAME, ED_ATTN_WPE = waves per SIMD the register allocation must allow).  See attention.hip for the design.
+// (ED_ATTN_NAME, ED_ATTN_WPE = waves per SIMD the register allocation must allow, ED_ATTN_RAGGED = 1 for the per-sample
+// key length form).  See attention.hip for the design.
 __global__ __attribute__((amdgpu_flat_work_group_size(64, 640), amdgpu_waves_per_eu(ED_ATTN_WPE, ED_ATTN_WPE))) void ED_ATTN_NAME(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
+#if ED_ATTN_RAGGED
+    int L, int H, int BH, int nqb, const int32_t* __restrict__ lens) {
+#else
     int L, int H, int BH, int nqb) {
+#endif
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [stage][K 8K | V 8K], 2 stages (1 when L <= 64)
 #ifdef ED_ATTN_TRACE
   // debug build (-DED_ATTN_TRACE): s_memtime stamps of every wave of the first 512 workgroups -> g_attn_trace[wg][wave][32]
@@ -29,11 +34,18 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 640), amdgpu_waves_per
   const int bh = (slot / nqb) * 8 + xcd, qb = slot - (slot / nqb) * nqb;
   if (bh >= BH) return;
   const int b = bh / H, h = bh - b * H;
+#if ED_ATTN_RAGGED
+  // ragged batch: sample b is valid on tokens [0, Lv); keys from Lv on are masked like keys >= L, query rows from Lv on are
+  // written as zeros.  Every valid query sees the tiles, clamps and tail variant of a launch at L = Lv: bit-identical rows.
+  const int Lv = lens ? lens[b] : L;
+#else
+  const int Lv = L;
+#endif
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int NW = __builtin_amdgcn_readfirstlane((int)blockDim.x >> 6);
   const int q0 = (qb * NW + wave) * 32;
-  const bool active = q0 < L;  // wave-uniform
+  const bool active = q0 < Lv;  // wave-uniform
   const int qi = lane & 31, hi = lane >> 5;
 
   const int D = H * 64;
@@ -50,7 +62,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 640), amdgpu_waves_per
     for (int g = wave; g < 8; g += NW) {  // wave-uniform
       char* d = base + g * 1024;
       const int schunk = (lane & 7) ^ (((lane >> 4) + 4 * (g & 1)) & 7);  // (row >> 1) & 7 with row = g*8 + srow
-      const int tok = min(kt * KV_TILE + g * 8 + srow, L - 1);  // keys >= L are masked / get weight 0; any finite row will do
+      const int tok = min(kt * KV_TILE + g * 8 + srow, Lv - 1);  // keys >= Lv are masked / get weight 0; any finite row will do
       glds16a(kbase + (int64_t)tok * D + schunk * 8, d);
       glds16a(vbase + (int64_t)tok * ldq + vchunk * 8, d + KV_BYTES);
     }
@@ -59,7 +71,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 640), amdgpu_waves_per
   // ---- Q^T fragments (B operand): lane -> query qi, d chunk ks*2 + hi -------------------------
   bf16x8 qf[4];
   {
-    const bf16_t* qrow = q + ((int64_t)b * L + min(q0 + qi, L - 1)) * D + h * 64;
+    const bf16_t* qrow = q + ((int64_t)b * L + min(q0 + qi, Lv - 1)) * D + h * 64;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + (ks * 2 + hi) * 8);
   }
@@ -81,7 +93,23 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 640), amdgpu_waves_per
   int tr_off[2];
 #pragma unroll
   for (int d = 0; d < 2; ++d) tr_off[d] = tr_row * 128 + (((d * 4 + tr_c) ^ tr_swz) << 4) + (ti & 1) * 8;
-  const int nkt = (L + KV_TILE - 1) / KV_TILE;
+#if ED_ATTN_RAGGED
+  // zero context rows [r0, min(r0 + 32, L)) of this (batch, head): lane (qi, hi) writes row r0 + qi, columns 4 hi + 8 g + 32 d ..+3
+  auto zero_rows = [&](int r0) {
+    const int qrow = r0 + qi;
+    if (qrow >= L) return;
+    bf16_t* dst = ctx + ((int64_t)b * L + qrow) * (H * 64) + h * 64;
+#pragma unroll
+    for (int d = 0; d < 2; ++d)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) *reinterpret_cast<uint2*>(dst + d * 32 + g * 8 + 4 * hi) = make_uint2(0u, 0u);
+  };
+  if (qb * NW * 32 >= Lv) {  // workgroup-uniform: every query of this workgroup is padding, nothing to stage
+    if (q0 < L) zero_rows(q0);
+    return;
+  }
+#endif
+  const int nkt = (Lv + KV_TILE - 1) / KV_TILE;
   stage(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -111,8 +139,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 640), amdgpu_waves_per
           s[t] = ED_MFMA_32x32x16(kf, qf[ks], s[t]);
         }
       }
-      if constexpr (decltype(MASKED)::value) {  // keys >= L exist only in the last tile
-        const int lim = L - kt * KV_TILE - 4 * hi;
+      if constexpr (decltype(MASKED)::value) {  // keys >= Lv exist only in the last tile
+        const int lim = Lv - kt * KV_TILE - 4 * hi;
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -170,17 +198,27 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 640), amdgpu_waves_per
     ED_TR(l_run);                                   // past the barrier
   };
   for (int kt = 0; kt + 1 < nkt; ++kt) tile(kt, std::false_type{}, std::false_type{});
-  const int tail = L - (nkt - 1) * KV_TILE;  // valid keys of the last tile, 1..64
+  const int tail = Lv - (nkt - 1) * KV_TILE;  // valid keys of the last tile, 1..64
   if (tail <= 32) tile(nkt - 1, std::true_type{}, std::true_type{});
   else if (tail < KV_TILE) tile(nkt - 1, std::true_type{}, std::false_type{});
   else tile(nkt - 1, std::false_type{}, std::false_type{});
 
   ED_TR(l_run);
+#if ED_ATTN_RAGGED
+  if (!active) {
+    if (q0 < L) zero_rows(q0);
+    return;
+  }
+#else
   if (!active) return;
+#endif
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l_tot;
   const int qrow = q0 + qi;
-  if (qrow < L) {
+#if ED_ATTN_RAGGED
+  if (qrow >= Lv && qrow < L) zero_rows(q0);
+#endif
+  if (qrow < Lv) {
     bf16_t* dst = ctx + ((int64_t)b * L + qrow) * (H * 64) + h * 64;
 #pragma unroll
     for (int d = 0; d < 2; ++d)

@@ -160,10 +160,13 @@ __global__ __launch_bounds__(256) void v_split_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------
 // q2, k2, v2: [B L, 2 D] f16 = [hi(D) | lo(D)] per token; ctx f32 [B L, D].  Workgroup = NW waves = 32 NW queries of one (batch,
 // head); block ids as in attention.hip (the query blocks of a head sit on one XCD).  s_unscale = 1 / (q_scale k_scale) so that
-// S_mfma * s_unscale = log2(e) / 8 * q . k;  o_unscale = 1 / (P_SCALE v_scale).
+// S_mfma * s_unscale = log2(e) / 8 * q . k;  o_unscale = 1 / (P_SCALE v_scale).  RAGGED: sample b is valid on tokens [0, lens[b])
+// (attention.hip's ragged form: keys beyond masked, context rows beyond written as zeros, valid rows equal to a launch at that L).
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void attention_split_kernel(const uint16_t* __restrict__ q2, const uint16_t* __restrict__ k2,
                                                               const uint16_t* __restrict__ v2, float* __restrict__ ctx, int L, int H,
-                                                              int BH, int nqb, float s_unscale, float o_unscale) {
+                                                              int BH, int nqb, float s_unscale, float o_unscale,
+                                                              const int32_t* __restrict__ lens) {
   extern __shared__ __attribute__((aligned(16))) char smem_as[];  // [stage][K hi | K lo | V hi | V lo], 2 stages (1 when L <= 64)
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
   const int bh = (slot / nqb) * 8 + xcd, qb = slot - (slot / nqb) * nqb;
@@ -173,9 +176,23 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const uint16_t* __
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int NW = __builtin_amdgcn_readfirstlane((int)blockDim.x >> 6);
   const int q0 = (qb * NW + wave) * 32;
-  const bool active = q0 < L;  // wave-uniform
+  const int Lv = RAGGED ? lens[b] : L;
+  const bool active = q0 < Lv;  // wave-uniform
   const int qi = lane & 31, hi = lane >> 5;
   const int D = H * 64, ld = 2 * D;
+  auto zero_rows = [&]() {   // (RAGGED) this lane's context row q0 + qi, 32 of its 64 columns, when it is padding
+    const int qrow = q0 + qi;
+    if (qrow < Lv || qrow >= L) return;
+    float* dst = ctx + ((int64_t)b * L + qrow) * D + h * 64;
+#pragma unroll
+    for (int d = 0; d < 2; ++d)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) *reinterpret_cast<sf32x4*>(dst + d * 32 + g * 8 + 4 * hi) = sf32x4{0.f, 0.f, 0.f, 0.f};
+  };
+  if (RAGGED && qb * NW * 32 >= Lv) {   // workgroup-uniform: only padding queries here
+    zero_rows();
+    return;
+  }
   const uint16_t* kbase = k2 + (int64_t)b * L * ld + h * 64;
   const uint16_t* vbase = v2 + (int64_t)b * L * ld + h * 64;
 
@@ -186,7 +203,7 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const uint16_t* __
     for (int g = wave; g < 8; g += NW) {  // wave-uniform
       char* d = base + g * 1024;
       const int schunk = (lane & 7) ^ (((lane >> 4) + 4 * (g & 1)) & 7);
-      const int tok = min(kt * KV_TILE + g * 8 + srow, L - 1);
+      const int tok = min(kt * KV_TILE + g * 8 + srow, Lv - 1);
       const uint16_t* kr = kbase + (int64_t)tok * ld + schunk * 8;
       const uint16_t* vr = vbase + (int64_t)tok * ld + vchunk * 8;
       glds16(kr, d);
@@ -198,7 +215,7 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const uint16_t* __
 
   sf16x8 qh[4], ql[4];
   {
-    const uint16_t* qrow = q2 + ((int64_t)b * L + min(q0 + qi, L - 1)) * ld + h * 64;
+    const uint16_t* qrow = q2 + ((int64_t)b * L + min(q0 + qi, Lv - 1)) * ld + h * 64;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       qh[ks] = *reinterpret_cast<const sf16x8*>(qrow + (ks * 2 + hi) * 8);
@@ -220,7 +237,7 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const uint16_t* __
   int tr_off[2];
 #pragma unroll
   for (int d = 0; d < 2; ++d) tr_off[d] = tr_row * 128 + (((d * 4 + tr_c) ^ tr_swz) << 4) + (ti & 1) * 8;
-  const int nkt = (L + KV_TILE - 1) / KV_TILE;
+  const int nkt = (Lv + KV_TILE - 1) / KV_TILE;
   stage(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -251,7 +268,7 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const uint16_t* __
         }
       }
       if constexpr (decltype(MASKED)::value) {
-        const int lim = L - kt * KV_TILE - 4 * hi;
+        const int lim = Lv - kt * KV_TILE - 4 * hi;
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -307,16 +324,17 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const uint16_t* __
     __syncthreads();
   };
   for (int kt = 0; kt + 1 < nkt; ++kt) tile(kt, std::false_type{}, std::false_type{});
-  const int tail = L - (nkt - 1) * KV_TILE;
+  const int tail = Lv - (nkt - 1) * KV_TILE;
   if (tail <= 32) tile(nkt - 1, std::true_type{}, std::true_type{});
   else if (tail < KV_TILE) tile(nkt - 1, std::true_type{}, std::false_type{});
   else tile(nkt - 1, std::false_type{}, std::false_type{});
 
+  if (RAGGED) zero_rows();
   if (!active) return;
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = o_unscale / l_tot;
   const int qrow = q0 + qi;
-  if (qrow < L) {
+  if (qrow < Lv) {
     float* dst = ctx + ((int64_t)b * L + qrow) * D + h * 64;
 #pragma unroll
     for (int d = 0; d < 2; ++d)
@@ -385,16 +403,21 @@ hipError_t launch_v_split(const float* qkv, uint16_t* v2, int M, int D, float sc
 }
 
 hipError_t launch_attention_split(const uint16_t* q2, const uint16_t* k2, const uint16_t* v2, float* ctx, int B, int L, int H,
-                                  float qk_scale_product, float v_scale, hipStream_t stream) {
+                                  float qk_scale_product, float v_scale, hipStream_t stream, const int32_t* lens) {
   if (B <= 0 || L <= 0) return hipSuccess;
   const int W = std::min(4, (L + 31) / 32);
   const int nw = (L + 31) / 32;
   const int nqb = (nw + W - 1) / W, BH = B * H;
   dim3 grid(8 * nqb * ((BH + 7) / 8)), block(64 * W);
   const int lds = (L <= KV_TILE ? 1 : 2) * STAGE;
-  if (const hipError_t a_ = ensure_dynamic_lds((const void*)attention_split_kernel, 2 * STAGE); a_ != hipSuccess) return a_;
-  hipLaunchKernelGGL(attention_split_kernel, grid, block, lds, stream, q2, k2, v2, ctx, L, H, BH, nqb, 1.0f / qk_scale_product,
-                     1.0f / (P_SCALE * v_scale));
+  const void* kern = lens ? (const void*)attention_split_kernel<true> : (const void*)attention_split_kernel<false>;
+  if (const hipError_t a_ = ensure_dynamic_lds(kern, 2 * STAGE); a_ != hipSuccess) return a_;
+  if (lens)
+    hipLaunchKernelGGL(attention_split_kernel<true>, grid, block, lds, stream, q2, k2, v2, ctx, L, H, BH, nqb, 1.0f / qk_scale_product,
+                       1.0f / (P_SCALE * v_scale), lens);
+  else
+    hipLaunchKernelGGL(attention_split_kernel<false>, grid, block, lds, stream, q2, k2, v2, ctx, L, H, BH, nqb, 1.0f / qk_scale_product,
+                       1.0f / (P_SCALE * v_scale), nullptr);
   return hipGetLastError();
 }
 

@@ -93,6 +93,12 @@ struct esmdiff_engine {
   float *f_rot = nullptr, *f_trans = nullptr;
   uint8_t* f_mask = nullptr;
   int frames_B = 0, frames_L = 0;
+  // ragged batch (esmdiff_set_lengths): sample b valid on tokens [0, lens_host[b]) while lens_B > 0; cur_lens is what the next
+  // forward's attention reads (lens_dev, or lens_sub_dev for the noise-removal sub-batch of esmdiff_ddpm_sample)
+  int32_t *lens_dev = nullptr, *lens_sub_dev = nullptr;
+  const int32_t* cur_lens = nullptr;
+  std::vector<int32_t> lens_host;
+  int lens_B = 0;
   // workspace
   float* x = nullptr;
   bf16_t *h = nullptr, *h2 = nullptr, *qkv = nullptr, *q = nullptr, *k = nullptr, *ctx = nullptr,
@@ -328,6 +334,15 @@ int check_bl(esmdiff_engine* e, int B, int L) {
   return 0;
 }
 
+// While lengths are set (esmdiff_set_lengths) a call must cover exactly that batch, and every length must fit its L.
+int check_lens(esmdiff_engine* e, int B, int L) {
+  if (e->lens_B == 0) return 0;
+  if (B != e->lens_B) return fail(e, ESMDIFF_E_INVALID, "lengths were set for B=%d, call has B=%d", e->lens_B, B);
+  for (int b = 0; b < B; ++b)
+    if (e->lens_host[b] > L) return fail(e, ESMDIFF_E_INVALID, "length %d of sample %d exceeds L=%d", e->lens_host[b], b, L);
+  return 0;
+}
+
 // Workspace of one sub-batch: the engine's buffers are all sample-major, so a sub-batch is a pointer offset.
 struct Part {
   const int64_t *seq, *xtok;
@@ -338,6 +353,7 @@ struct Part {
   float *rs, *fh2;
   const float *f_rot, *f_trans;
   const uint8_t* f_mask;
+  const int32_t* lens;   // ragged batch: this sub-batch's lengths (device), else null
   int B;
   hipStream_t st;
   const ed::GemmWorkspace* gws;
@@ -353,7 +369,7 @@ Part make_part(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, float
               e->gp ? e->gp + t0 * 15 * e->v_heads : nullptr, e->gctx ? e->gctx + t0 * 3 * e->v_heads : nullptr,
               e->a2 ? e->a2 + t0 * 3 * D : nullptr, e->rs ? e->rs + t0 : nullptr, e->fh2 ? e->fh2 + t0 * D : nullptr,
               e->f_rot ? e->f_rot + t0 * 9 : nullptr, e->f_trans ? e->f_trans + t0 * 3 : nullptr,
-              e->f_mask ? e->f_mask + t0 : nullptr, nb, st,
+              e->f_mask ? e->f_mask + t0 : nullptr, e->cur_lens ? e->cur_lens + b0 : nullptr, nb, st,
               e->gemm_ws[queue].partial ? &e->gemm_ws[queue] : nullptr,
               e->gemm_ws2[queue].partial ? &e->gemm_ws2[queue] : nullptr};
 }
@@ -417,6 +433,7 @@ struct SPart {   // one sub-batch of a strict forward: the engine's float32 work
   float* rs;
   const float *f_rot, *f_trans;
   const uint8_t* f_mask;
+  const int32_t* lens;   // ragged batch: this sub-batch's lengths (device), else null
   int B;
   hipStream_t st;
 };
@@ -469,11 +486,11 @@ static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int
       RUN(S_QKROPE, launch_qk_norm_rope_split(w.fqkv, ly.q_ln_w, ly.k_ln_w, e->rope_cos, e->rope_sin, q2, k2, B, L, H,
                                               ly.att_qk * 0.18033688011112042f /* log2(e) / 8 */, ly.att_qk, st));
       RUN(S_QKROPE, launch_v_split(w.fqkv, v2, M, D, ly.att_v, st));
-      RUN(S_ATTN, launch_attention_split(q2, k2, v2, w.fctx, B, L, H, ly.att_qk * ly.att_qk, ly.att_v, st));
+      RUN(S_ATTN, launch_attention_split(q2, k2, v2, w.fctx, B, L, H, ly.att_qk * ly.att_qk, ly.att_v, st, w.lens));
       RUN(S_ATTN, launch_split_rows(w.fctx, D, a2, rs, M, D, st));
     } else {
       RUN(S_QKROPE, launch_qk_norm_rope_f32(w.fqkv, ly.q_ln_w, ly.k_ln_w, e->rope_cos, e->rope_sin, w.fq, w.fk, B, L, H, st));
-      RUN(S_ATTN, launch_attention_f32(w.fq, w.fk, w.fqkv, w.fctx, B, L, H, st));
+      RUN(S_ATTN, launch_attention_f32(w.fq, w.fk, w.fqkv, w.fctx, B, L, H, st, w.lens));
     }
     if (sk) {
       RUN(S_OUT, launch_gemm256w4_splitk(a2, ly.s_out.w, ly.s_out.inv, skp, M, D, D, 3, st));
@@ -576,7 +593,7 @@ int forward_strict(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, c
                       off(e->fctx, D), off(e->fgu, 2 * FH), off(e->fmid, FH), off(e->fgp, 15 * e->v_heads), off(e->fgctx, 3 * e->v_heads),
                       off(e->fpair_qk, 128), logits + t0 * ld, off(e->pl_logits, e->ld_plddt), e->a2 ? e->a2 + t0 * WS : nullptr,
                       reinterpret_cast<uint16_t*>(e->fgu) + t0 * 3 * FH, e->rs ? e->rs + t0 : nullptr, e->f_rot ? e->f_rot + t0 * 9 : nullptr, e->f_trans ? e->f_trans + t0 * 3 : nullptr,
-                      e->f_mask ? e->f_mask + t0 : nullptr, b1 - b0, pi == 0 ? st : e->side[pi - 1]};
+                      e->f_mask ? e->f_mask + t0 : nullptr, e->cur_lens ? e->cur_lens + b0 : nullptr, b1 - b0, pi == 0 ? st : e->side[pi - 1]};
   }
   if (np > 1) {
     HIP_TRY(e, hipEventRecord(e->ev_fork, st));
@@ -644,6 +661,7 @@ int step0_shared_batch(esmdiff_engine* e, const int64_t* seq, const int64_t* x, 
   *shared = 0;
   if (!e->step0_share || B < 2) return 0;
   if (e->frames_B != 0) return 0;   // coordinate conditioning: frames may differ per sample and are not compared below
+  if (e->lens_B != 0) return 0;     // ragged batch: rows of different lengths are never shared
   const int bs = shared_forward_batch(e, B, L);
   if (bs >= B) return 0;
   HIP_TRY(e, launch_rows_identical(seq, x, B, L, e->flag_dev, st));
@@ -766,6 +784,11 @@ int esmdiff_describe_plan(const esmdiff_engine* e, int32_t B, int32_t L, char* b
       n += snprintf(at(), room(), " gemm[qkv]=%s gemm[out]=%s gemm[ffn_up]=%s gemm[ffn_down]=%s", g1, g2, g3, g4);
   }
   n += snprintf(at(), room(), " step0_sharing=%d final_skip=%d small_max_rows=%d", e->step0_share, e->final_skip, ed::small_max_rows());
+  if (e->lens_B == B) {   // ragged batch (esmdiff_set_lengths): attention walks each sample's own keys
+    int64_t valid = 0;
+    for (int b = 0; b < B; ++b) valid += std::min<int64_t>(e->lens_host[b], L);
+    n += snprintf(at(), room(), " ragged=1 valid_tokens=%lld padded_tokens=%lld", (long long)valid, (long long)B * L);
+  }
   if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", tmp);
   return n;
 }
@@ -1153,6 +1176,8 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     TRY(dalloc(e, &e->flag_dev, (size_t)4));
     TRY(dalloc(e, &e->has_dev, (size_t)cfg->max_batch));
     TRY(dalloc(e, &e->idx_dev, (size_t)cfg->max_batch));
+    TRY(dalloc(e, &e->lens_dev, (size_t)cfg->max_batch));
+    TRY(dalloc(e, &e->lens_sub_dev, (size_t)cfg->max_batch));
     TRY(dalloc(e, &e->cx, Mx));
     TRY(dalloc(e, &e->cseq, Mx));
     TRY(dalloc(e, &e->g_inv_mask, (size_t)128, true));
@@ -1293,6 +1318,7 @@ int esmdiff_forward_logits(esmdiff_engine* e, const int64_t* seq, const int64_t*
   if (!seq || !x || !logits_out) return fail(e, ESMDIFF_E_INVALID, "null pointer");
   if (ld_logits < e->cfg.vocab_out || (ld_logits & 3)) return fail(e, ESMDIFF_E_INVALID, "ld_logits (%d) must be >= vocab (%d) rounded up to a multiple of 4", ld_logits, e->cfg.vocab_out);
   if (int r = check_bl(e, B, L)) return r;
+  if (int r = check_lens(e, B, L)) return r;
   if ((e->split || e->head_split) && ld_logits < e->vocab_pad) {
     // the split head GEMM writes whole padded rows: run into the engine's own [M, vocab_pad] buffer, copy the valid columns
     if (int r = forward(e, seq, x, t_freq, e->logits, e->ld_logits, B, L, (hipStream_t)stream)) return r;
@@ -1379,6 +1405,7 @@ int esmdiff_ddpm_step_rows(esmdiff_engine* e, int64_t* x_inout, const float* log
   if (!x_inout || !logits || !params) return fail(e, ESMDIFF_E_INVALID, "null pointer");
   if (B <= 0 || L <= 0 || ld_logits < e->cfg.vocab_out) return fail(e, ESMDIFF_E_INVALID, "bad shape");
   if (e->cfg.vocab_out <= ESMDIFF_MASK_ID) return fail(e, ESMDIFF_E_INVALID, "ddpm needs the 4101-way head (mask column)");
+  if (int r = check_lens(e, B, L)) return r;   // (padding holds no MASK: the step leaves it as it is)
   if ((sample_flags || sample_min_gap) && !(margin_ratio >= 1.f && margin_diff >= 0.f))
     return fail(e, ESMDIFF_E_INVALID, "margins (%g, %g): a ratio >= 1 for updates, a difference >= 0 for final passes", margin_ratio, margin_diff);
   Prof p{e, (hipStream_t)stream};
@@ -1404,6 +1431,7 @@ int esmdiff_ddpm_sample(esmdiff_engine* e, const int64_t* seq, int64_t* x_inout,
   if (T <= 0 || T + 1 > e->tfreq_rows) return fail(e, ESMDIFF_E_INVALID, "num_steps %d out of range (1..%d)", T, e->tfreq_rows - 1);
   if (e->cfg.time_conditioning && !t_freq) return fail(e, ESMDIFF_E_INVALID, "t_freq required with time conditioning");
   if (int r = check_bl(e, B, L)) return r;
+  if (int r = check_lens(e, B, L)) return r;
   hipStream_t st = (hipStream_t)stream;
   const int F = e->cfg.freq_dim;
   if (t_freq) HIP_TRY(e, hipMemcpyAsync(e->tfreq, t_freq, (size_t)(T + 1) * F * sizeof(float), hipMemcpyHostToDevice, st));
@@ -1435,7 +1463,15 @@ int esmdiff_ddpm_sample(esmdiff_engine* e, const int64_t* seq, int64_t* x_inout,
         HIP_TRY(e, hipMemcpyAsync(e->idx_dev, idx.data(), (size_t)n_run * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(e, launch_move_token_rows(x_inout, e->cx, e->idx_dev, n_run, L, 1, st));
         HIP_TRY(e, launch_move_token_rows(seq, e->cseq, e->idx_dev, n_run, L, 1, st));
-        if (int r = forward(e, e->cseq, e->cx, t_freq ? e->tfreq + (size_t)i * F : nullptr, e->logits, e->ld_logits, n_run, L, st)) return r;
+        std::vector<int32_t> sub_lens;
+        if (e->lens_B) {   // ragged batch: the sub-batch's own lengths
+          for (int j = 0; j < n_run; ++j) sub_lens.push_back(e->lens_host[idx[j]]);
+          HIP_TRY(e, hipMemcpyAsync(e->lens_sub_dev, sub_lens.data(), (size_t)n_run * 4, hipMemcpyHostToDevice, st));
+          e->cur_lens = e->lens_sub_dev;
+        }
+        const int rf = forward(e, e->cseq, e->cx, t_freq ? e->tfreq + (size_t)i * F : nullptr, e->logits, e->ld_logits, n_run, L, st);
+        e->cur_lens = e->lens_B ? e->lens_dev : nullptr;
+        if (rf) return rf;
         p.mark(S_SAMPLER);
         HIP_TRY(e, launch_ddpm_step(e->cx, e->logits, e->ld_logits, e->cfg.vocab_out, 0.f, 0.f, 1, nullptr, 1, rng->seed, rng->sample_offset, i, n_run, L, st, 0));
         p.mark(S_SAMPLER);
@@ -1484,6 +1520,7 @@ int esmdiff_gibbs_step_rows(esmdiff_engine* e, int64_t* x_inout, const int64_t* 
   if (!(top_p > 0.f) || top_p > 1.f) return fail(e, ESMDIFF_E_INVALID, "top_p must be in (0, 1]");
   if (ld_logits < 4096 || e->cfg.vocab_out < 4096 || ld_logits < e->cfg.vocab_out) return fail(e, ESMDIFF_E_INVALID, "bad shape");
   if (int r = check_bl(e, B, L)) return r;
+  if (int r = check_lens(e, B, L)) return r;   // (padding holds no MASK: the step leaves it as it is)
   if (pair_bound < 0.f && (sample_flags || sample_gaps))
     return fail(e, ESMDIFF_E_INVALID, "sample_flags / sample_gaps need pair_bound >= 0 (and entropy_bound >= 0)");
   if (pair_bound >= 0.f && !(entropy_bound >= 0.f)) return fail(e, ESMDIFF_E_INVALID, "entropy_bound must be >= 0");
@@ -1504,6 +1541,7 @@ int esmdiff_gibbs_sample(esmdiff_engine* e, const int64_t* seq, int64_t* x_inout
   if (!seq || !x_inout || !n_unmask_table || !rng) return fail(e, ESMDIFF_E_INVALID, "null pointer");
   if (T <= 0 || T > e->tfreq_rows) return fail(e, ESMDIFF_E_INVALID, "num_steps %d out of range (1..%d)", T, e->tfreq_rows);
   if (int r = check_bl(e, B, L)) return r;
+  if (int r = check_lens(e, B, L)) return r;
   hipStream_t st = (hipStream_t)stream;
   if (!(temperature >= 0.f)) return fail(e, ESMDIFF_E_INVALID, "temperature must be >= 0 (0 = arg-max of the filtered logits)");
   if (!(top_p > 0.f) || top_p > 1.f) return fail(e, ESMDIFF_E_INVALID, "top_p must be in (0, 1]");
@@ -1705,6 +1743,42 @@ int esmdiff_attention_f16(esmdiff_engine* e, const void* qkv, const float* q_ln_
   return 0;
 }
 
+int esmdiff_attention_ragged(esmdiff_engine* e, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* ctx,
+                             const int32_t* lens, int32_t B, int32_t L, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (!qkv || !q_ln_w || !k_ln_w || !ctx) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (e->kind != 0) return fail(e, ESMDIFF_E_INVALID, "esmdiff_attention_ragged needs an ESM3 engine");
+  if (int r = check_bl(e, B, L)) return r;
+  hipStream_t st = (hipStream_t)stream;
+  const int H = e->cfg.n_heads, D = e->cfg.d_model;
+  const int32_t* dl = nullptr;
+  if (lens) {   // host lengths -> the engine's sub-batch length buffer (validated here: the kernels index with them)
+    for (int b = 0; b < B; ++b)
+      if (lens[b] < 1 || lens[b] > L) return fail(e, ESMDIFF_E_INVALID, "lens[%d] = %d outside 1..L (%d)", b, lens[b], L);
+    HIP_TRY(e, hipStreamSynchronize(st));
+    HIP_TRY(e, hipMemcpy(e->lens_sub_dev, lens, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
+    dl = e->lens_sub_dev;
+  }
+  if (e->strict && e->split) {   // f32 qkv -> split q / k / v rows (unit scales) -> float32-grade attention on the f16 MFMA
+    uint16_t *q2 = reinterpret_cast<uint16_t*>(e->fq), *k2 = reinterpret_cast<uint16_t*>(e->fk), *v2 = reinterpret_cast<uint16_t*>(e->fh);
+    HIP_TRY(e, launch_qk_norm_rope_split((const float*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, q2, k2, B, L, H,
+                                         0.18033688011112042f /* log2(e) / 8 */, 1.0f, st));
+    HIP_TRY(e, launch_v_split((const float*)qkv, v2, B * L, D, 1.0f, st));
+    HIP_TRY(e, launch_attention_split(q2, k2, v2, (float*)ctx, B, L, H, 1.0f, 1.0f, st, dl));
+  } else if (e->strict) {
+    HIP_TRY(e, launch_qk_norm_rope_f32((const float*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, e->fq, e->fk, B, L, H, st));
+    HIP_TRY(e, launch_attention_f32(e->fq, e->fk, (const float*)qkv, (float*)ctx, B, L, H, st, dl));
+  } else if (e->f16) {
+    HIP_TRY(e, ed16::launch_qk_norm_rope((const bf16_t*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, e->q, e->k, B, L, H, st));
+    HIP_TRY(e, ed16::launch_attention(e->q, e->k, (const bf16_t*)qkv, (bf16_t*)ctx, B, L, H, st, dl));
+  } else {
+    HIP_TRY(e, launch_qk_norm_rope((const bf16_t*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, e->q, e->k, B, L, H, st));
+    HIP_TRY(e, launch_attention(e->q, e->k, (const bf16_t*)qkv, (bf16_t*)ctx, B, L, H, st, dl));
+  }
+  if (lens) HIP_TRY(e, hipStreamSynchronize(st));   // the next call may rewrite lens_sub_dev
+  return 0;
+}
+
 int esmdiff_qk_norm_rope(esmdiff_engine* e, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* q, void* k,
                          int32_t B, int32_t L, int32_t H, void* stream) {
   if (!e) return ESMDIFF_E_INVALID;
@@ -1782,6 +1856,28 @@ int esmdiff_set_frames(esmdiff_engine* e, const float* rot, const float* trans, 
   HIP_TRY(e, hipMemcpyAsync(e->f_mask, has_frame, M, hipMemcpyDeviceToDevice, st));
   e->frames_B = B;
   e->frames_L = L;
+  return 0;
+}
+
+int esmdiff_set_lengths(esmdiff_engine* e, const int32_t* lens, int32_t B) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (!lens) {
+    e->lens_B = 0;
+    e->lens_host.clear();
+    e->cur_lens = nullptr;
+    return 0;
+  }
+  if (e->kind != 0) return fail(e, ESMDIFF_E_INVALID, "lengths are for the ESM3 engine, not the structure-token decoder");
+  if (B <= 0 || B > e->cfg.max_batch) return fail(e, ESMDIFF_E_INVALID, "B = %d outside 1..max_batch (%d)", B, e->cfg.max_batch);
+  for (int b = 0; b < B; ++b)
+    if (lens[b] < 3 || lens[b] > e->cfg.max_len)
+      return fail(e, ESMDIFF_E_INVALID, "lens[%d] = %d outside 3..max_len (%d): BOS, one residue and EOS at least", b, lens[b], e->cfg.max_len);
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipDeviceSynchronize());   // no forward still in flight reads the buffer
+  HIP_TRY(e, hipMemcpy(e->lens_dev, lens, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
+  e->lens_host.assign(lens, lens + B);
+  e->lens_B = B;
+  e->cur_lens = e->lens_dev;
   return 0;
 }
 

@@ -84,7 +84,7 @@ static int ED_FWD_NAME(esmdiff_engine* e, const int64_t* seq, const int64_t* xto
     }
     EACH(S_QKV, KN::launch_gemm_bf16(w.h, ly.w_qkv, w.qkv, nullptr, M, 3 * D, D, 3 * D, 3 * D, 1.f, ESMDIFF_EPI_BF16, w.st, w.gws));
     if (!(e->debug_skip & 1) || i == 0) EACH(S_QKROPE, KN::launch_qk_norm_rope(w.qkv, ly.q_ln_w, ly.k_ln_w, e->rope_cos, e->rope_sin, w.q, w.k, w.B, L, H, w.st));
-    if (!(e->debug_skip & 2) || i == 0) EACH(S_ATTN, KN::launch_attention(w.q, w.k, w.qkv, w.ctx, w.B, L, H, w.st));
+    if (!(e->debug_skip & 2) || i == 0) EACH(S_ATTN, KN::launch_attention(w.q, w.k, w.qkv, w.ctx, w.B, L, H, w.st, w.lens));
     if (small) EACH(S_OUT, KN::launch_gemm_partials(w.ctx, ly.w_out, w.gws2, M, D, D, w.st, &PA[pi]));
     else EACH(S_OUT, KN::launch_gemm_bf16(w.ctx, ly.w_out, w.dlt2, nullptr, M, D, D, D, D, inv_scale, ESMDIFF_EPI_BF16, w.st, w.gws));
     const bool geom_here = i == 0 && geom;

@@ -103,9 +103,11 @@ hipError_t launch_qk_norm_rope(const bf16_t* qkv, const float* q_ln_w, const flo
                                int B, int L, int H, hipStream_t stream);
 
 // ---- attention.hip ---------------------------------------------------------------------------
-// q,k [B*L, H*64] token-major, v read in place from qkv [B*L, 3*H*64] (columns 2*H*64 ..) -> ctx bf16 [B*L, H*64]
+// q,k [B*L, H*64] token-major, v read in place from qkv [B*L, 3*H*64] (columns 2*H*64 ..) -> ctx bf16 [B*L, H*64].
+// lens (device, [B], each in 1..L, or null = all L): sample b is valid on tokens [0, lens[b]); keys beyond are masked and
+// its context rows from lens[b] on are written as zeros.
 hipError_t launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* qkv, bf16_t* ctx, int B, int L,
-                            int H, hipStream_t stream);
+                            int H, hipStream_t stream, const int32_t* lens = nullptr);
 
 // ---- geom.hip --------------------------------------------------------------------------------
 // P bf16 [B*L, 15*VH] (proj output) + frames -> out bf16 [B*L, 3*VH]; w_rot / w_dist = softplus(scale) per head
@@ -146,7 +148,7 @@ hipError_t launch_swiglu_f32(const float* gu, float* mid, int M, int FH, hipStre
 hipError_t launch_qk_norm_rope_f32(const float* qkv, const float* q_ln_w, const float* k_ln_w, const float* rope_cos,
                                    const float* rope_sin, float* q, float* k, int B, int L, int H, hipStream_t stream);
 hipError_t launch_attention_f32(const float* q, const float* k, const float* qkv, float* ctx, int B, int L, int H,
-                                hipStream_t stream);
+                                hipStream_t stream, const int32_t* lens = nullptr);   // lens: as launch_attention's
 
 // ---- gemm_split.hip + gemm256w4.hip (SPLIT): float32-grade linears as three f16 MFMA passes over split operands ----
 // A3 f16 [M, 3K] = [hi | lo | hi] scaled per row (rs[M] = 1 / row scale), W3 f16 [N_pad, 3K] = [lo | hi | hi] scaled per
@@ -179,7 +181,8 @@ hipError_t launch_qk_norm_rope_split(const float* qkv, const float* q_ln_w, cons
                                      float k_scale, hipStream_t stream);
 hipError_t launch_v_split(const float* qkv, uint16_t* v2, int M, int D, float scale, hipStream_t stream);
 hipError_t launch_attention_split(const uint16_t* q2, const uint16_t* k2, const uint16_t* v2, float* ctx, int B, int L, int H,
-                                  float qk_scale_product, float v_scale, hipStream_t stream);
+                                  float qk_scale_product, float v_scale, hipStream_t stream,
+                                  const int32_t* lens = nullptr);   // lens: as launch_attention's
 hipError_t weight_rownorm_max(const void* src, int src_dtype, int64_t r0, int rows, int K, uint32_t* scratch_bits, float* out);
 
 // ---- convert.hip (weight preparation at engine create) ---------------------------------------

@@ -281,10 +281,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 
 // Attention in f32.  Block = one wave = 64 queries of one (batch, head); lane = query.  K and V tiles of 32 keys x 64
 // floats are staged in LDS by the wave itself; every lane walks the keys with broadcast LDS reads.
-// softmax(q . k / 8) v with the running-maximum form (rescale only when the maximum grows).
+// softmax(q . k / 8) v with the running-maximum form (rescale only when the maximum grows).  RAGGED: sample b is valid on tokens
+// [0, lens[b]): only those keys are walked, context rows from lens[b] on are written as zeros (valid rows equal a launch at that L).
+template <bool RAGGED>
 __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                            const float* __restrict__ qkv, float* __restrict__ ctx, int L,
-                                                           int H) {
+                                                           int H, const int32_t* __restrict__ lens) {
   constexpr int KT = 32;
   __shared__ float sK[KT * 64];
   __shared__ float sV[KT * 64];
@@ -292,7 +294,16 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restri
   const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * 64;
   const int D = H * 64;
   const int64_t base = (int64_t)b * L;
-  const int qi = min(q0 + lane, L - 1);
+  const int Lv = RAGGED ? lens[b] : L;
+  if (RAGGED && q0 >= Lv) {   // block-uniform: padding queries only
+    if (q0 + lane < L) {
+      float* op = ctx + (base + q0 + lane) * D + h * 64;
+#pragma unroll
+      for (int d = 0; d < 64; d += 4) *reinterpret_cast<f32x4*>(op + d) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    return;
+  }
+  const int qi = min(q0 + lane, Lv - 1);
   float qr[64], o[64];
   {
     const float* qp = q + (base + qi) * D + h * 64;
@@ -305,15 +316,15 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restri
     for (int d = 0; d < 64; ++d) o[d] = 0.f;
   }
   float m = -INFINITY, lsum = 0.f;
-  for (int k0 = 0; k0 < L; k0 += KT) {
-    const int nk = min(KT, L - k0);
+  for (int k0 = 0; k0 < Lv; k0 += KT) {
+    const int nk = min(KT, Lv - k0);
     __syncthreads();
     // stage: 32 rows x 16 float4 per tensor = 512 float4 -> 8 per lane
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int idx = i * 64 + lane;
       const int r = idx >> 4, c4 = (idx & 15) * 4;
-      const int kr = min(k0 + r, L - 1);
+      const int kr = min(k0 + r, Lv - 1);
       *reinterpret_cast<f32x4*>(&sK[r * 64 + c4]) = *reinterpret_cast<const f32x4*>(k + (base + kr) * D + h * 64 + c4);
       *reinterpret_cast<f32x4*>(&sV[r * 64 + c4]) = *reinterpret_cast<const f32x4*>(qkv + (base + kr) * 3 * D + 2 * D + h * 64 + c4);
     }
@@ -348,13 +359,17 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restri
       }
     }
   }
-  if (q0 + lane < L) {
+  if (q0 + lane < Lv) {
     float* op = ctx + (base + q0 + lane) * D + h * 64;
 #pragma unroll
     for (int d = 0; d < 64; d += 4) {
       f32x4 t{o[d] / lsum, o[d + 1] / lsum, o[d + 2] / lsum, o[d + 3] / lsum};
       *reinterpret_cast<f32x4*>(op + d) = t;
     }
+  } else if (RAGGED && q0 + lane < L) {
+    float* op = ctx + (base + q0 + lane) * D + h * 64;
+#pragma unroll
+    for (int d = 0; d < 64; d += 4) *reinterpret_cast<f32x4*>(op + d) = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 }
 
@@ -433,10 +448,11 @@ hipError_t launch_qk_norm_rope_f32(const float* qkv, const float* q_ln_w, const 
 }
 
 hipError_t launch_attention_f32(const float* q, const float* k, const float* qkv, float* ctx, int B, int L, int H,
-                                hipStream_t stream) {
+                                hipStream_t stream, const int32_t* lens) {
   if (B <= 0 || L <= 0) return hipSuccess;
   dim3 grid((L + 63) / 64, H, B), block(64);
-  hipLaunchKernelGGL(attention_f32_kernel, grid, block, 0, stream, q, k, qkv, ctx, L, H);
+  if (lens) hipLaunchKernelGGL(attention_f32_kernel<true>, grid, block, 0, stream, q, k, qkv, ctx, L, H, lens);
+  else hipLaunchKernelGGL(attention_f32_kernel<false>, grid, block, 0, stream, q, k, qkv, ctx, L, H, nullptr);
   return hipGetLastError();
 }
 

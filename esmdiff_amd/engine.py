@@ -9,13 +9,14 @@ sites of the reference's hot path with PyTorch-ROCm tensors as plain device-memo
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, Optional
+import contextlib
+from typing import Dict, Optional, Sequence
 
 import torch
 
 from . import _native as N
 from .config import ModelConfig
-from .constants import STRUCTURE_MASK_TOKEN, STRUCTURE_VOCAB
+from .constants import SEQUENCE_PAD_TOKEN, STRUCTURE_MASK_TOKEN, STRUCTURE_PAD_TOKEN, STRUCTURE_VOCAB
 from .schedule import DDPMSchedule
 
 
@@ -83,6 +84,7 @@ class Engine:
         self.has_sigma_embedder = any(k.startswith("sigma_embedder.mlp.0.") for k in state_dict)
         self.n_sequence_heads = next((int(v.shape[0]) for k, v in state_dict.items() if k.endswith("output_heads.sequence_head.3.weight")), 0)
         self._frames = None
+        self._lengths = None   # set_lengths
 
     def branch_linear_layernorm(self, A: torch.Tensor, W: torch.Tensor, x: torch.Tensor, alpha: float, w: torch.Tensor,
                                 b: Optional[torch.Tensor]):
@@ -141,14 +143,60 @@ class Engine:
         zero = timestep_embedding(torch.zeros(1, dtype=torch.float32), self.cfg.freq_dim)
         return zero.expand(t_freq.shape[0], -1).contiguous() if t_freq.dim() == 2 else zero[0]
 
+    # ---- ragged batches (esmdiff_set_lengths) ------------------------------------------------------------------------------
+    def set_lengths(self, lengths: Optional[Sequence[int]]) -> None:
+        """Ragged batch for the following calls (esmdiff_set_lengths): sample b of a (B, L) batch is valid on tokens [0, lengths[b])
+        (BOS and EOS counted) and holds the pad ids beyond (sequence 1, structure 4099).  A valid position's logits and ids are
+        then what the sample gives alone at L = lengths[b].  None clears it."""
+        if lengths is None:
+            self._chk(self._lib.esmdiff_set_lengths(self._h, None, 0))
+            self._lengths = None
+            return
+        lens = [int(v) for v in lengths]
+        arr = (ctypes.c_int32 * max(1, len(lens)))(*lens)
+        self._chk(self._lib.esmdiff_set_lengths(self._h, arr, len(lens)))
+        self._lengths = lens
+
+    def _check_padding(self, lens: Sequence[int], seq: torch.Tensor, x: Optional[torch.Tensor]) -> None:
+        """Host check of a ragged batch: every length in 3..L, the pad ids from each length on."""
+        B, L = seq.shape
+        if len(lens) != B:
+            raise ValueError(f"{len(lens)} lengths for a batch of {B}")
+        if min(lens) < 3 or max(lens) > L:
+            raise ValueError(f"lengths must be in 3..L={L} (BOS, one residue, EOS), got {min(lens)}..{max(lens)}")
+        pos = torch.arange(L, device=seq.device)[None]
+        pad = pos >= torch.tensor(lens, device=seq.device)[:, None]
+        if bool((pad & (seq != SEQUENCE_PAD_TOKEN)).any()):
+            raise ValueError(f"ragged batch: sequence positions from each length on must hold the pad id {SEQUENCE_PAD_TOKEN}")
+        if x is not None and bool((pad & (x != STRUCTURE_PAD_TOKEN)).any()):
+            raise ValueError(f"ragged batch: structure positions from each length on must hold the pad id {STRUCTURE_PAD_TOKEN}")
+
+    @contextlib.contextmanager
+    def _lengths_for_call(self, lengths: Optional[Sequence[int]], seq: torch.Tensor, x: Optional[torch.Tensor]):
+        """`lengths=` of one call: set for the call and cleared afterwards (None: whatever set_lengths left in place)."""
+        if lengths is None:
+            yield
+            return
+        lens = [int(v) for v in lengths]
+        self._check_padding(lens, seq, x)
+        self.set_lengths(lens)
+        try:
+            yield
+        finally:
+            self.set_lengths(None)
+
     def forward_logits(self, x: torch.Tensor, sequence_tokens: torch.Tensor, t_freq: Optional[torch.Tensor],
-                       out: Optional[torch.Tensor] = None, check_ids: bool = True) -> torch.Tensor:
+                       out: Optional[torch.Tensor] = None, check_ids: bool = True,
+                       lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
         """x, sequence_tokens: (B,L) int64.  t_freq: (freq_dim,) f32 sinusoid of the sigma all samples share, (B, freq_dim) for
-        one sigma per sample (esmdiff_forward_logits_sigmas), or None.
+        one sigma per sample (esmdiff_forward_logits_sigmas), or None.  lengths: a ragged batch for this call (set_lengths).
         Returns raw structure logits, a (B,L,4101) view of a (B,L,ld) float32 buffer."""
         B, L = x.shape
         x = self._tok(x, B, L)
         seq = self._tok(sequence_tokens, B, L)
+        if lengths is not None:
+            with self._lengths_for_call(lengths, seq, x):
+                return self.forward_logits(x, seq, t_freq, out, check_ids)
         if check_ids:      # (a device -> host read-back: loops that feed the engine its own output skip it after the first call)
             self._check_ids(seq, x)
         if out is None:
@@ -272,22 +320,51 @@ class Engine:
         return out
 
     def ddpm_sample(self, sequence_tokens: torch.Tensor, schedule: DDPMSchedule, *, seed: int,
-                    sample_offset: int = 0, input_prior: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Whole ancestral sampling loop on the device with Philox noise (esmdiff_ddpm_sample)."""
+                    sample_offset: int = 0, input_prior: Optional[torch.Tensor] = None,
+                    lengths: Optional[Sequence[int]] = None, sample_index: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Whole ancestral sampling loop on the device with Philox noise (esmdiff_ddpm_sample).  lengths: a ragged batch
+        (set_lengths; without input_prior the padded positions start as the structure pad id).  sample_index: (B,) Philox sample
+        index of each row instead of sample_offset + b — then the loop runs on the host, one forward and one
+        esmdiff_ddpm_step_rows per update, and every row draws exactly what its own sample index gives in a plain call."""
         B, L = sequence_tokens.shape
         seq = self._tok(sequence_tokens, B, L)
         if input_prior is None:
             x = torch.full((B, L), STRUCTURE_MASK_TOKEN, dtype=torch.int64, device=self.device)
+            if lengths is not None:
+                pos = torch.arange(L, device=self.device)[None]
+                x[pos >= torch.tensor([int(v) for v in lengths], device=self.device)[:, None]] = STRUCTURE_PAD_TOKEN
         else:
             if tuple(input_prior.shape) != (B, L):
                 raise ValueError(f"Invalid input_prior shape: {tuple(input_prior.shape)} v.s. (seq) {(B, L)}")
             x = input_prior.to(device=self.device, dtype=torch.int64).contiguous().clone()
         self._check_ids(seq, x)
+        if sample_index is not None and len(sample_index) != B:
+            raise ValueError(f"sample_index: {len(sample_index)} entries for a batch of {B}")
         T = schedule.num_steps
         f32 = lambda t: t.detach().to("cpu", torch.float32).contiguous()
         mc_t, mc_s = f32(schedule.mc_t[:T]), f32(schedule.mc_s[:T])
         tf = self.conditioning_rows(schedule.t_freq)
         tf = None if tf is None else f32(tf)
+        with self._lengths_for_call(lengths, seq, x):
+            if sample_index is not None:
+                return self._ddpm_sample_rows(seq, x, T, mc_t, mc_s, tf, seed, sample_index)
+            return self._ddpm_sample_device(seq, x, T, mc_t, mc_s, tf, seed, sample_offset)
+
+    def _ddpm_sample_rows(self, seq, x, T, mc_t, mc_s, tf, seed, sample_index) -> torch.Tensor:
+        """esmdiff_ddpm_sample's loop on the host with per-row sample indices: forward i with sinusoid i, update i (the noise
+        removal pass at i = T) through esmdiff_ddpm_step_rows."""
+        B, L = x.shape
+        idx = [int(v) for v in sample_index]
+        logits = torch.empty(B, L, self.ld_logits, dtype=torch.float32, device=self.device)
+        for i in range(T + 1):
+            fin = i == T
+            lg = self.forward_logits(x, seq, None if tf is None else tf[i], out=logits, check_ids=False)
+            params = self.sample_step_params(idx, 0.0 if fin else float(mc_t[i]), 0.0 if fin else float(mc_s[i]), i, int(fin))
+            self.ddpm_step_rows(x, lg, params, seed=seed)
+        return x
+
+    def _ddpm_sample_device(self, seq, x, T, mc_t, mc_s, tf, seed, sample_offset) -> torch.Tensor:
+        B, L = x.shape
         rng = N.Rng(int(seed), int(sample_offset))
         as_p = lambda t: t.numpy().ctypes.data_as(N.c_f32p)
         self._chk(self._lib.esmdiff_ddpm_sample(self._h, _ptr(seq), _ptr(x), B, L, T, as_p(mc_t), as_p(mc_s),
@@ -354,8 +431,11 @@ class Engine:
         return x
 
     def gibbs_sample(self, sequence_tokens: torch.Tensor, x0: torch.Tensor, n_unmask_table: torch.Tensor,
-                     temperature: float, top_p: float, *, seed: int, sample_offset: int = 0) -> torch.Tensor:
-        """Whole iterative-unmasking loop on the device (esmdiff_gibbs_sample).  n_unmask_table: (T,B) int32."""
+                     temperature: float, top_p: float, *, seed: int, sample_offset: int = 0,
+                     lengths: Optional[Sequence[int]] = None, sample_index: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Whole iterative-unmasking loop on the device (esmdiff_gibbs_sample).  n_unmask_table: (T,B) int32.  lengths: a ragged
+        batch (set_lengths; x0 holds the structure pad id beyond each length).  sample_index: (B,) Philox sample index per row
+        instead of sample_offset + b — a host loop of forward + esmdiff_gibbs_step_rows, per row the ids of a plain call."""
         B, L = sequence_tokens.shape
         seq = self._tok(sequence_tokens, B, L)
         x = x0.to(device=self.device, dtype=torch.int64).contiguous().clone()
@@ -363,6 +443,22 @@ class Engine:
         tab = n_unmask_table.detach().to("cpu", torch.int32).contiguous()
         T = tab.shape[0]
         assert tab.shape == (T, B)
+        if sample_index is not None and len(sample_index) != B:
+            raise ValueError(f"sample_index: {len(sample_index)} entries for a batch of {B}")
+        with self._lengths_for_call(lengths, seq, x):
+            if sample_index is not None:
+                idx = [int(v) for v in sample_index]
+                logits = torch.empty(B, L, self.ld_logits, dtype=torch.float32, device=self.device)
+                for i in range(T):
+                    lg = self.forward_logits(x, seq, None, out=logits, check_ids=False)
+                    params = torch.from_numpy(self.gibbs_step_params_host(idx, i, tab[i].numpy())).to(self.device)
+                    self.gibbs_step_rows(x, seq, lg, temperature, top_p, params, seed=seed)
+                return x
+            return self._gibbs_sample_device(seq, x, tab, temperature, top_p, seed, sample_offset)
+
+    def _gibbs_sample_device(self, seq, x, tab, temperature, top_p, seed, sample_offset) -> torch.Tensor:
+        B, L = x.shape
+        T = tab.shape[0]
         rng = N.Rng(int(seed), int(sample_offset))
         self._chk(self._lib.esmdiff_gibbs_sample(self._h, _ptr(seq), _ptr(x), B, L, T, float(temperature), float(top_p),
                                                  tab.numpy().ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
@@ -474,6 +570,19 @@ class Engine:
         fn = self._lib.esmdiff_attention_bf16 if qkv.dtype == torch.bfloat16 else self._lib.esmdiff_attention_f16
         self._chk(fn(self._h, _ptr(qkv), _ptr(q_ln_w.float().contiguous()), _ptr(k_ln_w.float().contiguous()), _ptr(ctx),
                      B, L, _stream()))
+        return ctx
+
+    def attention_ragged(self, qkv: torch.Tensor, q_ln_w: torch.Tensor, k_ln_w: torch.Tensor, B: int, L: int,
+                         lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """q/k LayerNorm + rotary + attention in this engine's precision (esmdiff_attention_ragged): qkv [B*L, 3*D] bf16 / f16
+        (16-bit engines) or f32 (f32, f32_split) -> ctx [B*L, D] of the same dtype; `lengths` (B,) selects the ragged kernels."""
+        D = self.cfg.d_model
+        want = {"bf16": torch.bfloat16, "f16": torch.float16}.get(self.precision, torch.float32)
+        assert qkv.dtype == want and qkv.shape == (B * L, 3 * D) and qkv.is_contiguous()
+        ctx = torch.full((B * L, D), float("nan"), dtype=qkv.dtype, device=self.device)   # NaN: a row the kernel skips shows
+        arr = None if lengths is None else (ctypes.c_int32 * B)(*[int(v) for v in lengths])
+        self._chk(self._lib.esmdiff_attention_ragged(self._h, _ptr(qkv), _ptr(q_ln_w.float().contiguous()),
+                                                     _ptr(k_ln_w.float().contiguous()), _ptr(ctx), arr, B, L, _stream()))
         return ctx
 
     def qk_norm_rope(self, qkv: torch.Tensor, q_ln_w: torch.Tensor, k_ln_w: torch.Tensor, B: int, L: int, H: int):

@@ -67,12 +67,18 @@ def encode_structure_prior(protein: ESMProtein, n_tokens: int) -> torch.Tensor:
 
 @torch.no_grad()
 def iterative_sampling_raw(client, proteins: Sequence[ESMProtein], configs: Sequence[GenerationConfig], *,
-                           seed: int = 0, sample_offset: int = 0, decoder=None, encoder=None) -> List[ESMProtein]:
+                           seed: int = 0, sample_offset: int = 0, decoder=None, encoder=None,
+                           sample_index=None) -> List[ESMProtein]:
     """client: an esmdiff_amd Engine, or an object with a `.net` Engine (the model wrapper); `decoder` / `encoder` default to
     the client's own `.decoder` / `.encoder` attributes when it has them.  `GenerationConfig.condition_on_coordinates_only =
     False` [ESM-RECALL: esm then also feeds the structure TOKENS its VQ-VAE encoder derives from the coordinates]: proteins
     that carry coordinates but no structure tokens get them from `encoder` (an esmdiff_amd.engine.StructureEncoder) for every
-    residue with finite coordinates; those positions are then known tokens, not MASK, and are not sampled."""
+    residue with finite coordinates; those positions are then known tokens, not MASK, and are not sampled.
+
+    Proteins of different lengths run as one ragged batch (Engine.set_lengths): padded to the longest with the pad ids (and
+    NaN coordinates), each protein's ids are those of its own run at the same Philox sample index (sample_offset + its place
+    in the list), and each comes back trimmed to its own length.  Not with certified sampling.  sample_index (one per protein):
+    the Philox sample index of each protein instead of sample_offset + its place (packed batches of several targets)."""
     eng = getattr(client, "net", client)
     # precision "certified" (esmdiff_amd/certified.py): `net` is the f32-grade engine, `fast` the f16 one that draws every step; the
     # decisions of a step that the f16 logits leave open are verified on `net` — the ids of `net`'s own chain at ~2x its rate
@@ -94,11 +100,17 @@ def iterative_sampling_raw(client, proteins: Sequence[ESMProtein], configs: Sequ
         if c.strategy not in ("entropy", "random"):
             raise ValueError(f"strategy {c.strategy!r}: 'entropy' or 'random'")
     seqs = [encode_sequence(p.sequence) for p in proteins]
-    L = seqs[0].numel()
-    if any(s.numel() != L for s in seqs):
-        raise ValueError("all proteins of a batch must have the same length")
-    seq = torch.stack(seqs)
-    x0 = torch.stack([encode_structure_prior(p, L) for p in proteins])
+    lens = [s.numel() for s in seqs]
+    L = max(lens)
+    ragged = min(lens) != L
+    if (ragged or sample_index is not None) and cert is not None:
+        raise NotImplementedError("certified sampling takes proteins of one length; mixed lengths run with precision "
+                                  "f16, bf16, f32_split or f32")
+    seq = torch.full((len(proteins), L), C.SEQUENCE_PAD_TOKEN, dtype=torch.int64)
+    x0 = torch.full((len(proteins), L), C.STRUCTURE_PAD_TOKEN, dtype=torch.int64)
+    for b, (p, s) in enumerate(zip(proteins, seqs)):
+        seq[b, :lens[b]] = s
+        x0[b, :lens[b]] = encode_structure_prior(p, lens[b])
     has_xyz = [p.coordinates is not None for p in proteins]
     for b, (p, c) in enumerate(zip(proteins, configs)):
         if not getattr(c, "condition_on_coordinates_only", True) and p.coordinates is not None and p.structure_tokens is None:
@@ -106,9 +118,9 @@ def iterative_sampling_raw(client, proteins: Sequence[ESMProtein], configs: Sequ
                 raise RuntimeError("condition_on_coordinates_only=False needs the VQ-VAE structure encoder: pass encoder= "
                                    "(esmdiff_amd.engine.StructureEncoder; CLI: --encoder_ckpt)")
             cb = torch.as_tensor(p.coordinates, dtype=torch.float32)
-            if cb.shape[0] != L - 2:
-                raise ValueError(f"coordinates cover {cb.shape[0]} residues, sequence has {L - 2}")
-            x0[b, 1:-1] = encoder.encode(cb[None]).reshape(-1).to(x0.device)     # MASK where a residue has no coordinates
+            if cb.shape[0] != lens[b] - 2:
+                raise ValueError(f"coordinates cover {cb.shape[0]} residues, sequence has {lens[b] - 2}")
+            x0[b, 1:lens[b] - 1] = encoder.encode(cb[None]).reshape(-1).to(x0.device)     # MASK where a residue has no coordinates
     frames = None
     if any(has_xyz):
         from .geometry import build_affine3d_from_coordinates
@@ -119,9 +131,9 @@ def iterative_sampling_raw(client, proteins: Sequence[ESMProtein], configs: Sequ
         for b, p in enumerate(proteins):
             if p.coordinates is not None:
                 cb = torch.as_tensor(p.coordinates, dtype=torch.float32)
-                if cb.shape[0] != L - 2:
-                    raise ValueError(f"coordinates cover {cb.shape[0]} residues, sequence has {L - 2}")
-                xyz[b, 1:-1] = cb[:, :3, :]                  # BOS / EOS carry no coordinates
+                if cb.shape[0] != lens[b] - 2:
+                    raise ValueError(f"coordinates cover {cb.shape[0]} residues, sequence has {lens[b] - 2}")
+                xyz[b, 1:lens[b] - 1] = cb[:, :3, :]         # BOS / EOS and padding carry no coordinates
         frames = build_affine3d_from_coordinates(xyz)
         if cert is None:
             eng.set_frames(*frames)
@@ -144,20 +156,24 @@ def iterative_sampling_raw(client, proteins: Sequence[ESMProtein], configs: Sequ
                                           frames=frames).cpu()
             else:
                 out_x = eng.gibbs_sample(seq, x0, table, cfg0.temperature, cfg0.top_p, seed=seed,
-                                         sample_offset=sample_offset).cpu()
+                                         sample_offset=sample_offset, **({"lengths": lens} if ragged else {}),
+                                         **({} if sample_index is None else {"sample_index": list(sample_index)})).cpu()
         finally:
             if custom:
                 for e_ in engines:
                     e_.set_gibbs_options()
     if any(has_xyz) and cert is None:
         eng.set_frames(None)
-    coords = plddt = ptm = None
+    coords, plddt, ptm = [None] * len(proteins), [None] * len(proteins), [None] * len(proteins)
     if decoder is not None:                        # esm: client.decode(tensor) -> ESMProtein with coordinates, pLDDT, pTM
         from .sample_esmdiff import decode_tokens
-        coords, plddt, ptm = decode_tokens(out_x[:, 1:-1], decoder, return_ptm=True)
-        coords, plddt = coords.cpu(), (None if plddt is None else plddt.cpu())
-        ptm = None if ptm is None else ptm.cpu()
-    return [ESMProtein(sequence=p.sequence, coordinates=None if coords is None else coords[b],
-                       structure_tokens=out_x[b, 1:-1].clone(), plddt=None if plddt is None else plddt[b],
-                       ptm=None if ptm is None else ptm[b])
+        for n in sorted(set(lens)):                # the decoder takes one length per call: one call per length group
+            rows = [b for b in range(len(proteins)) if lens[b] == n]
+            c_, p_, t_ = decode_tokens(out_x[rows, 1:n - 1], decoder, return_ptm=True)
+            for j, b in enumerate(rows):
+                coords[b] = c_[j].cpu()
+                plddt[b] = None if p_ is None else p_[j].cpu()
+                ptm[b] = None if t_ is None else t_[j].cpu()
+    return [ESMProtein(sequence=p.sequence, coordinates=coords[b], structure_tokens=out_x[b, 1:lens[b] - 1].clone(),
+                       plddt=plddt[b], ptm=ptm[b])
             for b, p in enumerate(proteins)]

@@ -172,7 +172,9 @@ class MaskedDiffusionLanguageModeling:
 
     @torch.no_grad()
     def ddpm_sample(self, sequence_tokens, num_steps=None, eps=1e-5, input_prior=None, sample_max_t=1.0, *,
-                    seed: int = 0, sample_offset: int = 0, noise: str = "philox"):
+                    seed: int = 0, sample_offset: int = 0, noise: str = "philox", lengths=None, sample_index=None):
+        """lengths / sample_index: a ragged batch and per-row Philox sample indices (Engine.ddpm_sample; philox noise with noise
+        removal, not with certified sampling)."""
         if num_steps is None:
             print("Using by default num_steps: 1000")
             num_steps = 1000
@@ -184,6 +186,12 @@ class MaskedDiffusionLanguageModeling:
                 f"Invalid input_prior shape: {input_prior.shape} v.s. (seq) {sequence_tokens.shape}"
         sch = ddpm_schedule(num_steps, eps, sample_max_t, self.noise, self.cfg.freq_dim)
         B, L = sequence_tokens.shape
+        if lengths is not None or sample_index is not None:
+            if noise != "philox" or not self.noise_removal or self.certified is not None:
+                raise NotImplementedError("lengths / sample_index need Philox noise with noise removal on a f16, bf16, f32_split "
+                                          "or f32 engine (not certified sampling)")
+            return self.net.ddpm_sample(sequence_tokens, sch, seed=seed, input_prior=input_prior, lengths=lengths,
+                                        sample_index=sample_index)
         if noise == "philox" and self.noise_removal:
             loop = self.certified if self.certified is not None else self.net
             return loop.ddpm_sample(sequence_tokens, sch, seed=seed, sample_offset=sample_offset, input_prior=input_prior)

@@ -145,6 +145,28 @@ def certified_record(cs) -> dict:
     return {k: cs.stats.get(k) for k in keys if k in cs.stats}
 
 
+def ddpm_masked_inputs(sequence: str, coordinates, mask_ids, structure_tokens, encoder):
+    """--mode ddpm --mask_ids: (sequence with the masked residues as '_', structure tokens with BOS / EOS of the known
+    residues); unchanged inputs without mask_ids."""
+    if mask_ids is not None and structure_tokens is None and coordinates is not None and encoder is not None:
+        # protseq_to_data (models/utils.py:116-137): the masked residues lose their coordinates, the rest is tokenised by
+        # the VQ-VAE encoder; BOS / EOS as esm's tokenizer adds them
+        xyz = torch.as_tensor(coordinates, dtype=torch.float32).clone()
+        for idx in mask_ids:
+            assert 0 <= idx < len(sequence), f"Invalid mask index {idx} for sequence of length {len(sequence)}"
+            xyz[idx] = float("Inf")
+        body = encoder.encode(xyz[None, :, :3, :])[0].cpu()
+        structure_tokens = torch.cat([torch.tensor([C.STRUCTURE_BOS_TOKEN]), body, torch.tensor([C.STRUCTURE_EOS_TOKEN])])
+    if mask_ids is not None:
+        assert structure_tokens is not None, "Need structure tokens of the known residues (or coordinates + an encoder) for masking"
+        seq_l = list(sequence)
+        for idx in mask_ids:
+            assert 0 <= idx < len(seq_l), f"Invalid mask index {idx} for sequence of length {len(seq_l)}"
+            seq_l[idx] = C.MASK_RESIDUE
+        sequence = "".join(seq_l)
+    return sequence, structure_tokens
+
+
 @timer
 @torch.no_grad()
 def ddpm_sample_by_esm(sequence, pl_model, output_dir: Path, sample_basename: str, num_samples: int = 5,
@@ -166,22 +188,7 @@ def ddpm_sample_by_esm(sequence, pl_model, output_dir: Path, sample_basename: st
     if save_to.exists():
         print(f"Skip existing {save_to}")
         return None
-    if mask_ids is not None and structure_tokens is None and coordinates is not None and encoder is not None:
-        # protseq_to_data (models/utils.py:116-137): the masked residues lose their coordinates, the rest is tokenised by
-        # the VQ-VAE encoder; BOS / EOS as esm's tokenizer adds them
-        xyz = torch.as_tensor(coordinates, dtype=torch.float32).clone()
-        for idx in mask_ids:
-            assert 0 <= idx < len(sequence), f"Invalid mask index {idx} for sequence of length {len(sequence)}"
-            xyz[idx] = float("Inf")
-        body = encoder.encode(xyz[None, :, :3, :])[0].cpu()
-        structure_tokens = torch.cat([torch.tensor([C.STRUCTURE_BOS_TOKEN]), body, torch.tensor([C.STRUCTURE_EOS_TOKEN])])
-    if mask_ids is not None:
-        assert structure_tokens is not None, "Need structure tokens of the known residues (or coordinates + an encoder) for masking"
-        seq_l = list(sequence)
-        for idx in mask_ids:
-            assert 0 <= idx < len(seq_l), f"Invalid mask index {idx} for sequence of length {len(seq_l)}"
-            seq_l[idx] = C.MASK_RESIDUE
-        sequence = "".join(seq_l)
+    sequence, structure_tokens = ddpm_masked_inputs(sequence, coordinates, mask_ids, structure_tokens, encoder)
     seq_tok = encode_sequence(sequence)
     start_t = time()
     offset, count = shard_samples(num_samples, world, rank)
@@ -329,6 +336,147 @@ def minibatch_gibbs_by_esm(protseq, esm3_model, output_dir: Path, sample_basenam
     return out_list
 
 
+# --pack_targets: padded tokens per forward, about configs[1]'s 100 samples x 258 tokens (the batch the engine is tuned for)
+DEFAULT_PACK_TOKENS = 100 * 258
+MAX_PAD_SHARE = 0.25
+
+
+def plan_packs(lengths, num_samples: int, world: int = 1, rank: int = 0, budget: int = DEFAULT_PACK_TOKENS,
+               max_pad: float = MAX_PAD_SHARE):
+    """--pack_targets: the ragged batches of one rank.  lengths: tokens per target (BOS and EOS included).  Every target
+    contributes this rank's shard_samples share of its samples, row (t, j) with Philox sample index offset + j — what the
+    per-target run gives it.  Targets are sorted by length (ties: input order) and the rows filled greedily into packs while
+    rows x (longest length) stays within `budget` and the padding within `max_pad` of it; a target's samples may span packs.
+    A pure function of its arguments: every rank computes the same plan.  -> [[(target, sample index), ...], ...]"""
+    offset, count = shard_samples(num_samples, world, rank)
+    order = sorted(range(len(lengths)), key=lambda t: (lengths[t], t))
+    packs, cur, cur_tokens = [], [], 0
+    for t in order:
+        n = lengths[t]                                   # ascending: the row being added is the pack's longest
+        for j in range(count):
+            rows = len(cur) + 1
+            if cur and (rows * n > budget or rows * n - (cur_tokens + n) > max_pad * rows * n):
+                packs.append(cur)
+                cur, cur_tokens = [], 0
+            cur.append((t, offset + j))
+            cur_tokens += n
+    if cur:
+        packs.append(cur)
+    return packs
+
+
+def pack_stats(pack, lengths):
+    """(rows, padded length, padded-row share = padded positions / (rows x L)) of one pack."""
+    L = max(lengths[t] for t, _ in pack)
+    return len(pack), L, 1.0 - sum(lengths[t] for t, _ in pack) / (len(pack) * L)
+
+
+@torch.no_grad()
+def sample_packed(targets, model, args, *, mask_ids=None, coords_of=None, decoder=None, encoder=None):
+    """--pack_targets: the samples of several targets in one ragged batch per forward (Engine.set_lengths), planned by
+    plan_packs.  Outputs per target are those of the per-target drivers: the same directory, <name>.tokens.npy, .json (plus a
+    "pack" record) and .pdb; skip-existing works per target.  Row (t, j) draws with Philox sample index offset_t + j, so the ids
+    equal the per-target run's for f32; bf16 / f16 / f32_split logits may differ at rounding level between batch compositions
+    (batch_sizes), so a near-tie can resolve differently."""
+    from .gibbs import iterative_sampling_raw
+    from .sdk import GenerationConfig
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    str_time = ("_" + strftime("%Y%m%d-%H%M%S")) if not args.no_timestamp else ""
+    temperature, top_p = 1.4, 0.9                        # minibatch_gibbs_by_esm's defaults, what main() runs
+    if args.mode == "ddpm":
+        out_dir = Path(args.output) / f"step{args.num_steps}_eps{1e-5}_N{args.num_samples}{str_time}"
+    else:
+        out_dir = Path(args.output) / f"T{temperature}_step{args.num_steps}_topp{top_p}_N{args.num_samples}{str_time}"
+    work = []                                            # (name, sequence as sampled, ddpm prior | gibbs coordinates)
+    for name, seq in targets:
+        if (out_dir / f"{name}.tokens.npy").exists():
+            if rank == 0:
+                print(f"Skip existing {out_dir / f'{name}.tokens.npy'}")
+            continue
+        coords = coords_of.get(name) if mask_ids is not None else None
+        if args.mode == "ddpm":
+            sq, st = ddpm_masked_inputs(seq, coords, mask_ids, None, encoder)
+            prior = None
+            if mask_ids is not None:
+                prior = torch.as_tensor(st, dtype=torch.int64).clone()
+                for idx in mask_ids:                     # token-space index, as ddpm_sample_by_esm
+                    prior[idx] = C.STRUCTURE_MASK_TOKEN
+            work.append((name, sq, prior))
+        else:
+            if mask_ids is not None and coords is None:
+                raise SystemExit("--mask_ids needs the coordinates of an input PDB")
+            sq = seq
+            if mask_ids is not None:
+                coords = torch.as_tensor(coords, dtype=torch.float32).clone()
+                sl = list(seq)
+                for idx in mask_ids:
+                    assert 0 <= idx < len(sl), f"Invalid mask index {idx} for sequence of length {len(sl)}"
+                    sl[idx] = C.MASK_RESIDUE
+                    coords[idx] = float("Inf")
+                sq = "".join(sl)
+            work.append((name, sq, coords))
+    if not work:
+        return
+    lengths = [len(sq) + 2 for _, sq, _ in work]
+    packs = plan_packs(lengths, args.num_samples, world, rank, args.pack_tokens)
+    offset, count = shard_samples(args.num_samples, world, rank)
+    local = [[None] * count for _ in work]
+    records = [[] for _ in work]
+    for pid, pack in enumerate(packs):
+        rows, L, pad = pack_stats(pack, lengths)
+        lens = [lengths[t] for t, _ in pack]
+        idx = [i for _, i in pack]
+        t0 = time()
+        if args.mode == "ddpm":
+            seq = torch.full((rows, L), C.SEQUENCE_PAD_TOKEN, dtype=torch.int64)
+            prior = None if mask_ids is None else torch.full((rows, L), C.STRUCTURE_PAD_TOKEN, dtype=torch.int64)
+            for r, (t, _) in enumerate(pack):
+                seq[r, :lens[r]] = encode_sequence(work[t][1])
+                if prior is not None:
+                    prior[r, :lens[r]] = work[t][2]
+            x = model.ddpm_sample(num_steps=args.num_steps, sequence_tokens=seq, eps=1e-5, input_prior=prior, seed=args.seed,
+                                  lengths=lens, sample_index=idx).cpu()
+            out = [x[r, 1:lens[r] - 1] for r in range(rows)]
+        else:
+            prots = [ESMProtein(sequence=work[t][1], coordinates=work[t][2]) for t, _ in pack]
+            cfgs = [GenerationConfig(track="structure", num_steps=args.num_steps, temperature=temperature, top_p=top_p)] * rows
+            out = [o.structure_tokens for o in iterative_sampling_raw(model, prots, cfgs, seed=args.seed, sample_index=idx)]
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        dt = time() - t0
+        names = sorted({work[t][0] for t, _ in pack})
+        if rank == 0:
+            print(f"Sampling token time: {dt:.2f}s (pack {pid}: {rows} rows x {L} tokens, padding {pad:.1%}, "
+                  f"{len(names)} targets)")
+        rec = {"id": pid, "targets": names, "rows": rows, "padded_row_share": round(pad, 4), "pack_seconds": round(dt, 3)}
+        for r, (t, i) in enumerate(pack):
+            local[t][i - offset] = out[r]
+            if not records[t] or records[t][-1] is not rec:
+                records[t].append(rec)
+    dev = getattr(model, "net", model).device
+    for t, (name, sq, _) in enumerate(work):            # target order on every rank: the gathers pair up
+        n = lengths[t] - 2
+        lt = torch.stack(local[t]).to(dev) if count else torch.empty(0, n, dtype=torch.int64, device=dev)
+        tokens = gather_ids(lt, args.num_samples)
+        coords = plddt = ptm = None
+        if decoder is not None:
+            coords, plddt, ptm = decode_shard_and_gather(lt, decoder, args.num_samples, return_ptm=True)
+        if rank == 0:
+            out_dir.mkdir(parents=True, exist_ok=True)
+            np.save(out_dir / f"{name}.tokens.npy", tokens.cpu().numpy().astype(np.int16))
+            meta = {"sequence": sq, "num_steps": args.num_steps, "num_samples": args.num_samples, "seed": args.seed,
+                    "world_size": world, "precision": getattr(getattr(model, "net", model), "precision", None),
+                    "pack": records[t]}
+            meta.update({"eps": 1e-5, "noise": "philox"} if args.mode == "ddpm" else
+                        {"mode": "gibbs", "temperature": temperature, "top_p": top_p})
+            if ptm is not None:
+                meta["ptm"] = [round(float(v), 4) for v in ptm.cpu()]
+            (out_dir / f"{name}.json").write_text(json.dumps(meta, indent=1))
+            if coords is not None:
+                write_models_pdb(coords, plddt, sq, out_dir / f"{name}.pdb", name)
+
+
 def get_argparser(argv=None):
     p = argparse.ArgumentParser(description="Evaluate the ensemble of protein structures.")
     p.add_argument("--input", type=str, default="data/targets/bpti", help="Path to the data directory.")
@@ -371,6 +519,14 @@ def get_argparser(argv=None):
                    help="arithmetic of the VQ-VAE structure decoder (and encoder): f32 (default, backbone within 1e-4 A of a float32 "
                         "decode, encoder codes equal to a float32 encoder's) or bf16")
     p.add_argument("--no_timestamp", action="store_true")
+    p.add_argument("--pack_targets", action="store_true",
+                   help="sample the targets of --input together: the samples of several targets share one padded (ragged) batch "
+                        "per forward, planned from the target lengths (sorted, filled up to --pack_tokens with at most 25 %% "
+                        "padding).  Same per-target outputs; a row keeps its per-target Philox sample index, so ids equal the "
+                        "per-target run's for --precision f32 and may differ at near-ties for bf16 / f16 / f32_split (batch "
+                        "composition moves their logits at rounding level).  Not with --precision certified or --parity")
+    p.add_argument("--pack_tokens", type=int, default=DEFAULT_PACK_TOKENS,
+                   help="--pack_targets: padded tokens per forward (rows x longest length; default 100 x 258)")
     return p.parse_args(argv)
 
 
@@ -378,6 +534,12 @@ def main(argv=None):
     args = get_argparser(argv)
     if args.head_precision in ("body", "bf16", "f16"):   # explicit: the head in the body's precision, also for the certified sampler's fast engine
         args.head_precision = {"bf16": "bf16", "f16": "f16", "certified": "f16"}.get(args.precision)
+    if args.pack_targets and args.parity:
+        raise SystemExit("--pack_targets cannot be combined with --parity: the reference's per-batch torch.rand stream "
+                         "cannot be packed")
+    if args.pack_targets and args.precision == "certified":
+        raise SystemExit("--pack_targets runs ragged batches, which certified sampling does not take: pass --precision "
+                         "f16|bf16|f32_split|f32")
     if args.parity and args.precision == "certified":
         args.precision = "f32_split"       # the reference's torch.rand stream is drawn per batch on one engine: the float32-grade one
     rank = int(os.environ.get("RANK", "0"))
@@ -427,6 +589,9 @@ def main(argv=None):
     # batch can exceed the regular one); bounded so that one 288 GB GPU holds the workspace, larger batches are chunked
     max_b = engine_capacity([len(s) for _, s in targets], per_rank, args.n_max_residue_square, args.mode)
     max_b = max(1, min(max_b, per_rank, max(1, (4 * DEFAULT_NMAX) // (max_len * max_len))))
+    if args.pack_targets:          # the largest pack of any rank (the plan is the same on every rank)
+        max_b = max(len(pk) for r in range(world)
+                    for pk in plan_packs([len(s) + 2 for _, s in targets], args.num_samples, world, r, args.pack_tokens) or [[0]])
     if args.random_init:
         from .config import ESM3_OPEN, TINY
         model = random_init_model(TINY if args.tiny else ESM3_OPEN, seed=args.seed, max_batch=max_b, max_len=max_len,
@@ -465,7 +630,9 @@ def main(argv=None):
           f"{'' if not lt else ' (' + lt['path'] + ')'}, NUMA pinning = {numa}", flush=True)
     if rank == 0:
         print(f">>> Sampling mode = {args.mode}, precision = {args.precision} ...")
-    for name, seq in targets:
+    if args.pack_targets:
+        sample_packed(targets, model, args, mask_ids=mask_ids, coords_of=coords_of, decoder=decoder, encoder=encoder)
+    for name, seq in ([] if args.pack_targets else targets):
         if args.mode == "gibbs":
             coordinates = coords_of.get(name) if mask_ids is not None else None   # sample_esmdiff.py:286-289
             if mask_ids is not None and coordinates is None:

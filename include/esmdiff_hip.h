@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ESMDIFF_ABI_VERSION 8   /* 8: + esmdiff_gibbs_step_rows; esmdiff_logit_error_stats writes 8 floats per row and takes all_columns; 7: + esmdiff_ddpm_step_rows, esmdiff_logit_error_stats (additions only); 6: + esmdiff_ddpm_step_margin, esmdiff_forward_logits_sigmas, esmdiff_set_small_batch_splitk */
+#define ESMDIFF_ABI_VERSION 8   /* 8: + esmdiff_gibbs_step_rows, esmdiff_set_lengths (an addition); esmdiff_logit_error_stats writes 8 floats per row and takes all_columns; 7: + esmdiff_ddpm_step_rows, esmdiff_logit_error_stats (additions only); 6: + esmdiff_ddpm_step_margin, esmdiff_forward_logits_sigmas, esmdiff_set_small_batch_splitk */
 
 /* structure-track vocabulary: esm constants mirrored at model.py:380-381 */
 #define ESMDIFF_VOCAB 4101
@@ -344,6 +344,16 @@ int esmdiff_gibbs_sample(esmdiff_engine* eng, const int64_t* seq, int64_t* x_ino
  * (ESMDIFF_E_MISSING otherwise). */
 int esmdiff_set_frames(esmdiff_engine* eng, const float* rot, const float* trans, const uint8_t* has_frame,
                        int32_t B, int32_t L, void* stream);
+
+/* Ragged batch for the following calls: B samples padded to one L, sample b valid on tokens [0, lens[b]) (lens counts BOS and
+ * EOS; each in 3..max_len).  Padding sits at the end of a row and holds the pad ids (sequence 1, structure 4099 = never MASK).
+ * A valid position's logits and ids then depend only on its own sample's valid positions: attention masks the padded keys and
+ * writes zeros for padded query rows, every other kernel is row-wise.  lens is a HOST array, copied (synchronously) to a device
+ * buffer of max_batch entries; NULL clears it.  Stateful like esmdiff_set_frames: while set, esmdiff_forward_logits[_sigmas],
+ * esmdiff_ddpm_sample, esmdiff_gibbs_sample and the *_step_rows entries refuse (ESMDIFF_E_INVALID) a call whose B differs
+ * from the set B or whose L is below a length, step-0 sharing is off, and esmdiff_describe_plan(B) reports
+ * "ragged=1 valid_tokens=...".  The GEMMs still run the padded rows. */
+int esmdiff_set_lengths(esmdiff_engine* eng, const int32_t* lens, int32_t B);
 
 /* VQ-VAE structure-token decoder: structure tokens -> backbone coordinates.  Replaces `esm3.decode(...)` as the
  * reference's decode() helper calls it once per sample (/root/reference/slm/sample_esmdiff.py:40-61, :225-230; the

@@ -81,6 +81,13 @@ int esmdiff_attention_bf16(esmdiff_engine* eng, const void* qkv, const float* q_
 int esmdiff_attention_f16(esmdiff_engine* eng, const void* qkv, const float* q_ln_w, const float* k_ln_w,
                           void* ctx, int32_t B, int32_t L, void* stream);
 
+/* Ragged attention (esmdiff_set_lengths' kernels) in the engine's own precision: q/k LayerNorm + rotary + attention of qkv
+ * [B*L, 3*D] -> ctx [B*L, D], bf16 / f16 for 16-bit engines, f32 for F32 and F32_SPLIT ones (F32_SPLIT: unit split scales).
+ * lens: HOST int32 [B], each in 1..L (sample b valid on tokens [0, lens[b]), its context rows beyond are written as zeros), or
+ * NULL for the plain kernels.  Synchronous when lens is given. */
+int esmdiff_attention_ragged(esmdiff_engine* eng, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* ctx,
+                             const int32_t* lens, int32_t B, int32_t L, void* stream);
+
 /* The q/k LayerNorm + rotary kernel alone, in the engine's 16-bit build (bf16 or f16; float32 engines are refused) with its
  * rotary tables: qkv [B*L, 3*H*64] -> q, k [B*L, H*64] token-major, q pre-scaled by log2(e)/8.  H (1 .. 32) is explicit and
  * independent of the engine's n_heads; L <= max_len. */
