@@ -24,6 +24,7 @@ UNITS = {
     "engine": [],
     "gemm": [],
     "gemm256w4": [],
+    "gemm256w4_split": [],    # f16 plane triples whatever the 16-bit operand type: not in F16_UNITS
     "gemm_split": [],
     "attention_split": [],
     "strict": [],

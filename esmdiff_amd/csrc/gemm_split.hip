@@ -5,7 +5,7 @@
 // MFMA rate.  A float32 value splits EXACTLY enough into two f16 numbers, x = hi + lo + r with |r| <= 2^-22 |x| (11 + 11
 // significand bits), and the product of two f16 numbers is exact in f32, so
 //     a . w  =  a_hi . w_hi  +  a_hi . w_lo  +  a_lo . w_hi      (+ a_lo . w_lo ~ 2^-22, dropped)
-// is three passes of v_mfma_f32_32x32x16_f16 into one f32 accumulator (gemm256w4.hip, SPLIT = 1): float32-grade products
+// is three passes of v_mfma_f32_32x32x16_f16 into one f32 accumulator (gemm256w4_split.hip): float32-grade products
 // (error 3 x 2^-22 per term, below the f32 accumulation round-off of a K >= 1536 dot product) at 1/3 of the bf16 rate
 // instead of 1/16.  (A bf16 split needs three parts and six passes for the same 22+ bits.)
 //
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256) void split_weight_kernel(const void* __restric
 }
 
 // x[m, n] = x[m, n] + ((parts[0] + parts[1]) + ... + parts[S-1])[m, n] * rs[m] / div: the epilogue of the K-sliced split GEMM
-// (gemm256w4.hip::launch_gemm256w4_splitk) for the two residual linears.  parts: [S][m_pad, N] f32, slices summed in order; the
+// (gemm256w4_split.hip::launch_gemm256w4_splitk) for the two residual linears.  parts: [S][m_pad, N] f32, slices summed in order; the
 // row scale is a power of two, so applying it after the sum is exact; `x + v / div` is the unsliced kernel's expression.
 __global__ __launch_bounds__(256) void splitk_reduce_resid_kernel(const float* __restrict__ parts, const float* __restrict__ rs,
                                                                   float* __restrict__ x, int M, int N, int S, int64_t plane, float div) {

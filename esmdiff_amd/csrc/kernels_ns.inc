@@ -81,7 +81,8 @@ int gemm_partial_splits(int N, int K);
 hipError_t launch_gemm_partials(const bf16_t* A, const bf16_t* W, const GemmWorkspace* ws, int M, int N, int K,
                                 hipStream_t stream, GemmPartials* res);
 
-// gemm256w4.hip: the same tile with 4 waves x 128x128 wave tiles, hand-placed main loop, accumulators in AGPRs; K % 128 == 0
+// gemm256w4.hip: the same tile with 4 waves x 128x128 wave tiles, hand-placed v_mfma_f32_16x16x32 main loop, accumulators in
+// AGPRs; K % 128 == 0
 hipError_t launch_gemm256w4_bf16(const bf16_t* A, const bf16_t* W, void* out, const float* bias, int M, int N,
                                  int K, int ldc, float alpha, int epilogue, hipStream_t stream);
 
@@ -150,13 +151,14 @@ hipError_t launch_qk_norm_rope_f32(const float* qkv, const float* q_ln_w, const 
 hipError_t launch_attention_f32(const float* q, const float* k, const float* qkv, float* ctx, int B, int L, int H,
                                 hipStream_t stream, const int32_t* lens = nullptr);   // lens: as launch_attention's
 
-// ---- gemm_split.hip + gemm256w4.hip (SPLIT): float32-grade linears as three f16 MFMA passes over split operands ----
+// ---- gemm_split.hip + gemm256w4_split.hip: float32-grade linears as three f16 MFMA passes over split operands ----
+// (gemm256w4_split.hip is compiled once, into namespace ed; the ed16 view of this header declares its launchers without a definition)
 // A3 f16 [M, 3K] = [hi | lo | hi] scaled per row (rs[M] = 1 / row scale), W3 f16 [N_pad, 3K] = [lo | hi | hi] scaled per
 // matrix (w_inv_scale = 1 / scale); out f32 [M, ldc] = epi(rs[m] * w_inv_scale * A . W^T); N % 256 == 0, K % 128 == 0,
 // ldc >= N (no column bound in the kernel); epi: ESMDIFF_F32EPI_STORE (+ bias[N] when non-null) or ESMDIFF_F32EPI_RESID_DIV.
 hipError_t launch_gemm256w4_split(const uint16_t* A2, const float* rs, const uint16_t* W2, float w_inv_scale, float* out,
                                   const float* bias, int M, int N, int K, int ldc, float div, int epi, hipStream_t stream);
-// K-sliced form for launches with few tiles (S slices as extra row blocks; gemm256w4.hip) and the pass that sums the slices
+// K-sliced form for launches with few tiles (S slices as extra row blocks; gemm256w4_split.hip) and the pass that sums the slices
 // in order, applies the row scales and adds the result into the residual stream: x = x + (sum_s parts[s]) * rs[m] / div
 hipError_t launch_gemm256w4_splitk(const uint16_t* A2, const uint16_t* W2, float w_scale, float* parts, int M, int N, int K,
                                    int S, hipStream_t stream);

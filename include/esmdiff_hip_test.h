@@ -42,7 +42,7 @@ typedef enum {
 int esmdiff_gemm_f32(const float* A, int32_t lda, const float* W, float* out, const float* bias, int32_t M, int32_t N,
                      int32_t K, int32_t ldc, int32_t n_valid, float div, int32_t epilogue, void* stream);
 
-/* The F32_SPLIT path's linear and its operand preparation (csrc/gemm_split.hip, csrc/gemm256w4.hip SPLIT = 1).
+/* The F32_SPLIT path's linear and its operand preparation (csrc/gemm_split.hip, csrc/gemm256w4_split.hip).
  *   esmdiff_split_rows    src f32 [M,K] (row stride ld) -> a3 f16 [M,3K] = [hi | lo | hi] of src * 2^k(row), rs[M] = 2^-k(row)
  *   esmdiff_split_weight  src f32 [N,K] -> w3 f16 [N_pad,3K] = [lo | hi | hi] of src * 2^k (rows N..N_pad-1 zero-filled,
  *                         N_pad a multiple of 256 >= N), *inv_scale_out [host] = 2^-k; synchronous

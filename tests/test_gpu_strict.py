@@ -85,7 +85,7 @@ def test_gemm_f32_vs_float64(M, N, K):
                                          (1, 256, 128, 1.0)])
 def test_gemm_split_vs_float64(M, N, K, scale):
     """The F32_SPLIT linear (three v_mfma_f32_32x32x16_f16 passes over operands split into two f16 numbers, csrc/gemm_split.hip +
-    gemm256w4.hip SPLIT) against a float64 product.  Bar: the SAME bound as the exact-f32 kernel's (2e-6 Sum|a w|); measured the
+    gemm256w4_split.hip) against a float64 product.  Bar: the SAME bound as the exact-f32 kernel's (2e-6 Sum|a w|); measured the
     split product is the more accurate of the two (1e-7 vs 3.5e-7 max: its products are exact to 2^-22 and it rounds once per 16
     terms, an fmaf chain once per term).  Rows mix magnitudes over 3 decades (f16 subnormal lo parts), whole rows are scaled by
     1e-4 / 3e3 (the per-row power-of-two scale), ragged M and N (padded weight rows, multi-tile persistent walk at M = 2600)."""

@@ -123,29 +123,30 @@ def test_product_library_reads_no_tuning_environment():
 
 
 def test_hand_placed_gemm_has_no_sgpr_reload_hazard():
-    """tools/check_asm_hazards.py on the hand-placed GEMM (csrc/gemm256w4.hip), both operand-type builds: hipcc may reload a
-    spilled SGPR with v_readlane directly in front of an inline-asm LDS-DMA that uses it as scalar base — a VALU-writes-SGPR ->
-    VMEM hazard (5 wait states) that nobody pads inside an asm statement; the first split-f16 build faulted that way at multi-tile
-    launches (r04).  The check compiles to gfx950 assembly (no GPU needed) and must find no such pair; the SPLIT kernels, whose
-    main loop has no slack at all, must not spill at all."""
+    """tools/check_asm_hazards.py on the hand-placed GEMMs: csrc/gemm256w4.hip in both operand-type builds and
+    csrc/gemm256w4_split.hip (compiled once).  hipcc may reload a spilled SGPR with v_readlane directly in front of an inline-asm
+    LDS-DMA that uses it as scalar base — a VALU-writes-SGPR -> VMEM hazard (5 wait states) that nobody pads inside an asm
+    statement; the first split-f16 build faulted that way at multi-tile launches (r04).  The check compiles to gfx950 assembly (no
+    GPU needed) and must find no such pair; the split kernels, whose main loop has no slack at all, must not spill at all."""
     import subprocess
     import sys
     sys.path.insert(0, str(ROOT / "tools"))
     import check_asm_hazards as chk
-    src = ROOT / "esmdiff_amd" / "csrc" / "gemm256w4.hip"
-    for extra in ([], ["-DED_F16", "-Ded=ed16"]):
+    csrc = ROOT / "esmdiff_amd" / "csrc"
+    for src, extra in ((csrc / "gemm256w4.hip", []), (csrc / "gemm256w4.hip", ["-DED_F16", "-Ded=ed16"]), (csrc / "gemm256w4_split.hip", [])):
         r = subprocess.run(["/opt/rocm/bin/hipcc", *chk.FLAGS, *extra, str(src), "-o", "/dev/stdout"], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
         seen = 0
         for name, meta, hazards in chk.analyse(r.stdout):
             assert not hazards, (name, hazards[:3])
             seen += 1
-            if "ELi1EEE" in name:          # gemm256w4_kernel<EPI, SPLIT = 1>
+            assert ("gemm256w4_split_kernel" in name) == (src.name == "gemm256w4_split.hip"), name
+            if "gemm256w4_split_kernel" in name and "ELb0EEE" in name:   # gemm256w4_split_kernel<EPI, KSLICED = false>
                 assert meta.get("vgpr_spill_count", 0) == 0, (name, meta)
                 if "ILi4E" not in name:    # (the fused-SwiGLU epilogue keeps a few scalars in VGPR lanes; none is reloaded near asm)
                     assert meta.get("sgpr_spill_count", 0) == 0, (name, meta)
             assert meta.get("agpr_count") == 256, (name, meta)      # the 128 x 128 wave tile lives in the accumulation registers
-        assert seen == 10, seen            # 5 bf16/f16 epilogues + 4 SPLIT = 1 + the K-sliced SPLIT = 2 store kernel
+        assert seen == 5, (src.name, extra, seen)   # 5 bf16 / f16 epilogues; 4 split epilogues + the K-sliced store kernel
 
 
 def test_no_kernel_ships_the_packed_float_form_that_fails_beside_the_gemm():

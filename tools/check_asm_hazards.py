@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """Static check of the hand-placed GEMM kernels' ISA for a hazard hipcc cannot see.
 
-The main loops of csrc/gemm256w4.hip are `asm volatile` statements; hipcc allocates registers around them and, when a kernel
+The main loops of csrc/gemm256w4.hip and csrc/gemm256w4_split.hip are `asm volatile` statements; hipcc allocates registers around them and, when a kernel
 runs out of SGPRs, spills scalars into VGPR lanes and reloads them with v_readlane_b32 wherever they are needed next — also
 directly in front of an inline-asm `global_load_lds_dwordx4 v, s[a:b]` that uses the reloaded pair as its scalar base.  gfx9
 needs 5 wait states between a VALU write of an SGPR and a VMEM instruction that reads it; the compiler pads that for its own
 instructions, not for the text inside an asm statement.  (r04: the first build of the split-f16 kernel faulted at multi-tile
 launches for exactly this reason.)
 
-    python tools/check_asm_hazards.py esmdiff_amd/csrc/gemm256w4.hip [more .hip files]
+    python tools/check_asm_hazards.py [esmdiff_amd/csrc/gemm256w4.hip esmdiff_amd/csrc/gemm256w4_split.hip | other .hip / .s files]
 
 compiles each file to gfx950 assembly (device only) and reports, per kernel: SGPR / VGPR spill counts from the code-object
 metadata, and every inline-asm VMEM instruction whose scalar operands were written by a VALU instruction (v_readlane_b32,
@@ -120,7 +120,7 @@ def compile_to_asm(src: Path) -> str:
 
 def main(argv):
     bad = 0
-    for f in argv or ["esmdiff_amd/csrc/gemm256w4.hip"]:
+    for f in argv or ["esmdiff_amd/csrc/gemm256w4.hip", "esmdiff_amd/csrc/gemm256w4_split.hip"]:
         p = Path(f)
         text = p.read_text() if p.suffix == ".s" else compile_to_asm(p)
         for k, mm, hz in analyse(text):
