@@ -108,11 +108,9 @@ def lib():
     L.esmdiff_gibbs_sample.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, ctypes.POINTER(i32), ctypes.POINTER(Rng), vp]
     L.esmdiff_gemm_bf16.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]
     L.esmdiff_gemm_f16.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]
-    if hasattr(L, "esmdiff_gemm_bf16_timed"):      # -DED_DEBUG builds only (scratch/ A-B scripts)
+    if hasattr(L, "esmdiff_gemm_bf16_timed"):      # -DED_DEBUG builds only (scratch/bench_gemm.py)
         L.esmdiff_gemm_bf16_timed.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, c_f32p, vp]
         L.esmdiff_gemm_bf16_timed.restype = ctypes.c_int
-        L.esmdiff_debug_graph_ab.argtypes = [vp, vp, vp, i32, i32, i32, c_f32p, c_f32p]
-        L.esmdiff_debug_graph_ab.restype = ctypes.c_int
     L.esmdiff_branch_linear_layernorm.argtypes = [vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, ctypes.POINTER(i32), vp]
     L.esmdiff_layernorm_bf16.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.esmdiff_attention_bf16.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
@@ -163,7 +161,7 @@ def lib():
 
 
 def build_info() -> str:
-    """esmdiff_get_build_info: ABI, arch, whether this is a -DED_DEBUG build (the only kind that reads ESMDIFF_* tuning switches)."""
+    """esmdiff_get_build_info: ABI, arch, whether this is a -DED_DEBUG build (the kind that exports esmdiff_gemm_bf16_timed)."""
     buf = ctypes.create_string_buffer(1024)
     lib().esmdiff_get_build_info(buf, 1024)
     return buf.value.decode()

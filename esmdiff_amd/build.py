@@ -84,7 +84,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     OBJDIR.mkdir(exist_ok=True)
     stamp = OBJDIR / "flags.txt"
     flags = " ".join(COMMON) + " | " + " ".join(f"{n}: {' '.join(f)}" for n, f in UNITS.items() if f)
-    if not stamp.exists() or stamp.read_text() != flags:   # different flags (e.g. -DED_GEMM_DEBUG, a unit's own flags): rebuild all
+    if not stamp.exists() or stamp.read_text() != flags:   # different flags (e.g. -DED_DEBUG, a unit's own flags): rebuild all
         force = True
     if LIB.exists() and not force and LIB.stat().st_mtime >= _newest_src():
         return LIB

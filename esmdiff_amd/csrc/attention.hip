@@ -6,8 +6,7 @@
 // in tiles of 64 through LDS with an online softmax, so L = 1026 (BASELINE config 4; K/V per head =
 // 263 KB > 160 KB LDS) needs no special casing — only the number of tiles changes.
 //
-// Workgroup = W waves (1..10; default min(4, ceil(L/32)), ESMDIFF_ATTN_WAVES overrides) = 32 W queries of one (batch,
-// head); every wave owns 32 queries and all of them share the staged K/V tiles.  Measured at L_tok = 258 (9 query waves,
+// Workgroup = W = min(4, ceil(L/32)) waves = 32 W queries of one (batch, head); every wave owns 32 queries and all of them share the staged K/V tiles.  Measured at L_tok = 258 (9 query waves,
 // which W = 4 cuts into 4 + 4 + 1, the third workgroup staging five K/V tiles for two queries) in ms of attention per
 // forward, one box: W = 4 / 3 waves per SIMD (the r01 kernel) 5.33, W = 3 (no idle wave) 5.30-5.32, W = 5 6.46, W = 9
 // (one workgroup per head, each K/V tile staged once) 6.20, W = 4 / 4 waves per SIMD 5.11 (kept); L_tok = 1026: 14.3 /
@@ -63,8 +62,8 @@ __device__ __forceinline__ bf16x4 lds_read_tr16(const char* p) {  // ds_read_b64
   return r;
 }
 
-// Two register budgets of the same body: 3 waves per SIMD (137 VGPRs, no spill) and 4 waves per SIMD (128 VGPRs, a
-// handful of spilled address registers outside the tile loop); the launcher picks (ESMDIFF_ATTN_OCC overrides).
+// Register budget: 4 waves per SIMD (128 VGPRs, a handful of spilled address registers outside the tile loop).  The 3-waves-
+// per-SIMD build of the same body (137 VGPRs, no spill) measured slower (header) and left with the A/B switches.
 // Ablation builds (-DED_ATTN_ABL=<bits>, wrong results by construction): 1 no v_exp_f32, 2 K/V staged once (tile 0 is
 // reused: no LDS-DMA in the loop), 4 no vmcnt wait / barrier per tile, 8 no P·V MFMAs.
 #ifndef ED_ATTN_ABL
@@ -76,75 +75,30 @@ extern "C" int esmdiff_debug_attn_trace(unsigned long long* out_host) {   // deb
   return (int)hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_attn_trace), sizeof(g_attn_trace));
 }
 #endif
-// Ragged batches (esmdiff_set_lengths): a separate instantiation per budget with a per-sample key length `lens` [B] (device
-// memory); the plain kernels are compiled from the same text with ED_ATTN_RAGGED = 0 and do not change.
-#define ED_ATTN_RAGGED 0
-#define ED_ATTN_NAME attention_kernel_occ3
-#define ED_ATTN_WPE 3
-#include "attention_kernel.inc"
-#undef ED_ATTN_NAME
-#undef ED_ATTN_WPE
-#define ED_ATTN_NAME attention_kernel_occ4
+// Ragged batches (esmdiff_set_lengths): a separate instantiation with a per-sample key length `lens` [B] (device memory); the
+// plain kernel is compiled from the same text with ED_ATTN_RAGGED = 0 and does not change.
 #define ED_ATTN_WPE 4
+#define ED_ATTN_RAGGED 0
+#define ED_ATTN_NAME attention_kernel_occ4
 #include "attention_kernel.inc"
 #undef ED_ATTN_NAME
-#undef ED_ATTN_WPE
 #undef ED_ATTN_RAGGED
 #define ED_ATTN_RAGGED 1
-#define ED_ATTN_NAME attention_kernel_ragged_occ3
-#define ED_ATTN_WPE 3
-#include "attention_kernel.inc"
-#undef ED_ATTN_NAME
-#undef ED_ATTN_WPE
 #define ED_ATTN_NAME attention_kernel_ragged_occ4
-#define ED_ATTN_WPE 4
 #include "attention_kernel.inc"
 #undef ED_ATTN_NAME
-#undef ED_ATTN_WPE
 #undef ED_ATTN_RAGGED
-
-// (ESMDIFF_ATTN_WAVES=-1 only: the occupancy model that was tried and measured slower, see the header)
-// Workgroup width for L tokens: nw = ceil(L/32) query waves per (batch, head) are cut into nWG workgroups of W waves.  A CU
-// holds k = min(4 occ / W, LDS / 32 KiB) of them (occ = waves per SIMD of the build), of which nw / (nWG W) of the waves
-// are working: pick the W that keeps the most working waves resident (ties: the widest, it stages each K/V tile fewer
-// times).  occ 4: L = 258 -> 3 (3 workgroups of 3, 15 working waves per CU; the old fixed 4 at occ 3 gave 9),
-// L = 1026 -> 3 (11 workgroups, 15), L = 60 -> 2.
-static int attention_waves(int L, int occ) {
-  const int nw = (L + 31) / 32, max_wg = L <= KV_TILE ? 10 : 5;  // LDS: 16 / 32 KiB per workgroup of 160
-  int best_w = 1, best_score = -1;
-  for (int W = 1; W <= 10; ++W) {
-    if (W > nw && W > 1) break;
-    const int nwg = (nw + W - 1) / W;
-    const int k = std::min(4 * occ / W, max_wg);
-    const int score = k * nw * 1000 / nwg;  // working waves per CU x 1000
-    if (score >= best_score) {
-      best_score = score;
-      best_w = W;
-    }
-  }
-  return best_w;
-}
+#undef ED_ATTN_WPE
 
 hipError_t launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* qkv, bf16_t* ctx, int B, int L,
                             int H, hipStream_t stream, const int32_t* lens) {
   if (B <= 0 || L <= 0) return hipSuccess;
-  static const int forced = [] {
-    const char* e = ed_dbg_env("ESMDIFF_ATTN_WAVES");
-    return e ? atoi(e) : 0;
-  }();
-  static const int occ = [] {
-    const char* e = ed_dbg_env("ESMDIFF_ATTN_OCC");
-    return e && atoi(e) == 3 ? 3 : 4;
-  }();
-  const int W = forced > 0 ? std::min(forced, 10) : (forced < 0 ? attention_waves(L, occ) : std::min(4, (L + 31) / 32));
-  const int nw = (L + 31) / 32;
+  const int nw = (L + 31) / 32, W = std::min(4, nw);
   const int nqb = (nw + W - 1) / W, BH = B * H;
   dim3 grid(8 * nqb * ((BH + 7) / 8)), block(64 * W);
   const size_t lds = (L <= KV_TILE ? 1 : 2) * 2 * KV_BYTES;
   // (the workgroup width W depends on L only; a query's arithmetic does not depend on W, so a ragged row equals its solo launch)
-  if (lens && occ == 3) hipLaunchKernelGGL(attention_kernel_ragged_occ3, grid, block, lds, stream, q, k, qkv, ctx, L, H, BH, nqb, lens);
-  else if (lens) hipLaunchKernelGGL(attention_kernel_ragged_occ4, grid, block, lds, stream, q, k, qkv, ctx, L, H, BH, nqb, lens);
-  else if (occ == 3) hipLaunchKernelGGL(attention_kernel_occ3, grid, block, lds, stream, q, k, qkv, ctx, L, H, BH, nqb);
+  if (lens) hipLaunchKernelGGL(attention_kernel_ragged_occ4, grid, block, lds, stream, q, k, qkv, ctx, L, H, BH, nqb, lens);
   else hipLaunchKernelGGL(attention_kernel_occ4, grid, block, lds, stream, q, k, qkv, ctx, L, H, BH, nqb);
   return hipGetLastError();
 }

@@ -50,8 +50,6 @@ struct Layer {
   SplitW s_qkv, s_out, s_up, s_down;
   // ... and the power-of-two operand scales of the split attention (attention_split.hip), from rigorous bounds at create
   float att_qk = 1.f, att_v = 1.f;
-  // ... and of the FFN mid row written by the fused SwiGLU epilogue of the split FFN-up (0: unfused, per-row scales)
-  bool up_fused = false;   // F32_SPLIT: FFN-up weight rows interleaved gate / up, SwiGLU in the GEMM's epilogue
 };
 
 }  // namespace
@@ -116,16 +114,11 @@ struct esmdiff_engine {
   // F32_SPLIT, opt-in (esmdiff_set_small_batch_splitk): at <= splitk_max_rows rows the two residual linears (6 column tiles each)
   // run K-sliced (out-proj 3 slices, FFN-down 4) so that a small batch uses more than a few dozen CUs; partial planes in sk_parts
   bool splitk_small = false;
-  int splitk_max_rows = 4096;
   float* sk_parts = nullptr;
-  int64_t strict_dual_min_tokens = 8192;   // F32_SPLIT: two sub-batch streams from this many tokens (ESMDIFF_STRICT_DUAL_MIN_TOKENS)
-  int64_t dual_min_tokens = 2200, dual_small_max_tokens = 1024;  // two streams from / small window up to (tokens), see forward()
+  int64_t dual_min_tokens = 2200;  // esmdiff_set_option(ESMDIFF_OPT_DUAL_MIN_TOKENS): two streams from this many tokens, see forward()
   int n_streams = 2;         // esmdiff_set_option(ESMDIFF_OPT_STREAMS): sub-batch launch queues of the 16-bit forward
-  int stream_offset_us = 0;  // phase offset of the second sub-batch stream (ESMDIFF_STREAM_OFFSET_US), see forward()
-  int debug_skip = 0;  // -DED_DEBUG builds only: ESMDIFF_DEBUG_SKIP bits (timing experiments, results are wrong): 1 rope, 2 attention, 4 / 8 the two add+LN; always 0 otherwise
   ed::GemmWorkspace gemm_ws[4] = {};  // split-K partials of the small-M GEMM path, one per launch queue
   ed::GemmWorkspace gemm_ws2[4] = {}; // ... a second set: the out-projection's K slices stay live next to the FFN-down's
-  int small_fused = 1;                // ESMDIFF_SMALL_FUSED=0: branch linears write bf16 deltas at every size (A/B runs)
   // precision = ESMDIFF_PRECISION_F32: float32 weights / activations (forward_strict); the bf16 members above stay null
   bool strict = false;
   // precision = ESMDIFF_PRECISION_F32_SPLIT: forward_strict with every large linear as three f16 MFMA passes over split
@@ -140,7 +133,7 @@ struct esmdiff_engine {
   float *fhead_w0 = nullptr, *fhead_w3 = nullptr, *fpl_w0 = nullptr, *fpl_w3 = nullptr, *fpw_down = nullptr;
   float *fg_proj = nullptr, *fg_out = nullptr, *fgp = nullptr, *fgctx = nullptr;
   float *fpw_l1 = nullptr, *fpw_l2 = nullptr, *fpair_x = nullptr, *fpair_h = nullptr;   // pairwise head in float32
-  float *fh = nullptr, *fh2 = nullptr, *fqkv = nullptr, *fq = nullptr, *fk = nullptr, *fctx = nullptr, *fgu = nullptr,
+  float *fh = nullptr, *fh2 = nullptr, *fqkv = nullptr, *fq = nullptr, *fk = nullptr, *fctx = nullptr, *fgu = nullptr,   // (fgu: F32 engines only)
         *fmid = nullptr, *fpair_qk = nullptr;
   // step-0 sharing (esmdiff_set_step0_sharing): when every sample of a sampling call starts from identical inputs, the first
   // forward runs on a sub-batch and all samples draw from its logits; counters of the work really executed
@@ -279,6 +272,14 @@ struct Prof {
   }
 };
 
+// One launch as a timed section: needs `e` and a Prof `p` in scope.
+#define RUN(section, call)   \
+  do {                       \
+    p.mark(section);         \
+    HIP_TRY(e, (call));      \
+    p.mark(section);         \
+  } while (0)
+
 void prof_collect(esmdiff_engine* e) {
   if (!e->profiling || e->ev_used < 2) {
     e->ev_used = 0;
@@ -381,17 +382,20 @@ Part make_part(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, float
 // reduced until they stay on the default path's side (tests/test_gpu_fullwidth.py::test_stream_options_never_change_a_bit).
 constexpr int kDefaultStreams = 2;
 constexpr int64_t kDefaultDualMinTokens = 2200;
+constexpr int64_t kDualSmallMaxTokens = 1024;      // the all-small two-queue window reaches up to this many tokens, see forward()
+constexpr int64_t kStrictDualMinTokens = 8192;     // F32_SPLIT: two sub-batch streams from this many tokens
+constexpr int kSplitkMaxRows = 4096;               // esmdiff_set_small_batch_splitk: K-sliced residual linears up to this many rows
 int parts_for(const esmdiff_engine* e, int B, int L, int n_streams, int64_t dual_min_tokens) {
   const int64_t tokens = (int64_t)B * L;
   if (!e->side.empty() && e->profiling != 1 && B >= 2 &&
-      (tokens >= dual_min_tokens || (B >= 8 && tokens <= e->dual_small_max_tokens && tokens >= std::min<int64_t>(768, dual_min_tokens))))
+      (tokens >= dual_min_tokens || (B >= 8 && tokens <= kDualSmallMaxTokens && tokens >= std::min<int64_t>(768, dual_min_tokens))))
     return std::min<int>({(int)e->side.size() + 1, n_streams, B, 4});
   return 1;
 }
 bool parts_small(const esmdiff_engine* e, int B, int L, int np) {
   if (e->strict) return false;
   const int b_first = (int)((int64_t)B * 1 / np), b_last = B - (int)((int64_t)B * (np - 1) / np);
-  return e->small_fused && e->gemm_ws[0].partial && e->gemm_ws2[0].partial && (int64_t)b_last * L < ed::small_max_rows() &&
+  return e->gemm_ws[0].partial && e->gemm_ws2[0].partial && (int64_t)b_last * L < ed::small_max_rows() &&
          (int64_t)b_first * L < ed::small_max_rows();
 }
 struct BatchPlan {
@@ -399,10 +403,6 @@ struct BatchPlan {
   bool small;   // the sub-batches take the small-batch path
 };
 BatchPlan plan_batch(const esmdiff_engine* e, int B, int L) {
-#ifdef ED_DEBUG   // (A/B builds move the thresholds themselves: the plan is then whatever the switches say)
-  const int np_dbg = parts_for(e, B, L, e->n_streams, e->dual_min_tokens);
-  return BatchPlan{np_dbg, parts_small(e, B, L, np_dbg)};
-#endif
   const int np_def = parts_for(e, B, L, kDefaultStreams, kDefaultDualMinTokens);
   const bool small = parts_small(e, B, L, np_def);
   int np = parts_for(e, B, L, e->n_streams, e->dual_min_tokens);
@@ -428,8 +428,8 @@ int shared_forward_batch(const esmdiff_engine* e, int B, int L) {
 // bf16 path's.  Block 0's geometric branch runs between the attention and the FFN branch while frames are set.
 struct SPart {   // one sub-batch of a strict forward: the engine's float32 workspace at a row offset, on its own stream
   const int64_t *seq, *xtok;
-  float *x, *fh, *fh2, *fqkv, *fq, *fk, *fctx, *fgu, *fmid, *fgp, *fgctx, *fpair_qk, *logits, *pl_logits;
-  uint16_t *a2, *a2b;   // split rows feeding the next linear; a2b: the FFN mid rows written by the fused SwiGLU epilogue
+  float *x, *fh, *fh2, *fqkv, *fq, *fk, *fctx, *fgu, *fmid, *fgp, *fgctx, *fpair_qk, *logits, *pl_logits;   // fgu: F32 engines only
+  uint16_t* a2;   // split rows feeding the next linear
   float* rs;
   const float *f_rot, *f_trans;
   const uint8_t* f_mask;
@@ -441,19 +441,13 @@ struct SPart {   // one sub-batch of a strict forward: the engine's float32 work
 // sub-batch streams of a float32-grade forward (one function for forward_strict and esmdiff_describe_plan).  (r06: with frames set
 // the two-queue forward was not deterministic while geom_attention_kernel held packed float ops beside the other queue's GEMM: geom.hip.)
 static int strict_parts(const esmdiff_engine* e, int B, int L) {
-  return (e->split && !e->side.empty() && e->profiling != 1 && B >= 2 && (int64_t)B * L >= e->strict_dual_min_tokens) ? 2 : 1;
+  return (e->split && !e->side.empty() && e->profiling != 1 && B >= 2 && (int64_t)B * L >= kStrictDualMinTokens) ? 2 : 1;
 }
 
 static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int ld, int L) {
   const esmdiff_config& c = e->cfg;
   const int D = c.d_model, H = c.n_heads, FH = c.ffn_hidden;
   const bool geom = e->has_geom && e->frames_B > 0;
-#define RUN(section, call)   \
-  do {                       \
-    p.mark(section);         \
-    HIP_TRY(e, (call));      \
-    p.mark(section);         \
-  } while (0)
   const int VH = e->v_heads;
   // precision = F32_SPLIT: the same op sequence; every LayerNorm / SwiGLU / attention output that feeds a linear is written
   // as a split row (a2, rs) and the linear runs as three f16 MFMA passes (gemm_split.hip); everything else is unchanged
@@ -467,7 +461,7 @@ static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int
   // K-sliced residual linears: only where the slicing constraints hold for this model (3 D / 3 and 3 FH / 4 multiples of 128)
   // this part's slice planes: the parts of a two-stream forward use disjoint regions (4 planes of its padded rows each)
   float* const skp = e->sk_parts ? e->sk_parts + (size_t)4 * D * ((size_t)round_up((int)((w.x - e->x) / D), 256) + (w.x != e->x ? 256 : 0)) : nullptr;
-  const bool sk = sp && e->splitk_small && e->sk_parts && M <= e->splitk_max_rows && e->kind == 0 && D % 128 == 0 && (3 * FH) % 512 == 0 &&
+  const bool sk = sp && e->splitk_small && e->sk_parts && M <= kSplitkMaxRows && e->kind == 0 && D % 128 == 0 && (3 * FH) % 512 == 0 &&
                   D >= 384 && 3 * FH / 4 >= 384;
   if (e->kind == 1) RUN(S_EMBED, launch_gather_rows(w.xtok, e->e_struct, w.x, M, D, ESMDIFF_VOCAB, st));
   else RUN(S_EMBED, launch_embed(w.seq, w.xtok, e->e_seq, e->e_struct, e->cvec, cond, w.x, B, L, D, st, e->sigma_rows > 1 ? D : 0));
@@ -509,7 +503,7 @@ static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int
     }
     if (sp) RUN(S_LN, launch_layernorm_split(w.x, ly.ln2_w, ly.ln2_b, a2, rs, nullptr, M, D, 0, st));
     else RUN(S_LN, launch_layernorm_f32(w.x, ly.ln2_w, ly.ln2_b, w.fh, M, D, st));
-    if (sp && ly.up_fused) {
+    if (sp) {
       // split FFN-up with the SwiGLU in its epilogue: reads the LayerNorm's split row (a2: [M, 3 D]), writes mid as f32 [M, FH];
       // split_rows then makes the FFN-down operand with every row's own power-of-two scale (r05: not a per-layer bound, see
       // gemm256w4.hip) — [M, 2 FH] of gate / up values never exist in memory
@@ -522,11 +516,10 @@ static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int
         RUN(S_FFN_DOWN, launch_gemm256w4_split(a2, rs, ly.s_down.w, ly.s_down.inv, w.x, nullptr, M, D, FH, D,
                                                c.residue_scale, ESMDIFF_F32EPI_RESID_DIV, st));
       }
-    } else {
-      LIN(S_FFN_UP, ly.s_up, ly.fw_up, w.fh, D, D, w.fgu, nullptr, 2 * FH, 2 * FH, 2 * FH, 1.f, ESMDIFF_F32EPI_STORE);
-      if (sp) RUN(S_FFN_UP, launch_swiglu_split(w.fgu, a2, rs, M, FH, st));
-      else RUN(S_FFN_UP, launch_swiglu_f32(w.fgu, w.fmid, M, FH, st));
-      LIN(S_FFN_DOWN, ly.s_down, ly.fw_down, w.fmid, FH, FH, w.x, nullptr, D, D, D, c.residue_scale, ESMDIFF_F32EPI_RESID_DIV);
+    } else {   // f32 engine: gate / up rows [M, 2 FH] in memory, SwiGLU as its own pass
+      RUN(S_FFN_UP, launch_gemm_f32(w.fh, D, ly.fw_up, w.fgu, nullptr, M, 2 * FH, D, 2 * FH, 2 * FH, 1.f, ESMDIFF_F32EPI_STORE, st));
+      RUN(S_FFN_UP, launch_swiglu_f32(w.fgu, w.fmid, M, FH, st));
+      RUN(S_FFN_DOWN, launch_gemm_f32(w.fmid, FH, ly.fw_down, w.x, nullptr, M, D, FH, D, D, c.residue_scale, ESMDIFF_F32EPI_RESID_DIV, st));
     }
   }
   if (sp) {
@@ -555,21 +548,14 @@ static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int
   if (e->has_plddt) RUN(S_LN, launch_layernorm_f32(w.fctx, e->pl_ln_w, e->pl_ln_b, w.fq, M, D, st));
   RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->fhead_w3, logits, e->head_b3, M, c.vocab_out, D, ld, c.vocab_out, 1.f, ESMDIFF_F32EPI_STORE, st));
   if (e->has_plddt) RUN(S_HEAD, launch_gemm_f32(w.fq, D, e->fpl_w3, w.pl_logits, e->pl_b3, M, e->plddt_bins, D, e->ld_plddt, e->plddt_bins, 1.f, ESMDIFF_F32EPI_STORE, st));
-#undef RUN
   return 0;
 }
 
 int forward_strict(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, const float* t_freq_dev, float* logits,
                    int ld, int B, int L, hipStream_t st) {
   const esmdiff_config& c = e->cfg;
-  const int D = c.d_model, H = c.n_heads, FH = c.ffn_hidden, M = B * L;
+  const int D = c.d_model, FH = c.ffn_hidden;
   Prof p{e, st};
-#define RUN(section, call)   \
-  do {                       \
-    p.mark(section);         \
-    HIP_TRY(e, (call));      \
-    p.mark(section);         \
-  } while (0)
   const float* cond = nullptr;
   if (t_freq_dev && e->sig_w1) {
     RUN(S_EMBED, launch_sigma_mlp(t_freq_dev, e->sig_w1, e->sig_b1, e->sig_w2, e->sig_b2, e->sig_hidden, e->cond, c.freq_dim, D, st,
@@ -592,7 +578,7 @@ int forward_strict(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, c
     parts[pi] = SPart{seq + t0, xtok + t0, off(e->x, D), off(e->fh, D), off(e->fh2, D), off(e->fqkv, 3 * D), off(e->fq, D), off(e->fk, D),
                       off(e->fctx, D), off(e->fgu, 2 * FH), off(e->fmid, FH), off(e->fgp, 15 * e->v_heads), off(e->fgctx, 3 * e->v_heads),
                       off(e->fpair_qk, 128), logits + t0 * ld, off(e->pl_logits, e->ld_plddt), e->a2 ? e->a2 + t0 * WS : nullptr,
-                      reinterpret_cast<uint16_t*>(e->fgu) + t0 * 3 * FH, e->rs ? e->rs + t0 : nullptr, e->f_rot ? e->f_rot + t0 * 9 : nullptr, e->f_trans ? e->f_trans + t0 * 3 : nullptr,
+                      e->rs ? e->rs + t0 : nullptr, e->f_rot ? e->f_rot + t0 * 9 : nullptr, e->f_trans ? e->f_trans + t0 * 3 : nullptr,
                       e->f_mask ? e->f_mask + t0 : nullptr, e->cur_lens ? e->cur_lens + b0 : nullptr, b1 - b0, pi == 0 ? st : e->side[pi - 1]};
   }
   if (np > 1) {
@@ -607,7 +593,6 @@ int forward_strict(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, c
     HIP_TRY(e, hipEventRecord(e->ev_join[0], e->side[0]));
     HIP_TRY(e, hipStreamWaitEvent(st, e->ev_join[0], 0));
   }
-#undef RUN
   return 0;
 }
 
@@ -744,7 +729,7 @@ int esmdiff_get_build_info(char* buf, int32_t cap) {
                          "libesmdiff_hip abi=%d arch=gfx950 debug_env=%d (%s) operand_builds=bf16,f16 fp_contract_off=sampler,gibbs,metrics "
                          "compiler=%s",
                          ESMDIFF_ABI_VERSION, dbg,
-                         dbg ? "-DED_DEBUG: ESMDIFF_* tuning switches are read from the environment" : "product build: no ESMDIFF_* tuning switch is read",
+                         dbg ? "-DED_DEBUG: esmdiff_gemm_bf16_timed is exported; no ESMDIFF_* tuning switch is read" : "product build: no ESMDIFF_* tuning switch is read",
                          __VERSION__);
   if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", tmp);
   return n;
@@ -765,7 +750,7 @@ int esmdiff_describe_plan(const esmdiff_engine* e, int32_t B, int32_t L, char* b
     const int64_t tokens = (int64_t)B * L;
     const int np = strict_parts(e, B, L);
     n += snprintf(at(), room(), " streams=%d path=%s k_sliced_small_batches=%d", np,
-                  e->split ? "split(3 f16 MFMA passes, 256x256w4)" : "strict(f32 MFMA)", e->sk_parts && tokens <= e->splitk_max_rows ? 1 : 0);
+                  e->split ? "split(3 f16 MFMA passes, 256x256w4)" : "strict(f32 MFMA)", e->sk_parts && tokens <= kSplitkMaxRows ? 1 : 0);
   } else {
     const int np = plan_parts(e, B, L);
     const bool small = plan_small(e, B, L);
@@ -807,10 +792,9 @@ int esmdiff_set_final_skip(esmdiff_engine* e, int32_t on) {
 int esmdiff_set_small_batch_splitk(esmdiff_engine* e, int32_t on) {
   if (!e) return ESMDIFF_E_INVALID;
   if (on && !e->split) return fail(e, ESMDIFF_E_INVALID, "K-sliced small batches exist for the F32_SPLIT precision only");
-  if (const char* mr = ed_dbg_env("ESMDIFF_SPLITK_MAX_ROWS")) e->splitk_max_rows = atoi(mr);   // (experiments: K-sliced at every size)
   if (on && !e->sk_parts) {
     HIP_TRY(e, hipSetDevice(e->device));
-    const int64_t rows = std::min<int64_t>(e->splitk_max_rows, (int64_t)e->cfg.max_batch * e->cfg.max_len);
+    const int64_t rows = std::min<int64_t>(kSplitkMaxRows, (int64_t)e->cfg.max_batch * e->cfg.max_len);
     // two parts of a two-stream forward may both qualify (e.g. 2 x 4096 rows): room for two padded parts + the part offset
     const size_t n = (size_t)4 * (size_t)(2 * ((rows + 255) / 256 * 256) + 512) * e->cfg.d_model;
     if (int r = dalloc(e, &e->sk_parts, n)) return r;
@@ -945,10 +929,8 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     if (split) {
       // FFN-up with the SwiGLU fused into the split GEMM's epilogue (rows interleaved gate / up; mid leaves it as f32 and is split
       // with its row's own scale, forward_strict)
-      const bool fuse = FH % 32 == 0 && !ed_dbg_env("ESMDIFF_SPLIT_UNFUSED_SWIGLU");
-      TRY(load_split(e, t, b + "ffn.1.weight", {2 * FH, D}, &ly.s_up, 0, fuse ? FH : 0));
+      TRY(load_split(e, t, b + "ffn.1.weight", {2 * FH, D}, &ly.s_up, 0, FH));
       TRY(load_split(e, t, b + "ffn.3.weight", {D, FH}, &ly.s_down));
-      ly.up_fused = fuse;
     } else if (strict) {
       TRY(load_f32(e, t, b + "ffn.1.weight", {2 * FH, D}, &ly.fw_up));
       TRY(load_f32(e, t, b + "ffn.3.weight", {D, FH}, &ly.fw_down));
@@ -1126,7 +1108,7 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
       TRY(dalloc(e, &e->fq, Mx * D));
       TRY(dalloc(e, &e->fk, Mx * D));
       TRY(dalloc(e, &e->fctx, Mx * D));
-      TRY(dalloc(e, &e->fgu, Mx * 2 * FH));
+      if (!split) TRY(dalloc(e, &e->fgu, Mx * 2 * FH));   // gate / up rows: the split FFN-up's SwiGLU epilogue never writes them out
       TRY(dalloc(e, &e->fmid, Mx * FH));
       if (e->has_pair) TRY(dalloc(e, &e->fpair_qk, Mx * 128));
       if (split) {
@@ -1186,8 +1168,7 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     TRY(dalloc(e, &e->g_rowgap, Mx));
     TRY(dalloc(e, &e->g_nunmask, (size_t)e->tfreq_rows * cfg->max_batch));
     {  // split-K workspaces: S * N <= 12288 for every shape the launcher splits; rows up to the small-batch switch
-      const char* sk = ed_dbg_env("ESMDIFF_GEMM_SPLITK");
-      if (!(sk && sk[0] == '0') && !strict) {
+      if (!strict) {
         const size_t rows = (size_t)round_up((int)std::min<size_t>(Mx, ed::small_max_rows()), 128);
         for (int q = 0; q < 4; ++q) {
           e->gemm_ws[q].partial_floats = rows * 12288;
@@ -1199,36 +1180,14 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     }
   }
 #undef TRY
-  // second launch queue for the two-stream forward (ESMDIFF_DUAL_STREAM=0 disables, ESMDIFF_DUAL_STREAM_MIN_TOKENS tunes)
-  {
-    int n_streams = 2;  // (-DED_DEBUG: ESMDIFF_DUAL_STREAM = 0/1: one stream; 2 (default) .. 4: that many sub-batches)
-    if (const char* ds = ed_dbg_env("ESMDIFF_DUAL_STREAM")) n_streams = std::max(1, std::min(4, atoi(ds)));
-    e->n_streams = n_streams;
-    if (hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess)
-      return bail(fail(e, ESMDIFF_E_HIP, "engine create: fork event: %s", hipGetErrorString(hipGetLastError())));
-    for (int i = 1; i < n_streams; ++i) {
-      hipStream_t sd = nullptr;
-      hipEvent_t ev = nullptr;
-      if (hipStreamCreateWithFlags(&sd, hipStreamNonBlocking) != hipSuccess ||
-          hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-        return bail(fail(e, ESMDIFF_E_HIP, "engine create: side stream: %s", hipGetErrorString(hipGetLastError())));
-      e->side.push_back(sd);
-      e->ev_join.push_back(ev);
-    }
-#ifdef ED_DEBUG
-    if (const char* ds = ed_dbg_env("ESMDIFF_DEBUG_SKIP")) e->debug_skip = atoi(ds);
-#else
-    // the launch-skipping switch of the timing experiments (results are wrong by construction) exists in -DED_DEBUG builds only;
-    // a product library that finds it in the environment refuses to start rather than silently ignore a request it once honoured
-    if (getenv("ESMDIFF_DEBUG_SKIP"))
-      return bail(fail(e, ESMDIFF_E_INVALID, "ESMDIFF_DEBUG_SKIP is set, but this libesmdiff_hip.so was built without -DED_DEBUG: unset it"));
-#endif
-    if (const char* so = ed_dbg_env("ESMDIFF_STREAM_OFFSET_US")) e->stream_offset_us = atoi(so);
-    if (const char* sf = ed_dbg_env("ESMDIFF_SMALL_FUSED")) e->small_fused = atoi(sf);
-    if (const char* mt = ed_dbg_env("ESMDIFF_DUAL_STREAM_MIN_TOKENS")) e->dual_min_tokens = atoll(mt);
-    if (const char* mt = ed_dbg_env("ESMDIFF_STRICT_DUAL_MIN_TOKENS")) e->strict_dual_min_tokens = atoll(mt);
-    if (const char* mt = ed_dbg_env("ESMDIFF_DUAL_STREAM_SMALL_MAX_TOKENS")) e->dual_small_max_tokens = atoll(mt);
-  }
+  // second launch queue for the two-stream forward (esmdiff_set_option(ESMDIFF_OPT_STREAMS) adds more)
+  if (hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess)
+    return bail(fail(e, ESMDIFF_E_HIP, "engine create: fork event: %s", hipGetErrorString(hipGetLastError())));
+  if (int r = add_side_stream(e)) return bail(r);
+  // the launch-skipping switch of the retired timing experiments gave wrong results by construction; a library that finds it in
+  // the environment refuses to start rather than silently ignore a request it once honoured
+  if (getenv("ESMDIFF_DEBUG_SKIP"))
+    return bail(fail(e, ESMDIFF_E_INVALID, "ESMDIFF_DEBUG_SKIP is set, but no build of libesmdiff_hip.so honours it any more: unset it"));
   if (hipDeviceSynchronize() != hipSuccess) return bail(fail(e, ESMDIFF_E_HIP, "engine create: %s", hipGetErrorString(hipGetLastError())));
   *out = e;
   return 0;
@@ -1561,57 +1520,6 @@ int esmdiff_gibbs_sample(esmdiff_engine* e, const int64_t* seq, int64_t* x_inout
   return 0;
 }
 
-#ifdef ED_DEBUG
-// Measurement aid: the same forward `n` times as plain launches and as `n` replays of ONE captured hipGraph of it, on an
-// engine-owned stream; milliseconds per forward of each into ms_direct / ms_graph [host].
-int esmdiff_debug_graph_ab(esmdiff_engine* e, const int64_t* seq, const int64_t* x, int32_t B, int32_t L, int32_t n,
-                           float* ms_direct, float* ms_graph) {
-  if (!e || !seq || !x || !ms_direct || !ms_graph || n <= 0) return ESMDIFF_E_INVALID;
-  if (int r = check_bl(e, B, L)) return r;
-  hipStream_t st;
-  HIP_TRY(e, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  hipEvent_t a, b;
-  hipEventCreate(&a);
-  hipEventCreate(&b);
-  const float* tf = e->cfg.time_conditioning ? e->tfreq : nullptr;
-  const int prof = e->profiling;
-  e->profiling = 0;
-  int r = forward(e, seq, x, tf, e->logits, e->ld_logits, B, L, st);
-  hipEventRecord(a, st);
-  for (int i = 0; i < n && r == 0; ++i) r = forward(e, seq, x, tf, e->logits, e->ld_logits, B, L, st);
-  hipEventRecord(b, st);
-  hipEventSynchronize(b);
-  hipEventElapsedTime(ms_direct, a, b);
-  *ms_direct /= n;
-  hipGraph_t g = nullptr;
-  hipGraphExec_t ge = nullptr;
-  if (r == 0) {
-    HIP_TRY(e, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    r = forward(e, seq, x, tf, e->logits, e->ld_logits, B, L, st);
-    hipError_t ce = hipStreamEndCapture(st, &g);
-    if (r == 0 && ce != hipSuccess) r = fail(e, ESMDIFF_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-  }
-  if (r == 0) HIP_TRY(e, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-  if (r == 0) {
-    hipGraphLaunch(ge, st);
-    hipEventRecord(a, st);
-    for (int i = 0; i < n; ++i) hipGraphLaunch(ge, st);
-    hipEventRecord(b, st);
-    hipEventSynchronize(b);
-    hipEventElapsedTime(ms_graph, a, b);
-    *ms_graph /= n;
-  }
-  if (ge) hipGraphExecDestroy(ge);
-  if (g) hipGraphDestroy(g);
-  hipEventDestroy(a);
-  hipEventDestroy(b);
-  hipStreamDestroy(st);
-  e->profiling = prof;
-  return r;
-}
-
-#endif  // ED_DEBUG
-
 int esmdiff_gemm_bf16(const void* A, const void* W, void* out, const float* bias, int32_t M, int32_t N, int32_t K,
                       int32_t ldc, int32_t n_valid, float alpha, int32_t epilogue, void* stream) {
   if (!A || !W || !out) return ESMDIFF_E_INVALID;
@@ -1676,7 +1584,7 @@ int esmdiff_gemm_bf16_ws(esmdiff_engine* e, const void* A, const void* W, void* 
   return 0;
 }
 
-#ifdef ED_DEBUG
+#ifdef ED_DEBUG   // measurement aid (scratch/bench_gemm.py), not a switch
 int esmdiff_gemm_bf16_timed(const void* A, const void* W, void* out, const float* bias, int32_t M, int32_t N,
                             int32_t K, int32_t ldc, int32_t n_valid, float alpha, int32_t epilogue, int32_t iters,
                             float* ms_out, void* stream) {

@@ -7,12 +7,6 @@ static int ED_FWD_NAME(esmdiff_engine* e, const int64_t* seq, const int64_t* xto
   const int D = c.d_model, H = c.n_heads, FH = c.ffn_hidden;
   const float inv_scale = 1.0f / c.residue_scale;
   Prof p{e, st};
-#define RUN(section, call)   \
-  do {                       \
-    p.mark(section);         \
-    HIP_TRY(e, (call));      \
-    p.mark(section);         \
-  } while (0)
 
   const float* cond = nullptr;
   // sigma_embedder runs whenever its weights were loaded and the caller hands a sinusoid: with time conditioning off the
@@ -35,10 +29,7 @@ static int ED_FWD_NAME(esmdiff_engine* e, const int64_t* seq, const int64_t* xto
   }
   if (np > 1) {
     HIP_TRY(e, hipEventRecord(e->ev_fork, st));
-    for (int pi = 1; pi < np; ++pi) {
-      HIP_TRY(e, hipStreamWaitEvent(e->side[pi - 1], e->ev_fork, 0));
-      HIP_TRY(e, ed::launch_delay_us(e->stream_offset_us * pi, e->side[pi - 1]));
-    }
+    for (int pi = 1; pi < np; ++pi) HIP_TRY(e, hipStreamWaitEvent(e->side[pi - 1], e->ev_fork, 0));
   }
 #define EACH(section, expr)                  \
   do {                                       \
@@ -79,12 +70,12 @@ static int ED_FWD_NAME(esmdiff_engine* e, const int64_t* seq, const int64_t* xto
     if (small) {
       if (pending) EACH(S_LN, KN::launch_add_partials_layernorm_bf16(w.x, PF[pi], D, inv_scale, ly.ln1_w, ly.ln1_b, w.h, M, D, w.st));
       else EACH(S_LN, KN::launch_add_layernorm_bf16(w.x, nullptr, nullptr, 0, ly.ln1_w, ly.ln1_b, w.h, M, D, w.st));
-    } else if (!(e->debug_skip & 4) || i == 0) {
+    } else {
       EACH(S_LN, KN::launch_add_layernorm_bf16(w.x, pending ? w.dlt : nullptr, nullptr, 0, ly.ln1_w, ly.ln1_b, w.h, M, D, w.st));
     }
     EACH(S_QKV, KN::launch_gemm_bf16(w.h, ly.w_qkv, w.qkv, nullptr, M, 3 * D, D, 3 * D, 3 * D, 1.f, ESMDIFF_EPI_BF16, w.st, w.gws));
-    if (!(e->debug_skip & 1) || i == 0) EACH(S_QKROPE, KN::launch_qk_norm_rope(w.qkv, ly.q_ln_w, ly.k_ln_w, e->rope_cos, e->rope_sin, w.q, w.k, w.B, L, H, w.st));
-    if (!(e->debug_skip & 2) || i == 0) EACH(S_ATTN, KN::launch_attention(w.q, w.k, w.qkv, w.ctx, w.B, L, H, w.st, w.lens));
+    EACH(S_QKROPE, KN::launch_qk_norm_rope(w.qkv, ly.q_ln_w, ly.k_ln_w, e->rope_cos, e->rope_sin, w.q, w.k, w.B, L, H, w.st));
+    EACH(S_ATTN, KN::launch_attention(w.q, w.k, w.qkv, w.ctx, w.B, L, H, w.st, w.lens));
     if (small) EACH(S_OUT, KN::launch_gemm_partials(w.ctx, ly.w_out, w.gws2, M, D, D, w.st, &PA[pi]));
     else EACH(S_OUT, KN::launch_gemm_bf16(w.ctx, ly.w_out, w.dlt2, nullptr, M, D, D, D, D, inv_scale, ESMDIFF_EPI_BF16, w.st, w.gws));
     const bool geom_here = i == 0 && geom;
@@ -101,7 +92,7 @@ static int ED_FWD_NAME(esmdiff_engine* e, const int64_t* seq, const int64_t* xto
       EACH(S_LN, KN::launch_add_partials_layernorm_bf16(w.x, PA[pi], D, inv_scale, ly.ln2_w, ly.ln2_b, w.h, M, D, w.st));
     } else if (small) {  // x already holds x + dF + dA; the geometric branch came back as a bf16 delta
       EACH(S_LN, KN::launch_add_layernorm_bf16(w.x, nullptr, w.dlt2, 1, ly.ln2_w, ly.ln2_b, w.h, M, D, w.st));
-    } else if (!(e->debug_skip & 8) || i == 0) {
+    } else {
       EACH(S_LN, KN::launch_add_layernorm_bf16(w.x, pending ? w.dlt : nullptr, w.dlt2, 1, ly.ln2_w, ly.ln2_b, w.h, M, D, w.st));
     }
     EACH(S_FFN_UP, KN::launch_gemm_bf16(w.h, ly.w_up, w.mid, nullptr, M, 2 * FH, D, FH, FH, 1.f, ESMDIFF_EPI_SWIGLU_BF16, w.st, w.gws));
@@ -146,7 +137,6 @@ static int ED_FWD_NAME(esmdiff_engine* e, const int64_t* seq, const int64_t* xto
     HIP_TRY(e, hipStreamWaitEvent(st, e->ev_join[pi - 1], 0));
   }
 #undef EACH
-#undef RUN
   return 0;
 }
 

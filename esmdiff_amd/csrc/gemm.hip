@@ -405,14 +405,7 @@ static hipError_t launch_tiles(const bf16_t* A, const bf16_t* W, void* out, cons
 
 // Tile height of the small-M path: 64-row tiles while the 128-row grid (x K slices) would leave half the CUs without a
 // workgroup.  The K order per output element is the same, so this never changes a result bit.
-// ESMDIFF_GEMM_SMALL_BM=64|128 forces one (A/B runs).
 static int small_tile_mi(int M, int N, int S) {
-  static const int forced = [] {
-    const char* e = ed_dbg_env("ESMDIFF_GEMM_SMALL_BM");
-    return e ? atoi(e) : 0;
-  }();
-  if (forced == 64) return 1;
-  if (forced == 128) return 2;
   return ((M + 127) / 128) * (N / BN) * S <= 128 ? 1 : 2;
 }
 
@@ -427,17 +420,9 @@ struct GemmChoice {
 static GemmChoice choose_gemm(int M, int N, int K, bool has_ws, size_t ws_floats) {
   // Tile selection: the 256x256 kernel once it has >= 128 tiles to hand out, the 128x128 kernel otherwise.  Measured crossovers
   // (us, 128 vs 256): N = 1536, K = 4096: M = 4128 67 / 81, M = 6192 109 / 87; N = 4608: M = 1032 28 / 37, M = 2064 48 / 42;
-  // N = 8192: M = 1032 47 / 40.  ESMDIFF_GEMM_TILE=128|256 forces one (-DED_DEBUG builds: A/B benchmarking).
+  // N = 8192: M = 1032 47 / 40.
   // (Measured and rejected: splitting the rows so that 256-row tiles fill whole 256-CU rounds and the leftover
   // rows go through this kernel — 93 + 29 us apart, 138 us back to back, vs 132 us unsplit at N = K = 1536.)
-  static const int forced = [] {
-    const char* e = ed_dbg_env("ESMDIFF_GEMM_TILE");
-    return e ? atoi(e) : 0;
-  }();
-  static const int min_tiles = [] {
-    const char* e = ed_dbg_env("ESMDIFF_GEMM_256_MIN_TILES");
-    return e ? atoi(e) : 128;
-  }();
   // (r02, inside the two-stream forward: the N = 1536 linears of a 2 817 .. 5 376-row sub-batch — 72 .. 126 tiles — also
   // run better on the persistent 256x256 kernel, which leaves the other CUs to the other stream: B = 24 .. 40 at L_tok = 258
   // +1 .. 3 %; at 7 - 8 row tiles (QKV of a 1 548-row sub-batch, 126 tiles) the 128-column kernel still wins, B = 12 -3 %)
@@ -446,7 +431,7 @@ static GemmChoice choose_gemm(int M, int N, int K, bool has_ws, size_t ws_floats
   // shapes left the product in r05: scratch/gemm256_8wave_kernel.hip.txt of the round-5 tree, git commit 8ee0514.)
   const int t256m = (M + 255) / 256, t256 = t256m * (N / 256);
   if (N % 256 == 0 && K % (2 * BK) == 0 && K >= 6 * BK &&
-      (forced == 256 || (forced == 0 && (t256 >= min_tiles || (t256 >= 72 && t256m >= 12)))))
+      (t256 >= 128 || (t256 >= 72 && t256m >= 12)))
     return GemmChoice{true, 2, 1};
   const int tiles_n = N / BN;
   // split-K factor, a function of (N, K) only: for K >= 2048 (FFN-down) the largest divisor of K/64 that is <= 8 and
@@ -494,14 +479,9 @@ void describe_gemm(int M, int N, int K, size_t ws_floats, char* out, size_t cap)
 // scales and adds them to the residual stream — so no reduce kernel runs and the K = 1536 out-projection can be sliced
 // as well (with a separate reduce pass its slices did not pay, see above).  S is a function of (N, K) only: the
 // largest divisor of K/64 <= 8 that leaves every slice >= 6 K-tiles and tiles_n * S <= 96 (N = 1536: K = 1536 -> 4,
-// K = 4096 -> 8).  ESMDIFF_GEMM_PSPLIT=<S> overrides (A/B runs; must divide K/64).
+// K = 4096 -> 8).
 int gemm_partial_splits(int N, int K) {
-  static const int forced = [] {
-    const char* e = ed_dbg_env("ESMDIFF_GEMM_PSPLIT");
-    return e ? atoi(e) : 0;
-  }();
   const int nk = K / BK, tiles_n = N / BN;
-  if (forced > 0 && nk % forced == 0) return forced;
   for (int c = 8; c >= 2; --c)
     if (nk % c == 0 && nk / c >= 6 && tiles_n * c <= 96) return c;
   return 1;

@@ -21,7 +21,6 @@
 // Kernels here (all HBM-bound, one wave per row):
 //   split_rows_kernel          f32 [M, K] -> A3, rs
 //   layernorm_split_kernel     LayerNorm (optionally of GELU(x): the head's Linear -> GELU -> LayerNorm) -> A3, rs
-//   swiglu_split_kernel        silu(gate) * up of the FFN-up output [M, 2 FH] -> A3 [M, 3 FH], rs
 //   weight_absmax / split_weight_kernel   create-time weight conversion
 #include <string.h>
 
@@ -248,47 +247,6 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(
   }
 }
 
-// mid = silu(gate) * up (strict.hip::swiglu_f32_kernel's arithmetic) of one [2 FH] row, as a split row.  FH <= 256 * NV.
-template <int NV, bool FULL>
-__global__ __launch_bounds__(256) void swiglu_split_kernel(const float* __restrict__ gu, uint16_t* __restrict__ dst,
-                                                           float* __restrict__ rs, int M, int FH) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  const float* g = gu + (int64_t)row * 2 * FH;
-  f32x4 v[NV];
-  float amax = 0.f;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = j * 256 + lane * 4;
-    if (FULL || c < FH) {
-      const f32x4 gg = *reinterpret_cast<const f32x4*>(g + c);
-      const f32x4 uu = *reinterpret_cast<const f32x4*>(g + FH + c);
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (gg[e] / (1.0f + expf(-gg[e]))) * uu[e];
-      v[j] = o;
-      amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
-    }
-  }
-  amax = wmax64(amax);
-  float sc, inv;
-  row_scale(amax, sc, inv);
-  if (lane == 0) rs[row] = inv;
-  uint16_t* d = dst + (int64_t)row * 3 * FH;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = j * 256 + lane * 4;
-    if (FULL || c < FH) {
-      f16x4 hi, lo;
-      split4(v[j], sc, hi, lo);
-      *reinterpret_cast<f16x4*>(d + c) = hi;
-      *reinterpret_cast<f16x4*>(d + FH + c) = lo;
-      *reinterpret_cast<f16x4*>(d + 2 * FH + c) = hi;
-    }
-  }
-}
-
 // ---- weights (engine create) ----------------------------------------------------------------------------------
 __device__ __forceinline__ float load_w(const void* src, int dt, int64_t i) {
   if (dt == ESMDIFF_F32) return reinterpret_cast<const float*>(src)[i];
@@ -404,24 +362,6 @@ hipError_t launch_layernorm_split(const float* x, const float* w, const float* b
     default: ED_LN(8); break;
   }
 #undef ED_LN
-  return hipGetLastError();
-}
-
-hipError_t launch_swiglu_split(const float* gu, uint16_t* dst, float* rs, int M, int FH, hipStream_t stream) {
-  if (M <= 0) return hipSuccess;
-  if (FH % 4 || FH > 4096) return hipErrorInvalidValue;
-  dim3 grid((M + 3) / 4), block(256);
-  const int nv = (FH + 255) / 256;
-#define ED_SW(N)                                                                                                     \
-  do {                                                                                                               \
-    if (FH == N * 256) hipLaunchKernelGGL((swiglu_split_kernel<N, true>), grid, block, 0, stream, gu, dst, rs, M, FH); \
-    else hipLaunchKernelGGL((swiglu_split_kernel<N, false>), grid, block, 0, stream, gu, dst, rs, M, FH);            \
-  } while (0)
-  if (nv <= 4) ED_SW(4);
-  else if (nv <= 8) ED_SW(8);
-  else if (nv <= 14) ED_SW(14);
-  else ED_SW(16);
-#undef ED_SW
   return hipGetLastError();
 }
 

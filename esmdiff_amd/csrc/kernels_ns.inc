@@ -64,14 +64,9 @@ hipError_t launch_gemm_bf16(const bf16_t* A, const bf16_t* W, void* out, const f
 // the kernel launch_gemm_bf16 would pick for (M, N, K), as text
 void describe_gemm(int M, int N, int K, size_t ws_floats, char* out, size_t cap);
 
-// Row count below which a (sub-)batch takes the small-batch path (DESIGN 3.8).  ESMDIFF_SMALL_MAX_ROWS overrides (A/B runs).
+// Row count below which a (sub-)batch takes the small-batch path (DESIGN 3.8).
 inline int small_max_rows() {
-  static const int v = [] {
-    const char* e = ed_dbg_env("ESMDIFF_SMALL_MAX_ROWS");
-    const int x = e ? atoi(e) : 1152;  // r02: 1 024 -> 1 152 (+4 % at 1 032 - 1 080 rows; 2 048 loses 5 - 20 % from 1 440 rows)
-    return x < 128 ? 128 : (x > 8192 ? 8192 : x);
-  }();
-  return v;
+  return 1152;  // r02: 1 024 -> 1 152 (+4 % at 1 032 - 1 080 rows; 2 048 loses 5 - 20 % from 1 440 rows)
 }
 
 // Small-batch path (M < small_max_rows()): the product as S raw f32 K-slice planes in `ws` (plane stride `stride` floats, row stride
@@ -130,7 +125,6 @@ hipError_t launch_gather_rows(const int64_t* tok, const float* table, float* out
                               hipStream_t stream);
 // v f32 [M, ld] (23 used) -> backbone N/CA/C coordinates f32 [M, 3, 3]
 hipError_t launch_dim6_to_backbone(const float* v, int ld, float* out, int M, float trans_scale, hipStream_t stream);
-hipError_t launch_delay_us(int us, hipStream_t stream);
 // pairwise.hip: the decoder's pairwise confidence head (pair features; PAE / pTM from the 64 PAE bin logits)
 hipError_t launch_pair_features(const bf16_t* qk, bf16_t* X, int nb, int L, hipStream_t stream);
 hipError_t launch_pair_features_f32(const float* qk, float* X, int nb, int L, hipStream_t stream);
@@ -170,7 +164,6 @@ hipError_t launch_split_rows(const float* src, int ld, uint16_t* dst, float* rs,
 hipError_t launch_layernorm_split(const float* x, const float* w, const float* b, uint16_t* dst, float* rs, float* y32,
                                   int M, int D, int gelu_in, hipStream_t stream, const uint16_t* delta = nullptr,
                                   int delta_is_f16 = 0);
-hipError_t launch_swiglu_split(const float* gu, uint16_t* dst, float* rs, int M, int FH, hipStream_t stream);
 // create time, synchronous: dst [rows_pad, 3K] (caller zero-fills the padding rows); scratch_bits: 4 device bytes
 hipError_t split_weight(const void* src, int src_dtype, uint16_t* dst, int64_t rows, int K, uint32_t* scratch_bits,
                         float* inv_scale_out, int interleave_h = 0);

@@ -838,7 +838,8 @@ def gemm_split(a2: torch.Tensor, rs: Optional[torch.Tensor], w2: torch.Tensor, w
 
 
 def gemm_bf16_timed(A, W, out, epilogue, iters=20, bias=None, alpha=1.0) -> float:
-    """Average milliseconds per launch, HIP events on the launch stream (esmdiff_gemm_bf16_timed; -DED_DEBUG builds only)."""
+    """Average milliseconds per launch, HIP events on the launch stream (esmdiff_gemm_bf16_timed, the one entry point
+    that -DED_DEBUG adds to the library; that flag changes nothing else)."""
     _require_gpu()
     if not hasattr(N.lib(), "esmdiff_gemm_bf16_timed"):
         raise RuntimeError("esmdiff_gemm_bf16_timed is a measurement aid of -DED_DEBUG builds: "

@@ -120,10 +120,10 @@ typedef struct esmdiff_engine esmdiff_engine;
 int esmdiff_abi_version(void);
 
 /* What this library is and how an engine will run a batch — for logs (the CLI prints both beside "Sampling token time").
- * The product library reads NO ESMDIFF_* environment variable (one exception: it refuses to create an engine while
- * ESMDIFF_DEBUG_SKIP is set); the tuning switches of the A/B experiments exist in -DED_DEBUG builds only, and
- * esmdiff_get_build_info says which kind this is.  Both write a NUL-terminated text into buf [host, cap bytes] and return
- * the length the full text needs (excluding the NUL), or < 0.
+ * No build of the library reads an ESMDIFF_* environment variable (one exception: it refuses to create an engine while
+ * ESMDIFF_DEBUG_SKIP, the launch-skipping switch of the retired A/B experiments, is set); debug_env=1 in the build info only
+ * means a -DED_DEBUG build, which also exports the timing aid declared in esmdiff_hip_test.h.  Both write a NUL-terminated
+ * text into buf [host, cap bytes] and return the length the full text needs (excluding the NUL), or < 0.
  *   esmdiff_get_build_info   "abi=7 arch=gfx950 debug_env=0 ..."
  *   esmdiff_describe_plan    the dispatch plan of a (B, L) forward on this engine: precision, head precision, number of
  *                            sub-batch streams and their sizes, regular / small-batch path, the GEMM kernel of each block

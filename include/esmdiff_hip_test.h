@@ -1,7 +1,7 @@
 /*
  * esmdiff_hip_test.h — entry points of libesmdiff_hip.so that are NOT part of the drop-in surface (esmdiff_hip.h): one kernel
  * at a time for the parity tests (tests/test_gpu_*.py compare each against a float32 / float64 statement of the same op), the
- * per-section device-time profiler bench.py's roofline leg reads, and the measurement aids of -DED_DEBUG builds.  No call site
+ * per-section device-time profiler bench.py's roofline leg reads, and the timing aid of -DED_DEBUG builds.  No call site
  * of the reference binds any of them; same conventions as esmdiff_hip.h (device pointers owned by the caller, int status,
  * caller's stream).
  */
@@ -117,15 +117,10 @@ int esmdiff_set_profiling(esmdiff_engine* eng, int32_t on);
 int esmdiff_get_profile(esmdiff_engine* eng, float* ms_out, int32_t* launches_out);
 
 #ifdef ED_DEBUG
-/* ---- measurement aids: exported only by libraries built with -DED_DEBUG (ESMDIFF_EXTRA_CXXFLAGS=-DED_DEBUG python -m
- * esmdiff_amd.build); the product library carries neither these nor the ESMDIFF_DEBUG_SKIP launch-skipping switch, and
- * esmdiff_engine_create FAILS when that variable is set.  Used by scratch/ A/B scripts only. ---- */
-/* Measurement aid: one forward at (B, L) `n` times as plain launches and as `n` replays of one captured hipGraph of the
- * same launches (engine-owned stream); milliseconds per forward of each [host]. */
-int esmdiff_debug_graph_ab(esmdiff_engine* eng, const int64_t* seq, const int64_t* x, int32_t B, int32_t L, int32_t n,
-                           float* ms_direct, float* ms_graph);
-
-/* Wall-clock helper for the bench's roofline leg: runs the GEMM `iters` times on `stream` bracketed by
+/* ---- measurement aid: exported only by libraries built with -DED_DEBUG (ESMDIFF_EXTRA_CXXFLAGS=-DED_DEBUG python -m
+ * esmdiff_amd.build).  That flag switches nothing else: no build reads an ESMDIFF_* tuning variable.  Used by
+ * scratch/bench_gemm.py only. ---- */
+/* Runs the GEMM `iters` times on `stream` bracketed by
  * HIP events on that stream and returns the average milliseconds per launch in *ms_out [host]. */
 int esmdiff_gemm_bf16_timed(const void* A, const void* W, void* out, const float* bias, int32_t M,
                             int32_t N, int32_t K, int32_t ldc, int32_t n_valid, float alpha,

@@ -40,7 +40,7 @@ def test_library_exports_every_declared_symbol():
     assert lib_path.exists()
     surface = (ROOT / "include" / "esmdiff_hip.h").read_text()
     header = surface + (ROOT / "include" / "esmdiff_hip_test.h").read_text()
-    header = re.sub(r"#ifdef ED_DEBUG.*?#endif /\* ED_DEBUG \*/", "", header, flags=re.S)   # measurement aids of debug builds
+    header = re.sub(r"#ifdef ED_DEBUG.*?#endif /\* ED_DEBUG \*/", "", header, flags=re.S)   # the timing aid of debug builds
     assert "esmdiff_debug_graph_ab" not in header
     declared = set(re.findall(r"\b(esmdiff_[a-z0-9_]+)\s*\(", header))
     declared -= {"esmdiff_gemm_epilogue"}
@@ -104,8 +104,8 @@ def test_no_silent_cpu_fallback():
 
 
 def test_product_library_reads_no_tuning_environment():
-    """every ESMDIFF_* switch that can change a dispatch path (and with it the last bits of the logits) lives
-    behind -DED_DEBUG; the product library's strings hold no ESMDIFF_* name except the C enum constants that appear in mangled
+    """no ESMDIFF_* switch can change a dispatch path (and with it the last bits of the logits): r05 moved them
+    behind -DED_DEBUG, r09 retired them; the product library's strings hold no ESMDIFF_* name except the C enum constants that appear in mangled
     template names / messages and ESMDIFF_DEBUG_SKIP, which it reads only to REFUSE to create an engine.  Callers choose the
     legitimate knobs through esmdiff_set_option, and esmdiff_get_build_info says which kind of build this is."""
     import re

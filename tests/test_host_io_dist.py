@@ -599,7 +599,7 @@ def test_bench_dump_outputs_cap(tmp_path, monkeypatch):
 
 def test_bench_fails_fast_and_refuses_debug_switches(monkeypatch):
     """`--gpus N` with fewer visible GPUs ends in seconds with one line (no launcher started); ESMDIFF_DEBUG_SKIP in the
-    environment — the launch-skipping switch of -DED_DEBUG builds — makes bench.py refuse to measure at all."""
+    environment — the retired launch-skipping switch, which no build honours any more — makes bench.py refuse to measure at all."""
     import subprocess
     import sys
     import time
