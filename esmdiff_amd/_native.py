@@ -59,7 +59,9 @@ EXPORTS = [
     "esmdiff_get_sequence_logits", "esmdiff_gibbs_step_rows", "esmdiff_shared_forward_batch",
     "esmdiff_attention_f16", "esmdiff_qk_norm_rope", "esmdiff_add_layernorm", "esmdiff_geom_attention",
     "esmdiff_set_lengths", "esmdiff_attention_ragged",
+    "esmdiff_q_xt", "esmdiff_nelbo_rows", "esmdiff_nelbo_eval",
 ]
+QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
 OPT_STREAMS, OPT_DUAL_MIN_TOKENS = 1, 2      # esmdiff_option
 
 
@@ -122,6 +124,9 @@ def lib():
     L.esmdiff_get_profile.argtypes = [vp, c_f32p, ctypes.POINTER(i32)]
     L.esmdiff_set_frames.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.esmdiff_set_lengths.argtypes = [vp, ctypes.POINTER(i32), i32]
+    L.esmdiff_q_xt.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, i32, i32, vp]
+    L.esmdiff_nelbo_rows.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
+    L.esmdiff_nelbo_eval.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp]
     L.esmdiff_attention_ragged.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(i32), i32, i32, vp]
     L.esmdiff_decoder_create.argtypes = L.esmdiff_engine_create.argtypes
     L.esmdiff_decoder_decode.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]

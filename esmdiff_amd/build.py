@@ -39,6 +39,7 @@ UNITS = {
     "pairwise": [],
     "convert": [],
     "sampler": ["-ffp-contract=off"],
+    "score": ["-ffp-contract=off"],      # the sampler's canonical log-sum-exp order, bit for bit with the C oracle
     "gibbs": ["-ffp-contract=off"],
     "metrics": ["-ffp-contract=off"],
 }

@@ -142,7 +142,8 @@ struct esmdiff_engine {
   // exact skip of the noise-removal forward (esmdiff_set_final_skip): only samples that still hold a MASK run forward T + 1
   int final_skip = 0;
   int32_t *has_dev = nullptr, *idx_dev = nullptr;
-  int64_t *cx = nullptr, *cseq = nullptr;   // compacted token rows of those samples
+  int64_t *cx = nullptr, *cseq = nullptr;   // compacted token rows of those samples; esmdiff_nelbo_eval: the masked tokens xt and the coupled sequence
+  float* n_rowloss = nullptr;               // esmdiff_nelbo_rows: log_p * weight per token row, read by the per-sample reduction
   // gibbs options (esmdiff_set_gibbs_options): 0 entropy-ordered / 1 random positions; bit v of inv_mask = id v is never drawn
   int g_strategy = 0;
   uint32_t* g_inv_mask = nullptr;
@@ -1162,6 +1163,7 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     TRY(dalloc(e, &e->lens_sub_dev, (size_t)cfg->max_batch));
     TRY(dalloc(e, &e->cx, Mx));
     TRY(dalloc(e, &e->cseq, Mx));
+    TRY(dalloc(e, &e->n_rowloss, Mx));
     TRY(dalloc(e, &e->g_inv_mask, (size_t)128, true));
     TRY(dalloc(e, &e->g_sampled, Mx));
     TRY(dalloc(e, &e->g_rowflag, Mx));
@@ -1379,6 +1381,68 @@ int esmdiff_logit_error_stats(const float* a, int32_t ld_a, const float* b, int3
                               int32_t vocab, int32_t all_columns, float* out, void* stream) {
   if (!a || !b || !x || !out || rows < 0 || vocab <= 0 || ld_a < vocab || ld_b < vocab) return ESMDIFF_E_INVALID;
   return launch_logit_error_stats(a, ld_a, b, ld_b, x, rows, vocab, all_columns ? 1 : 0, out, (hipStream_t)stream) == hipSuccess ? 0 : ESMDIFF_E_HIP;
+}
+
+static int q_xt_checked(esmdiff_engine* e, const int64_t* x0, const int64_t* seq, const float* move_chance, const uint8_t* non_moving,
+                        const float* u, uint64_t seed, const uint64_t* sample_index, const int32_t* draw, int64_t* xt_out,
+                        int64_t* seq_out, int32_t B, int32_t L, hipStream_t st) {
+  if (!x0 || !move_chance || !xt_out) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (!u && (!sample_index || !draw)) return fail(e, ESMDIFF_E_INVALID, "need explicit uniforms, or sample_index and draw for the Philox source");
+  if (seq_out && !seq) return fail(e, ESMDIFF_E_INVALID, "seq_out (the coupled sequence mask) needs seq");
+  if (int r = check_bl(e, B, L)) return r;
+  if (int r = check_lens(e, B, L)) return r;
+  HIP_TRY(e, launch_q_xt(x0, seq, move_chance, non_moving, u, seed, sample_index, draw, e->cur_lens, xt_out, seq_out, B, L, st));
+  return 0;
+}
+
+static int nelbo_rows_checked(esmdiff_engine* e, const float* logits, int32_t ld_logits, const int64_t* xt, const int64_t* x0,
+                              const float* weight, const uint8_t* loss_mask, float* log_p_out, float* sample_sum,
+                              int32_t* sample_count, int32_t B, int32_t L, hipStream_t st) {
+  if (!logits || !xt || !x0 || !weight || !sample_sum || !sample_count) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (ld_logits < e->cfg.vocab_out) return fail(e, ESMDIFF_E_INVALID, "ld_logits (%d) below the vocabulary (%d)", ld_logits, e->cfg.vocab_out);
+  if (e->cfg.vocab_out <= ESMDIFF_MASK_ID) return fail(e, ESMDIFF_E_INVALID, "the nelbo needs the 4101-way head (mask column)");
+  if (int r = check_bl(e, B, L)) return r;      // (row_loss lives in the engine's workspace)
+  if (int r = check_lens(e, B, L)) return r;
+  Prof p{e, st};
+  p.mark(S_SAMPLER);
+  HIP_TRY(e, launch_nelbo_rows(logits, ld_logits, e->cfg.vocab_out, xt, x0, weight, loss_mask, e->cur_lens, log_p_out, e->n_rowloss,
+                               sample_sum, sample_count, B, L, st));
+  p.mark(S_SAMPLER);
+  return 0;
+}
+
+int esmdiff_q_xt(esmdiff_engine* e, const int64_t* x0, const int64_t* seq, const float* move_chance, const uint8_t* non_moving,
+                 const float* u, uint64_t seed, const uint64_t* sample_index, const int32_t* draw, int64_t* xt_out,
+                 int64_t* seq_out, int32_t B, int32_t L, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (e->kind != 0) return fail(e, ESMDIFF_E_INVALID, "this engine is a structure-token decoder (esmdiff_decoder_create)");
+  return q_xt_checked(e, x0, seq, move_chance, non_moving, u, seed, sample_index, draw, xt_out, seq_out, B, L, (hipStream_t)stream);
+}
+
+int esmdiff_nelbo_rows(esmdiff_engine* e, const float* logits, int32_t ld_logits, const int64_t* xt, const int64_t* x0,
+                       const float* weight, const uint8_t* loss_mask, float* log_p_out, float* sample_sum, int32_t* sample_count,
+                       int32_t B, int32_t L, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (e->kind != 0) return fail(e, ESMDIFF_E_INVALID, "this engine is a structure-token decoder (esmdiff_decoder_create)");
+  return nelbo_rows_checked(e, logits, ld_logits, xt, x0, weight, loss_mask, log_p_out, sample_sum, sample_count, B, L,
+                            (hipStream_t)stream);
+}
+
+int esmdiff_nelbo_eval(esmdiff_engine* e, const int64_t* seq, const int64_t* x0, const float* t_freq, const float* move_chance,
+                       const float* weight, const uint8_t* non_moving, const float* u, uint64_t seed, const uint64_t* sample_index,
+                       const int32_t* draw, const uint8_t* loss_mask, int32_t coupled, float* sample_sum, int32_t* sample_count,
+                       float* log_p_out, int32_t B, int32_t L, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (e->kind != 0) return fail(e, ESMDIFF_E_INVALID, "this engine is a structure-token decoder (esmdiff_decoder_create)");
+  if (!seq) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (int r = q_xt_checked(e, x0, seq, move_chance, non_moving, u, seed, sample_index, draw, e->cx, coupled ? e->cseq : nullptr, B, L, st))
+    return r;
+  const int64_t* net_seq = coupled ? e->cseq : seq;
+  const int rf = t_freq ? esmdiff_forward_logits_sigmas(e, net_seq, e->cx, t_freq, e->logits, e->ld_logits, B, L, stream)
+                        : esmdiff_forward_logits(e, net_seq, e->cx, nullptr, e->logits, e->ld_logits, B, L, stream);
+  if (rf) return rf;
+  return nelbo_rows_checked(e, e->logits, e->ld_logits, e->cx, x0, weight, loss_mask, log_p_out, sample_sum, sample_count, B, L, st);
 }
 
 int esmdiff_ddpm_sample(esmdiff_engine* e, const int64_t* seq, int64_t* x_inout, int32_t B, int32_t L, int32_t T,

@@ -38,6 +38,18 @@ hipError_t launch_move_token_rows(const int64_t* src, int64_t* dst, const int32_
 // flag[0] (device int32) = -1 if every row of seq and x [B, L] equals row 0, else 0
 hipError_t launch_rows_identical(const int64_t* seq, const int64_t* x, int B, int L, int32_t* flag, hipStream_t stream);
 
+// ---- score.hip -----------------------------------------------------------------------------
+// xt = (u < move_chance[b] and not non_moving and l < lens[b]) ? MASK : x0, and seq_out likewise with the sequence MASK when not
+// null; u: explicit uniforms [B,L], or null for Philox(seed, sample_index[b], draw[b], l, ESMDIFF_QXT_PHILOX_COLUMN)
+hipError_t launch_q_xt(const int64_t* x0, const int64_t* seq, const float* move_chance, const uint8_t* non_moving, const float* u,
+                       uint64_t seed, const uint64_t* sample_index, const int32_t* draw, const int32_t* lens, int64_t* xt,
+                       int64_t* seq_out, int B, int L, hipStream_t stream);
+// log_p (may be null) and row_loss [B,L] of the re-parameterised logits gathered at x0, then the per-sample masked sums in a
+// fixed order (esmdiff_nelbo_rows); loss_mask / lens may be null
+hipError_t launch_nelbo_rows(const float* logits, int ld, int V, const int64_t* xt, const int64_t* x0, const float* weight,
+                             const uint8_t* loss_mask, const int32_t* lens, float* log_p, float* row_loss, float* sample_sum,
+                             int32_t* sample_count, int B, int L, hipStream_t stream);
+
 // ---- gibbs.hip ---------------------------------------------------------------------------------
 // one entropy-ordered unmasking step: per masked row nucleus(top_p) + temperature draw + entropy, then per prompt
 // the n_unmask[b] lowest-entropy masked positions take their token.  u: [B,L,4096] explicit uniforms or null.

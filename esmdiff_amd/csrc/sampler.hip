@@ -17,6 +17,7 @@
 // Float-operation order is the canonical one documented in oracle/csrc/sampler_oracle.c; this TU is
 // compiled with -ffp-contract=off so that ed_math.h evaluates identically on host and device.
 #include "ed_math.h"
+#include "ed_wave.h"
 #include "kernels.h"
 
 namespace ed {
@@ -24,19 +25,6 @@ namespace ed {
 constexpr int NT = 256;
 constexpr int MASK_ID = ESMDIFF_MASK_ID;
 constexpr int MAX_PER_THREAD = 20;  // supports V <= 5120
-
-__device__ __forceinline__ float wave_halving_sum(float v) {
-  // t[i] = t[i] + t[i+off], off = 32..1; lane 0 ends with the canonical tree value
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 // MARGIN (esmdiff_ddpm_step_margin): the same draw, plus the runner-up of the arg-max: sample_flags[b] is set when, for some
 // masked row of sample b, the winner does not beat the runner-up by the factor `margin` (final pass: by the difference

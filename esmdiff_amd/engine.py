@@ -319,6 +319,110 @@ class Engine:
                                                     self.cfg.n_structure_heads, int(bool(all_columns)), _ptr(out), _stream()))
         return out
 
+    # ---- scoring (esmdiff_q_xt / esmdiff_nelbo_rows / esmdiff_nelbo_eval; host side in esmdiff_amd/nelbo.py) ----------------
+    def _per_sample(self, v, B: int, dtype: torch.dtype, what: str) -> torch.Tensor:
+        t = torch.as_tensor(v).reshape(-1).to(device=self.device, dtype=dtype).contiguous()
+        if t.numel() != B:
+            raise ValueError(f"{what}: {t.numel()} values for a batch of {B}")
+        return t
+
+    def _mask_u8(self, m, B: int, L: int, what: str) -> Optional[torch.Tensor]:
+        if m is None:
+            return None
+        m = (torch.as_tensor(m) != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        if tuple(m.shape) != (B, L):
+            raise ValueError(f"{what}: shape {tuple(m.shape)}, expected {(B, L)}")
+        return m
+
+    def _noise_args(self, B: int, L: int, u, seed, sample_index, draw):
+        """Explicit uniforms (B, L), or the Philox key arrays (u64 as int64 bits, int32)."""
+        if u is not None:
+            u = torch.as_tensor(u).to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(u.shape) != (B, L):
+                raise ValueError(f"u: shape {tuple(u.shape)}, expected {(B, L)}")
+            return u, None, None, 0
+        if seed is None or sample_index is None:
+            raise ValueError("masking noise: explicit uniforms `u` (B, L), or a Philox `seed` with `sample_index` (and `draw`)")
+        si = self._per_sample([int(v) for v in sample_index], B, torch.int64, "sample_index")
+        dr = self._per_sample([0] * B if draw is None else [int(v) for v in draw], B, torch.int32, "draw")
+        return None, si, dr, int(seed)
+
+    def q_xt(self, x0: torch.Tensor, move_chance, *, sequence_tokens: Optional[torch.Tensor] = None, coupled: bool = False,
+             non_moving_mask=None, u=None, seed: Optional[int] = None, sample_index=None, draw=None):
+        """The forward (masking) process, model.py:494-512 (esmdiff_q_xt): xt = MASK where u < move_chance[b] and the position
+        is not in non_moving_mask (and below the sample's length while lengths are set), else x0.  u: explicit uniforms (B, L),
+        or Philox(seed, sample_index[b], draw[b], l).  Returns (xt, sequence) — the sequence with the coupled mask when
+        `coupled`, else as given."""
+        B, L = x0.shape
+        x0 = self._tok(x0, B, L)
+        seq = None if sequence_tokens is None else self._tok(sequence_tokens, B, L)
+        mc = self._per_sample(move_chance, B, torch.float32, "move_chance")
+        nm = self._mask_u8(non_moving_mask, B, L, "non_moving_mask")
+        u, si, dr, seed = self._noise_args(B, L, u, seed, sample_index, draw)
+        xt = torch.empty_like(x0)
+        seq_out = torch.empty_like(seq) if (coupled and seq is not None) else None
+        self._chk(self._lib.esmdiff_q_xt(self._h, _ptr(x0), _ptr(seq), _ptr(mc), _ptr(nm), _ptr(u), seed, _ptr(si), _ptr(dr),
+                                         _ptr(xt), _ptr(seq_out), B, L, _stream()))
+        return xt, (seq_out if seq_out is not None else seq)
+
+    def nelbo_rows(self, logits: torch.Tensor, xt: torch.Tensor, x0: torch.Tensor, weight, *, loss_mask=None,
+                   return_log_p: bool = True, check_ids: bool = True):
+        """RAW logits (B, L, >= 4101) f32 -> (sample_sum f32 (B,), sample_count int32 (B,), log_p f32 (B, L) or None):
+        log p(x0) of the re-parameterised rows, times the signed per-sample weight, summed over the loss mask per sample in a
+        fixed order (esmdiff_nelbo_rows)."""
+        B, L = xt.shape
+        assert logits.dtype == torch.float32 and logits.is_cuda and logits.stride(-1) == 1 and tuple(logits.shape[:2]) == (B, L)
+        ld = logits.stride(1)
+        assert logits.stride(0) == ld * L and ld >= STRUCTURE_VOCAB and logits.shape[-1] >= STRUCTURE_VOCAB
+        xt, x0 = self._tok(xt, B, L), self._tok(x0, B, L)
+        if check_ids and bool(((x0 < 0) | (x0 >= STRUCTURE_VOCAB)).any()):     # (a device -> host read-back)
+            raise ValueError(f"structure ids must be in 0..{STRUCTURE_VOCAB - 1}")
+        w = self._per_sample(weight, B, torch.float32, "weight")
+        lm = self._mask_u8(loss_mask, B, L, "loss_mask")
+        ssum = torch.empty(B, dtype=torch.float32, device=self.device)
+        scnt = torch.empty(B, dtype=torch.int32, device=self.device)
+        lp = torch.empty(B, L, dtype=torch.float32, device=self.device) if return_log_p else None
+        self._chk(self._lib.esmdiff_nelbo_rows(self._h, _ptr(logits), ld, _ptr(xt), _ptr(x0), _ptr(w), _ptr(lm), _ptr(lp),
+                                               _ptr(ssum), _ptr(scnt), B, L, _stream()))
+        return ssum, scnt, lp
+
+    def nelbo_eval(self, sequence_tokens: torch.Tensor, x0: torch.Tensor, t_freq: Optional[torch.Tensor], move_chance, weight, *,
+                   non_moving_mask=None, u=None, seed: Optional[int] = None, sample_index=None, draw=None, loss_mask=None,
+                   coupled: bool = False, return_log_p: bool = False, lengths: Optional[Sequence[int]] = None,
+                   check_ids: bool = True):
+        """Mask, forward with one sigma per sample, score — one batch, queued without a host synchronisation
+        (esmdiff_nelbo_eval).  t_freq (B, freq_dim): the sinusoids of the conditioning sigmas as conditioning_rows returns
+        them, or None.  Returns (sample_sum f32 (B,), sample_count int32 (B,), log_p (B, L) or None) on the device."""
+        B, L = x0.shape
+        x0 = self._tok(x0, B, L)
+        seq = self._tok(sequence_tokens, B, L)
+        if lengths is not None:
+            with self._lengths_for_call(lengths, seq, x0):
+                return self.nelbo_eval(seq, x0, t_freq, move_chance, weight, non_moving_mask=non_moving_mask, u=u, seed=seed,
+                                       sample_index=sample_index, draw=draw, loss_mask=loss_mask, coupled=coupled,
+                                       return_log_p=return_log_p, check_ids=check_ids)
+        if check_ids:
+            self._check_ids(seq, x0)
+            if bool((x0 < 0).any()):
+                raise ValueError(f"structure ids must be in 0..{STRUCTURE_VOCAB - 1}")
+        tf = None
+        if t_freq is not None:
+            tf = t_freq.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(tf.shape) != (B, self.cfg.freq_dim):
+                raise ValueError(f"t_freq: shape {tuple(tf.shape)}, expected {(B, self.cfg.freq_dim)} (one sinusoid per sample)")
+        mc = self._per_sample(move_chance, B, torch.float32, "move_chance")
+        w = self._per_sample(weight, B, torch.float32, "weight")
+        nm = self._mask_u8(non_moving_mask, B, L, "non_moving_mask")
+        lm = self._mask_u8(loss_mask, B, L, "loss_mask")
+        u, si, dr, seed = self._noise_args(B, L, u, seed, sample_index, draw)
+        ssum = torch.empty(B, dtype=torch.float32, device=self.device)
+        scnt = torch.empty(B, dtype=torch.int32, device=self.device)
+        lp = torch.empty(B, L, dtype=torch.float32, device=self.device) if return_log_p else None
+        self._chk(self._lib.esmdiff_nelbo_eval(self._h, _ptr(seq), _ptr(x0), _ptr(tf), _ptr(mc), _ptr(w), _ptr(nm), _ptr(u), seed,
+                                               _ptr(si), _ptr(dr), _ptr(lm), int(bool(coupled)), _ptr(ssum), _ptr(scnt), _ptr(lp),
+                                               B, L, _stream()))
+        return ssum, scnt, lp
+
     def ddpm_sample(self, sequence_tokens: torch.Tensor, schedule: DDPMSchedule, *, seed: int,
                     sample_offset: int = 0, input_prior: Optional[torch.Tensor] = None,
                     lengths: Optional[Sequence[int]] = None, sample_index: Optional[Sequence[int]] = None) -> torch.Tensor:

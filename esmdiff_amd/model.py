@@ -17,7 +17,8 @@ from typing import Dict, Optional
 import torch
 
 from .config import ESM3_OPEN, ModelConfig
-from .constants import STRUCTURE_MASK_TOKEN, STRUCTURE_VOCAB
+from . import nelbo as _nelbo
+from .constants import SEQUENCE_MASK_TOKEN, STRUCTURE_MASK_TOKEN, STRUCTURE_VOCAB
 from .engine import Engine
 from .schedule import CosineNoise, CosineSqrNoise, GeometricNoise, Linear, LogLinearNoise, Noise, ddpm_schedule
 from .weights import load_checkpoint_state_dict, random_init_state_dict
@@ -27,7 +28,9 @@ class MaskedDiffusionLanguageModeling:
     def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: ModelConfig = ESM3_OPEN,
                  noise_schedule: Optional[Noise] = None, max_batch: int = 128, max_len: int = 1026,
                  device: int = 0, noise_removal: bool = True, precision: str = "bf16", step0_sharing: bool = True,
-                 head_precision: Optional[str] = None):
+                 head_precision: Optional[str] = None, antithetic_sampling: bool = True, importance_sampling: bool = False,
+                 change_of_variables: bool = False, T: int = 0, sampling_eps: float = 1e-3, structure_only: bool = False,
+                 coupled_condition_mask: bool = False):
         if noise_schedule is None:
             print("Using default noise schedule: CosineNoise(eps=1e-3)")    # model.py:345-347
             noise_schedule = CosineNoise(eps=1e-3)
@@ -38,6 +41,16 @@ class MaskedDiffusionLanguageModeling:
         self.vocab_size = STRUCTURE_VOCAB
         self.mask_index = STRUCTURE_MASK_TOKEN
         self.neg_infinity = -1000000.0
+        # the flags of the scoring path (model_step / nelbo; model.py:353-361), the reference's names and defaults
+        assert not (change_of_variables and importance_sampling)               # model.py:377
+        self.antithetic_sampling = antithetic_sampling
+        self.importance_sampling = importance_sampling
+        self.change_of_variables = change_of_variables
+        self.T = T
+        self.sampling_eps = sampling_eps
+        self.structure_only = structure_only
+        self.coupled_condition_mask = coupled_condition_mask
+        self.condition_mask_index = SEQUENCE_MASK_TOKEN
         # precision="certified": the f32-grade engine is `net` (every generic path — parity noise, _model_wrapper — runs on it);
         # the Philox ddpm loop and the gibbs loop (esmdiff_amd.gibbs.iterative_sampling_raw) draw on an f16 engine and verify only
         # the decisions its measured error leaves open on `net` (certified.py): the ids of `net`'s chain at about 2.4x its rate
@@ -133,6 +146,36 @@ class MaskedDiffusionLanguageModeling:
             sigma = torch.zeros_like(sigma)
         assert sigma.ndim == 1, sigma.shape
         return sigma
+
+    # ---- scoring: the forward-only validation path (esmdiff_amd/nelbo.py, csrc/score.hip) ------------------------------------
+    def _sample_t(self, n, device=None):
+        """model.py:517-525 on the host: n times from torch.rand(n) on the CPU generator (`device` is accepted and ignored: the
+        schedule scalars live on the host)."""
+        return _nelbo.sample_t(self, n)
+
+    @torch.no_grad()
+    def q_xt(self, x, move_chance, condition_seq=None, non_moving_mask=None, *, u=None, seed: Optional[int] = None,
+             sample_index=None, draw=None):
+        """model.py:494-512 on the device: (xt, condition_seq).  Noise: explicit uniforms `u` (B, L), a Philox `seed` (with
+        sample_index, default 0..B-1, and draw, default 0), or — neither given — torch.rand(*x.shape) on the CPU generator like
+        the reference."""
+        if u is None and seed is None:
+            u = torch.rand(*x.shape)
+        if u is None and sample_index is None:
+            sample_index = list(range(x.shape[0]))
+        return _nelbo.q_xt(self, x, move_chance, condition_seq, non_moving_mask, u=u, seed=seed, sample_index=sample_index, draw=draw)
+
+    @torch.no_grad()
+    def model_step(self, batch, training: bool = False, *, noise: str = "philox", seed: int = 0, sample_index=None):
+        """The reference's validation metric (model.py:386-462 with training=False): (loss, {"nelbo": loss}).  esmdiff_amd.nelbo.model_step."""
+        return _nelbo.model_step(self, batch, training, noise=noise, seed=seed, sample_index=sample_index)
+
+    @torch.no_grad()
+    def nelbo(self, structure_tokens, sequence_tokens, num_draws: int = 8, seed: int = 0, lengths=None, sample_index=None,
+              mask=None, non_moving_mask=None, *, max_batch: Optional[int] = None, return_log_p: bool = False):
+        """Per-structure negative ELBO (nats per counted token) and its standard error over num_draws draws: esmdiff_amd.nelbo.nelbo."""
+        return _nelbo.nelbo(self, structure_tokens, sequence_tokens, num_draws, seed, lengths, sample_index, mask, non_moving_mask,
+                            max_batch=max_batch, return_log_p=return_log_p)
 
     @torch.no_grad()
     def _ddpm_update(self, x, t, sequence_tokens, dt, *, u=None, seed: Optional[int] = None, sample_offset: int = 0, step: int = 0,
@@ -243,6 +286,19 @@ def config_from_hydra_yaml(path, cfg: ModelConfig = ESM3_OPEN):
     return cfg, noise
 
 
+SCORING_FLAGS = {"antithetic_sampling": bool, "importance_sampling": bool, "change_of_variables": bool, "T": int,
+                 "sampling_eps": float, "structure_only": bool, "coupled_condition_mask": bool}
+
+
+def scoring_flags_from_hydra_yaml(path) -> Dict[str, object]:
+    """The scoring flags a run's `.hydra/config.yaml` sets under `model:` (mdlm.yaml:37-49; model.py:334-340 for the ones the
+    yaml leaves to their defaults): the constructor's keyword arguments, so that model_step / nelbo of a loaded checkpoint use
+    the time grid, sampling_eps and loss branch the run was trained and validated with."""
+    import yaml
+    m = (yaml.safe_load(Path(path).read_text()) or {}).get("model", {}) or {}
+    return {k: cast(m[k]) for k, cast in SCORING_FLAGS.items() if m.get(k) is not None}
+
+
 def load_state_dict_from_lightning_ckpt(ckpt_path, device="cuda", max_batch: int = 128, max_len: int = 1026,
                                         cfg: ModelConfig = ESM3_OPEN, precision: str = "bf16",
                                         head_precision: Optional[str] = None):
@@ -255,8 +311,10 @@ def load_state_dict_from_lightning_ckpt(ckpt_path, device="cuda", max_batch: int
     print(f"Loading ESMDiff ckpt from {ckpt_path}")
     _, exp_cfg_path = checkpoint_file_and_config(ckpt_path)
     noise = LogLinearNoise()
+    flags = {}
     if exp_cfg_path is not None:
         cfg, noise = config_from_hydra_yaml(exp_cfg_path, cfg)
+        flags = scoring_flags_from_hydra_yaml(exp_cfg_path)
     else:
         print("Config file not found next to the checkpoint. Use default config (configs/experiment/mdlm.yaml).")
     print(f"Loaded experiment config: {exp_cfg_path or 'mdlm.yaml defaults'}...")
@@ -265,7 +323,7 @@ def load_state_dict_from_lightning_ckpt(ckpt_path, device="cuda", max_batch: int
     dev = torch.device(device).index or 0
     sd, load_t = broadcast_state_dict(lambda: load_checkpoint_state_dict(ckpt_path), torch.device("cuda", dev))
     model = MaskedDiffusionLanguageModeling(sd, cfg, noise, max_batch, max_len, dev, noise_removal=True, precision=precision,
-                                            head_precision=head_precision)
+                                            head_precision=head_precision, **flags)
     model.load_timings = load_t
     del sd
     print(f"Sucessfully loaded model from {ckpt_path}... (rank {load_t['rank']}: {load_t['load_s']} s, {load_t['bytes'] / 1e9:.2f} GB, "

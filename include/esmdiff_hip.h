@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ESMDIFF_ABI_VERSION 8   /* 8: + esmdiff_gibbs_step_rows, esmdiff_set_lengths (an addition); esmdiff_logit_error_stats writes 8 floats per row and takes all_columns; 7: + esmdiff_ddpm_step_rows, esmdiff_logit_error_stats (additions only); 6: + esmdiff_ddpm_step_margin, esmdiff_forward_logits_sigmas, esmdiff_set_small_batch_splitk */
+#define ESMDIFF_ABI_VERSION 8   /* 8: + esmdiff_q_xt, esmdiff_nelbo_rows, esmdiff_nelbo_eval (additions only, the number stays); + esmdiff_gibbs_step_rows, esmdiff_set_lengths (an addition); esmdiff_logit_error_stats writes 8 floats per row and takes all_columns; 7: + esmdiff_ddpm_step_rows, esmdiff_logit_error_stats (additions only); 6: + esmdiff_ddpm_step_margin, esmdiff_forward_logits_sigmas, esmdiff_set_small_batch_splitk */
 
 /* structure-track vocabulary: esm constants mirrored at model.py:380-381 */
 #define ESMDIFF_VOCAB 4101
@@ -114,6 +114,17 @@ typedef struct {
   uint64_t seed;
   uint64_t sample_offset; /* global index of batch row 0 */
 } esmdiff_rng;
+
+/* Philox columns reserved beyond the vocabulary (the single list; a new user takes a column that is not on it).  The draws read
+ * columns 0 .. 4100 (ddpm) and 0 .. 4095 (gibbs); beyond them:
+ *   4104  ESMDIFF_QXT_PHILOX_COLUMN: the mask uniform of position l in the scoring path (esmdiff_q_xt, esmdiff_nelbo_eval), key
+ *         (sample, draw, l, 4104) — `draw`, the index of the noise draw of that structure, sits in the counter word the samplers
+ *         use for the step;
+ *   4105  at l = 0: the HOST's draw of the time of that (sample, draw) pair (esmdiff_amd/nelbo.py);
+ *   4352  the per-position uniform of the gibbs "random" strategy (csrc/gibbs.hip).
+ * The three differ from each other and from every drawn column, so a score never reuses a uniform that produced the sample it
+ * scores. */
+#define ESMDIFF_QXT_PHILOX_COLUMN 4104
 
 typedef struct esmdiff_engine esmdiff_engine;
 
@@ -248,6 +259,43 @@ int esmdiff_ddpm_step_rows(esmdiff_engine* eng, int64_t* x_inout, const float* l
  * zeros for rows that are not MASK. */
 int esmdiff_logit_error_stats(const float* a, int32_t ld_a, const float* b, int32_t ld_b, const int64_t* x, int32_t rows,
                               int32_t vocab, int32_t all_columns, float* out, void* stream);
+
+/* ---- Scoring: the forward-only validation metric, MaskedDiffusionLanguageModeling.model_step(training=False), model.py:386-446.
+ *
+ * esmdiff_q_xt replaces q_xt (model.py:494-512): xt_out[b,l] = (u < move_chance[b] && !non_moving[b,l]) ? MASK : x0[b,l].
+ *   move_chance f32 [B] DEVICE (one per sample: every sample has its own time); non_moving u8 [B,L] or NULL;
+ *   u f32 [B,L] explicit uniforms (what torch.rand(*x.shape) draws, :503), or NULL for the Philox source: the uniform of
+ *   (seed, sample_index[b], draw[b], l, ESMDIFF_QXT_PHILOX_COLUMN) — sample_index u64 [B], draw i32 [B], DEVICE; a row's mask
+ *   depends on its own (sample_index, draw) only, not on its batch position.  seq_out != NULL (needs seq): the coupled sequence
+ *   mask of :510-511, seq_out = moved ? SEQUENCE_MASK (32) : seq.  xt_out may be x0 itself, seq_out may be seq.  While lengths
+ *   are set (esmdiff_set_lengths) positions l >= lens[b] keep x0.
+ *
+ * esmdiff_nelbo_rows replaces logits_parameterization + gather + the loss weighting and the masked sum (model.py:527-533,
+ *   :432-445) on RAW logits f32 [B,L,ld_logits]: log_p[b,l] = log p(x0[b,l]) of the re-parameterised row — for a MASK row of xt
+ *   z[x0] - logsumexp (mask column pushed by -1e6) in the sampler's canonical operation order (bit for bit the C oracle's
+ *   value); for any other row 0 where x0 == xt, else -1e6, without reading the logits.  weight f32 [B] DEVICE is the SIGNED
+ *   per-sample factor: -(dsigma / expm1(sigma)) (:443), or +log1p(-exp(-sigma_min)) in the change_of_variables /
+ *   importance_sampling branch (:439).  sample_sum[b] (f32 [B]) = sum_l log_p * weight[b] * loss_mask[b,l] in a fixed order
+ *   (position l is added by lane l % 256 in ascending l, then a halving tree per 64 lanes, then (w0 + w1) + (w2 + w3)),
+ *   sample_count[b] (i32 [B]) = sum_l loss_mask[b,l]: both a function of the sample alone.  loss_mask u8 [B,L] of 0 / 1 or NULL
+ *   (all ones); log_p_out f32 [B,L] or NULL.  While lengths are set, positions l >= lens[b] are outside the loss mask.
+ *   The batch scalar of :445 is sum_b sample_sum / sum_b sample_count, left to the caller.
+ *
+ * esmdiff_nelbo_eval runs the three steps for one batch on `stream` without a host synchronisation: esmdiff_q_xt into the
+ *   engine's own token buffers, esmdiff_forward_logits_sigmas (t_freq [B, freq_dim] DEVICE, one sinusoid per sample; NULL: a
+ *   network without conditioning) into the engine's own logits workspace, esmdiff_nelbo_rows.  coupled != 0: the network sees
+ *   the coupled sequence mask.  Honours esmdiff_set_lengths and esmdiff_set_frames like the forward.  The outputs equal those of
+ *   the three separate calls bit for bit (tests/test_gpu_nelbo.py). */
+int esmdiff_q_xt(esmdiff_engine* eng, const int64_t* x0, const int64_t* seq, const float* move_chance, const uint8_t* non_moving,
+                 const float* u, uint64_t seed, const uint64_t* sample_index, const int32_t* draw, int64_t* xt_out,
+                 int64_t* seq_out, int32_t B, int32_t L, void* stream);
+int esmdiff_nelbo_rows(esmdiff_engine* eng, const float* logits, int32_t ld_logits, const int64_t* xt, const int64_t* x0,
+                       const float* weight, const uint8_t* loss_mask, float* log_p_out, float* sample_sum, int32_t* sample_count,
+                       int32_t B, int32_t L, void* stream);
+int esmdiff_nelbo_eval(esmdiff_engine* eng, const int64_t* seq, const int64_t* x0, const float* t_freq, const float* move_chance,
+                       const float* weight, const uint8_t* non_moving, const float* u, uint64_t seed, const uint64_t* sample_index,
+                       const int32_t* draw, const uint8_t* loss_mask, int32_t coupled, float* sample_sum, int32_t* sample_count,
+                       float* log_p_out, int32_t B, int32_t L, void* stream);
 
 /* Replaces MaskedDiffusionLanguageModeling.ddpm_sample (model.py:543-581) for one batch, entirely on
  * the device, Philox noise: T updates + the noise-removal pass.  x_inout holds the prior on entry
