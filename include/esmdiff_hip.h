@@ -479,6 +479,36 @@ int esmdiff_metrics_validity(const double* ca, int32_t n, int32_t L, double ca_v
 int esmdiff_metrics_bonding_validity(const double* ca_model, int32_t n_model, const double* ca_ref, int32_t n_ref,
                                      int32_t L, double* out, void* stream);
 
+/* Superposition of ensembles (float64, device pointers in and out; each call synchronises `stream`): what the reference's
+ * evaluations compute pair by pair on the host — /root/reference/slm/utils/geo_utils.py:58-122 (squared_deviation through
+ * _find_rigid_alignment), analysis/apo_analysis.py:182-288 (scipy's align_vectors on sample pairs) and slm/utils/tm_utils.py
+ * (one `TMscore -seq` subprocess per pair).  (An addition; the ABI number stays.)
+ * A f64 [n, L, 3] is superposed onto B f64 [m, L, 3], residue i onto residue i; B == NULL: A against itself (m is ignored,
+ * maskB = maskA).  maskA u8 [n, L] / maskB u8 [m, L] or NULL (all valid): a pair's aligned set is the AND of both; masked
+ * coordinates are never read into a sum (they may be NaN).
+ *
+ * esmdiff_superpose_pairs: the least-squares (Kabsch) superposition of every pair.  allow_reflection = 1: R = V U^T of the SVD
+ * of the covariance with no determinant correction, as geo_utils._find_rigid_alignment (a mirror image aligns with RMSD 0);
+ * allow_reflection = 0: the proper rotation (det R = +1: scipy's Rotation.align_vectors, the RMSD `TMscore` prints).  Outputs,
+ * each may be NULL: rmsd f64 [n, m] (sqrt of the mean squared deviation over the aligned set); sd f64 [n, m, L] per-residue
+ * squared deviation after alignment, NaN where masked; R f64 [n, m, 3, 3] and t f64 [n, m, 3] with R a + t ~ b.  A pair with
+ * fewer than 2 aligned residues gives NaN everywhere.  Rank-deficient covariances (2 residues, collinear, planar) give the
+ * right RMSD and an orthogonal R.  Any L >= 1 (the structures are read from global memory).
+ *
+ * esmdiff_tm_pairs: tm f64 [n, m] = the TM-score of model A[i] against native B[j] with the fixed residue-to-residue
+ * correspondence (`TMscore -seq` on identical sequences), normalised by the number Ln of valid residues of B[j],
+ * d0 = max(0.5, 1.24 cbrt(Ln - 15) - 1.8); the maximisation over superpositions is the TMscore program's fragment-seeded
+ * heuristic search as DESIGN.md ("Superposition") states it — [TMSCORE-RECALL], restated from memory, PARITY UNPINNED: the
+ * program itself is in no tree this project can reach.  R / t (optional, shapes as above): the best superposition found.
+ * L > ESMDIFF_TM_MAX_L (both structures of a pair are staged in LDS) returns ESMDIFF_E_CAPACITY: there is no slow path.
+ * Both entries are deterministic (fixed reduction order, no float atomics) and a pair's value does not depend on the launch. */
+#define ESMDIFF_TM_MAX_L 1280
+int esmdiff_superpose_pairs(const double* A, int32_t n, const double* B, int32_t m, int32_t L, const uint8_t* maskA,
+                            const uint8_t* maskB, int32_t allow_reflection, double* rmsd, double* sd, double* R, double* t,
+                            void* stream);
+int esmdiff_tm_pairs(const double* A, int32_t n, const double* B, int32_t m, int32_t L, const uint8_t* maskA,
+                     const uint8_t* maskB, double* tm, double* R, double* t, void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
