@@ -61,8 +61,10 @@ EXPORTS = [
     "esmdiff_set_lengths", "esmdiff_attention_ragged",
     "esmdiff_q_xt", "esmdiff_nelbo_rows", "esmdiff_nelbo_eval",
     "esmdiff_superpose_pairs", "esmdiff_tm_pairs",
+    "esmdiff_cluster_threshold", "esmdiff_cluster_gromos",
 ]
 TM_MAX_L = 1280                              # ESMDIFF_TM_MAX_L
+CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
 OPT_STREAMS, OPT_DUAL_MIN_TOKENS = 1, 2      # esmdiff_option
 
@@ -141,6 +143,8 @@ def lib():
     L.esmdiff_metrics_bonding_validity.argtypes = [vp, i32, vp, i32, i32, f64p, vp]
     L.esmdiff_superpose_pairs.argtypes = [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.esmdiff_tm_pairs.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.esmdiff_cluster_threshold.argtypes = [vp, i32, i32, i32, f64, i32, vp, vp]
+    L.esmdiff_cluster_gromos.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.esmdiff_encoder_create.argtypes = [i32] * 9 + [ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.esmdiff_encoder_destroy.argtypes = [vp]
     L.esmdiff_encoder_destroy.restype = None

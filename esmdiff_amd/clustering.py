@@ -1,0 +1,193 @@
+"""Clustering of ensembles on the device: the GROMOS algorithm (Daura et al. 1999, the `gromos` method of `gmx cluster`) on the
+all-pairs layer of esmdiff_amd/ensemble.py, and the populations of given states.
+
+Which distinct conformations are in an ensemble, how populated is each, and which model represents each one.  The reference has
+no clustering of its own: analysis/bpti_analysis.py reads the five kinetic clusters of BPTI from files; `state_populations` asks
+that question ("how much of my ensemble is in each known basin") of any set of states.  There is no CPU fallback.
+
+The algorithm (DESIGN.md "Clustering"; tests/cluster_ref.py restates it on the host): i < j are neighbours iff d[i, j] <= cutoff
+(similarities, `larger_is_closer`: >=) — only the upper triangle of the matrix is ever read, that one entry decides the pair in
+both directions, a NaN entry means "not neighbours", every structure is its own neighbour.  Among the structures not yet assigned
+the one with the most unassigned neighbours (ties: the lowest index) is the centre of the next cluster; the cluster is the centre
+and all its unassigned neighbours; repeat.  csrc/cluster.hip holds the relation as a bit matrix and runs the whole loop in one
+launch; the matrix itself never has to exist in full.
+
+metric="tm" is [TMSCORE-RECALL], PARITY UNPINNED, as every TM-score of esmdiff_amd/ensemble.py (its module docstring)."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .ensemble import _check, _dev, _mask, _p, _stream
+
+CLUSTER_MAX_N = N.CLUSTER_MAX_N
+TM_NOTE = "[TMSCORE-RECALL], parity unpinned"
+
+
+@dataclass
+class Clustering:
+    """labels (n,) int32: the cluster of each structure, clusters numbered in order of creation; centres (K,) int32: the structure
+    at the centre of each cluster; sizes (K,) int32, non-increasing; n_clusters = K."""
+    labels: np.ndarray
+    centres: np.ndarray
+    sizes: np.ndarray
+    n_clusters: int
+
+
+def _need_gpu():
+    if not torch.cuda.is_available():
+        raise RuntimeError("esmdiff_amd.clustering needs an MI355X (gfx950); there is no CPU fallback")
+
+
+def _check_n(n: int, what: str):
+    if not 1 <= n <= CLUSTER_MAX_N:
+        raise ValueError(f"{what}: n = {n} structures, the clustering kernel takes 1 to {CLUSTER_MAX_N} (one count per structure in LDS)")
+
+
+def _code(code: int, what: str):
+    if code != 0:
+        raise RuntimeError(f"libesmdiff_hip {what} failed ({code})")
+
+
+def _new_adj(n: int) -> torch.Tensor:
+    return torch.zeros((n, (n + 63) // 64), dtype=torch.int64, device="cuda")
+
+
+def _threshold(block: torch.Tensor, row0: int, n: int, cutoff: float, larger_is_closer: bool, adj: torch.Tensor):
+    """block f64 (rows, n) on the device: rows row0 .. of the matrix -> their bits of adj."""
+    _code(N.lib().esmdiff_cluster_threshold(_p(block), block.shape[0], row0, n, float(cutoff), int(bool(larger_is_closer)), _p(adj),
+                                            _stream()), "esmdiff_cluster_threshold")
+
+
+def _gromos(adj: torch.Tensor, n: int) -> Clustering:
+    out = torch.empty((3, n), dtype=torch.int32, device="cuda")          # labels, centres, sizes
+    k = torch.zeros(1, dtype=torch.int32, device="cuda")
+    _code(N.lib().esmdiff_cluster_gromos(_p(adj), n, _p(out), _p(out, 4 * n), _p(out, 8 * n), _p(k), _stream()), "esmdiff_cluster_gromos")
+    K = int(k.item())
+    labels, centres, sizes = out.cpu().numpy()
+    return Clustering(labels.copy(), centres[:K].copy(), sizes[:K].copy(), K)
+
+
+def cluster_matrix(d, cutoff: float, larger_is_closer: bool = False, block_rows: int = 1024) -> Clustering:
+    """GROMOS clustering of n structures from any square matrix d (numpy, or a tensor on the host or the device) of distances, or
+    with larger_is_closer of similarities.  Only d[i, j] with i < j is read.  A host matrix goes to the device `block_rows` rows at
+    a time."""
+    shape = tuple(d.shape) if hasattr(d, "shape") else np.shape(d)
+    if len(shape) != 2 or shape[0] != shape[1]:
+        raise ValueError(f"cluster_matrix takes a square matrix, got {shape}")
+    n = int(shape[0])
+    _check_n(n, "cluster_matrix")
+    _need_gpu()
+    if not torch.is_tensor(d):
+        d = np.asarray(d)
+    adj = _new_adj(n)
+    for r0 in range(0, n, max(1, int(block_rows))):
+        rows = d[r0:r0 + max(1, int(block_rows))]
+        block = (rows if torch.is_tensor(rows) else torch.as_tensor(np.ascontiguousarray(rows))).to(device="cuda", dtype=torch.float64)
+        _threshold(block.contiguous(), r0, n, cutoff, larger_is_closer, adj)
+    return _gromos(adj, n)
+
+
+def _tm_device(A, B, ma, mb) -> torch.Tensor:
+    n, m, L = A.shape[0], B.shape[0], A.shape[1]
+    tm = torch.empty(n, m, dtype=torch.float64, device="cuda")
+    _check(N.lib().esmdiff_tm_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), _p(tm), None, None, _stream()), "esmdiff_tm_pairs", L)
+    return tm
+
+
+def _rmsd_device(A, B, ma, mb) -> torch.Tensor:
+    n, m, L = A.shape[0], B.shape[0], A.shape[1]
+    out = torch.empty(n, m, dtype=torch.float64, device="cuda")
+    _check(N.lib().esmdiff_superpose_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), 0, _p(out), None, None, None, _stream()),
+           "esmdiff_superpose_pairs", L)
+    return out
+
+
+def _metric(metric: str) -> bool:
+    """-> larger_is_closer"""
+    if metric not in ("rmsd", "tm"):
+        raise ValueError(f"metric should be 'rmsd' or 'tm', got {metric!r}")
+    return metric == "tm"
+
+
+def cluster_ensemble(samples, cutoff: float, metric: str = "rmsd", mask=None, block_rows: int = 1024) -> Clustering:
+    """GROMOS clustering of an ensemble: `samples` (n, L, 3) CA traces as everywhere in esmdiff_amd/ensemble.py (array, tensor or
+    path), residues with NaN coordinates or masked by `mask` (n, L) left out of every superposition.
+
+    metric="rmsd": cutoff in Angstrom on the RMSD after least-squares superposition with proper rotations (pairwise_rmsd).  The
+    relation is built from blocks of `block_rows` rows of the all-pairs matrix (esmdiff_superpose_pairs of the block against all,
+    then esmdiff_cluster_threshold): no more than block_rows x n doubles of the matrix exist at any time, and nothing of it crosses
+    to the host.
+    metric="tm": cutoff on the symmetric mean 0.5 (tm[i, j] + tm[j, i]) of the TM-score, larger is closer.  The mean needs both
+    triangles, so the FULL n x n TM matrix is built on the device (8 n^2 bytes, and one workgroup per ordered pair).
+    [TMSCORE-RECALL], PARITY UNPINNED (esmdiff_amd/ensemble.py): the TM search restates the TMscore program's heuristic from
+    memory and has not been compared with the program."""
+    larger = _metric(metric)
+    A = _dev(samples, "samples")
+    n, L = A.shape[:2]
+    _check_n(n, "cluster_ensemble")
+    ma = _mask(A, mask)
+    adj = _new_adj(n)
+    if larger:
+        tm = _tm_device(A, A, ma, ma)
+        _threshold((0.5 * (tm + tm.T)).contiguous(), 0, n, cutoff, True, adj)
+        return _gromos(adj, n)
+    step = max(1, min(int(block_rows), n))
+    buf = torch.empty((step, n), dtype=torch.float64, device="cuda")
+    fn = N.lib().esmdiff_superpose_pairs
+    for r0 in range(0, n, step):
+        rows = min(step, n - r0)
+        code = fn(_p(A, r0 * L * 24), rows, _p(A), n, L, _p(ma, r0 * L), _p(ma), 0, _p(buf), None, None, None, _stream())
+        _check(code, "esmdiff_superpose_pairs", L)
+        _threshold(buf[:rows], r0, n, cutoff, False, adj)
+    return _gromos(adj, n)
+
+
+def _to_states(A: torch.Tensor, B: torch.Tensor, ma, mb, larger: bool) -> torch.Tensor:
+    """(n, K) on the device: the RMSD of every A[i] to every B[k], or the symmetric mean of the two TM-scores."""
+    if larger:
+        return 0.5 * (_tm_device(A, B, ma, mb) + _tm_device(B, A, mb, ma).T)
+    return _rmsd_device(A, B, ma, mb)
+
+
+def centre_distances(samples, clustering: Clustering, metric: str = "rmsd", mask=None) -> np.ndarray:
+    """Each structure's distance to the centre of its own cluster -> (n,): the RMSD in Angstrom (the centres themselves: 0 to
+    rounding), or for metric="tm" the symmetric mean TM-score ([TMSCORE-RECALL], parity unpinned).  One n x K launch and a gather."""
+    larger = _metric(metric)
+    A = _dev(samples, "samples")
+    labels = np.asarray(clustering.labels)
+    assert labels.shape == (A.shape[0],), f"the clustering is of {labels.shape[0]} structures, the samples are {A.shape[0]}"
+    ma = _mask(A, mask)
+    centres = torch.as_tensor(np.asarray(clustering.centres), dtype=torch.int64, device="cuda")
+    C = A[centres].contiguous()
+    mc = None if ma is None else ma[centres].contiguous()
+    d = _to_states(A, C, ma, mc, larger)
+    return d.gather(1, torch.as_tensor(labels, dtype=torch.int64, device="cuda")[:, None])[:, 0].cpu().numpy()
+
+
+def state_populations(samples, states, cutoff=None, metric: str = "rmsd"):
+    """Each sample goes to the nearest of K given states (K, L, 3) -> (assignment (n,) int32, populations (K,), distance (n,)):
+    the state's index (ties: the lowest), the fraction of the n samples assigned to each state, and the sample's RMSD to its state
+    (metric="tm": the symmetric mean TM-score, and nearest means largest; [TMSCORE-RECALL], parity unpinned).  With a cutoff a
+    sample farther than it from every state (tm: below it) is assigned to none, -1, and the populations sum to less than one; so
+    is a sample with no defined distance to any state (NaN).  `distance` is to the nearest state either way."""
+    larger = _metric(metric)
+    A, S = _dev(samples, "samples"), _dev(states, "states")
+    assert S.shape[1] == A.shape[1], f"structures of different lengths: {A.shape[1]} and {S.shape[1]} (the correspondence is residue to residue)"
+    d = _to_states(A, S, _mask(A, None), _mask(S, None), larger)
+    K = S.shape[0]
+    worst = float("-inf") if larger else float("inf")
+    key = torch.where(torch.isnan(d), torch.full_like(d, worst), d)
+    best = key.max(1).values if larger else key.min(1).values
+    index = torch.arange(K, device="cuda")[None].expand_as(key)
+    assignment = torch.where(key == best[:, None], index, torch.full_like(index, K)).min(1).values     # the lowest index on a tie
+    none = best == worst
+    if cutoff is not None:
+        none |= (best < cutoff) if larger else (best > cutoff)
+    assignment = torch.where(none, torch.full_like(assignment, -1), assignment)
+    populations = torch.bincount(assignment[~none], minlength=K).to(torch.float64) / A.shape[0]
+    distance = torch.where(best == worst, torch.full_like(best, float("nan")), best)
+    return assignment.to(torch.int32).cpu().numpy(), populations.cpu().numpy(), distance.cpu().numpy()

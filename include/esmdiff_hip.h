@@ -509,6 +509,33 @@ int esmdiff_superpose_pairs(const double* A, int32_t n, const double* B, int32_t
 int esmdiff_tm_pairs(const double* A, int32_t n, const double* B, int32_t m, int32_t L, const uint8_t* maskA,
                      const uint8_t* maskB, double* tm, double* R, double* t, void* stream);
 
+/* Clustering of an ensemble (device pointers in and out; each call synchronises `stream`): the GROMOS algorithm (Daura et al.
+ * 1999, the `gromos` method of `gmx cluster`) on a neighbour relation, as DESIGN.md ("Clustering") states it.  (An addition; the
+ * ABI number stays.)  The reference clusters nothing itself: analysis/bpti_analysis.py reads the five kinetic clusters of BPTI
+ * from files.
+ * The relation is a bit matrix adj u64 [n, W], W = ceil(n / 64): bit (j % 64) of adj[i, j / 64] = "i and j are neighbours";
+ * the padding bits of a row's last word are zero.  n > ESMDIFF_CLUSTER_MAX_N (the loop keeps one int32 count per structure
+ * in LDS) returns ESMDIFF_E_CAPACITY, n < 1 ESMDIFF_E_INVALID, before anything is launched.
+ *
+ * esmdiff_cluster_threshold: d f64 [rows, n] holds rows row0 .. row0 + rows - 1 of an n x n matrix (a caller may feed the matrix
+ * block by block and never hold all of it).  For every row i of the block and every j > i the bit (i, j) is set iff
+ * d[i, j] <= cutoff (larger_is_closer = 1, similarities: d[i, j] >= cutoff); a NaN entry sets nothing; the bit (i, i) is always
+ * set; entries with j < i are never read, and no bit below the diagonal is written.  Bits are OR-ed into adj: the caller zeroes
+ * adj once before the first block.
+ *
+ * esmdiff_cluster_gromos: first makes adj symmetric IN PLACE from its bits on and above the diagonal (bit (j, i) = bit (i, j)
+ * for i < j; whatever stood below the diagonal or in the padding on entry is ignored and overwritten; the diagonal is set), then
+ * runs the loop in one launch of one persistent workgroup: among the structures not yet assigned, the one with the most
+ * unassigned neighbours (itself included; ties: the lowest index) is the centre of the next cluster, the cluster is the centre
+ * and all its unassigned neighbours; repeat until none is left.  labels i32 [n]: the cluster of each structure, clusters
+ * numbered in order of creation; centres i32 [n] and sizes i32 [n]: the first n_clusters[0] entries are valid (sizes are
+ * non-increasing); n_clusters i32 [1].  Integers only: the result is a pure function of adj's upper triangle. */
+#define ESMDIFF_CLUSTER_MAX_N 16384
+int esmdiff_cluster_threshold(const double* d, int32_t rows, int32_t row0, int32_t n, double cutoff, int32_t larger_is_closer,
+                              uint64_t* adj, void* stream);
+int esmdiff_cluster_gromos(uint64_t* adj, int32_t n, int32_t* labels, int32_t* centres, int32_t* sizes, int32_t* n_clusters,
+                           void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
