@@ -62,7 +62,9 @@ EXPORTS = [
     "esmdiff_q_xt", "esmdiff_nelbo_rows", "esmdiff_nelbo_eval",
     "esmdiff_superpose_pairs", "esmdiff_tm_pairs",
     "esmdiff_cluster_threshold", "esmdiff_cluster_gromos",
+    "esmdiff_lddt_pairs",
 ]
+LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
 TM_MAX_L = 1280                              # ESMDIFF_TM_MAX_L
 CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
@@ -145,6 +147,7 @@ def lib():
     L.esmdiff_tm_pairs.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.esmdiff_cluster_threshold.argtypes = [vp, i32, i32, i32, f64, i32, vp, vp]
     L.esmdiff_cluster_gromos.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.esmdiff_lddt_pairs.argtypes = [vp, i32, vp, i32, i32, vp, vp, f64, f64p, i32, i32, vp, vp, vp, vp, vp]
     L.esmdiff_encoder_create.argtypes = [i32] * 9 + [ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.esmdiff_encoder_destroy.argtypes = [vp]
     L.esmdiff_encoder_destroy.restype = None

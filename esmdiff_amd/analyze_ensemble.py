@@ -1,11 +1,17 @@
 """Evaluate one sampled ensemble against its target structures on the device.
 
     python -m esmdiff_amd.analyze_ensemble --samples <multi-MODEL pdb> --targets a.pdb [b.pdb ...] --output <dir> [--max_models 100]
+                                           [--lddt] [--plddt_scale 1.0]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
 three columns of bpti_tm_rmsd_div.csv (TM-ens, RMSD-ens, TM-div).  Writes <output>/<samples stem>.ensemble.json.
-TM-scores are [TMSCORE-RECALL], parity unpinned (esmdiff_amd/ensemble.py)."""
+TM-scores are [TMSCORE-RECALL], parity unpinned (esmdiff_amd/ensemble.py).
+--lddt adds the superposition-free scores of csrc/lddt.hip (integer counts, held exactly to numpy): lddt_ens (the best sample's
+CA-lDDT per target, averaged), lddt_div (the mean symmetric lDDT over sample pairs), best_lddt / best_lddt_model / best_lddt_residue
+(per target: the best sample's lDDT, its position among the analysed samples, its per-residue lDDT) and, when the samples' PDB
+carries B-factors (the decoder's pLDDT, divided by --plddt_scale), plddt_agreement: per target the per-residue mean observed lDDT,
+the mean predicted one, their Pearson r and the mean absolute difference."""
 from __future__ import annotations
 
 import argparse
@@ -15,12 +21,14 @@ from pathlib import Path
 import numpy as np
 
 from . import ensemble
-from .pdbio import load_coords
+from .pdbio import load_coords, read_pdb_bfactors
 
 
 def _jsonable(v):
     if isinstance(v, np.ndarray):
         return [_jsonable(x) for x in v.tolist()]
+    if isinstance(v, dict):
+        return {k: _jsonable(x) for k, x in v.items()}
     if isinstance(v, (list, tuple)):
         return [_jsonable(x) for x in v]
     if isinstance(v, (float, np.floating)):
@@ -28,19 +36,44 @@ def _jsonable(v):
     return v
 
 
-def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0) -> dict:
+def lddt_report(samples, targets, plddt=None, plddt_scale: float = 1.0) -> dict:
+    """The --lddt keys: samples (n, L, 3), targets (K, L, 3), plddt (n, L) or None."""
+    score, res = ensemble.lddt_matrix(samples, targets, per_residue=True)
+    best = np.where(np.isnan(score), -1.0, score).argmax(0)          # a sample without a defined score is never the best
+    out = {"lddt_ens": ensemble.lddt_ensemble(samples, targets), "lddt_div": ensemble.lddt_diversity(samples),
+           "best_lddt": [float(score[i, k]) for k, i in enumerate(best)], "best_lddt_model": [int(i) for i in best],
+           "best_lddt_residue": [res[i, k] for k, i in enumerate(best)]}
+    if plddt is not None:
+        out["plddt_agreement"] = [ensemble.plddt_agreement(samples, t, plddt, plddt_scale) for t in targets]
+    return out
+
+
+def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0) -> dict:
     samples = load_coords(Path(samples_path), max_n_model=None, verbose=False)
+    n_all, keep = len(samples), np.arange(len(samples))
     if len(samples) > max_models:
-        samples = samples[np.sort(np.random.default_rng(seed).choice(len(samples), max_models, replace=False))]
+        keep = np.sort(np.random.default_rng(seed).choice(len(samples), max_models, replace=False))
+        samples = samples[keep]
     targets = [load_coords(Path(p), max_n_model=None, verbose=False)[0] for p in target_paths]
     for p, t in zip(target_paths, targets):
         if t.shape[0] != samples.shape[1]:
             raise ValueError(f"{p} has {t.shape[0]} residues, the samples {samples.shape[1]}: the correspondence is residue to residue")
     if len(targets) == 2:
-        return ensemble.apo_report(samples, targets[0], targets[1])
-    best_tm, best_rmsd = ensemble.tm_n_ensemble(samples, np.stack(targets), max_n_model=max_models, rng=seed)
-    return {"best_tm": best_tm, "best_rmsd": best_rmsd, "TM-ens": float(np.mean(best_tm)), "RMSD-ens": float(np.mean(best_rmsd)),
-            "TM-div": ensemble.tm_diversity(samples)}
+        report = ensemble.apo_report(samples, targets[0], targets[1])
+    else:
+        best_tm, best_rmsd = ensemble.tm_n_ensemble(samples, np.stack(targets), max_n_model=max_models, rng=seed)
+        report = {"best_tm": best_tm, "best_rmsd": best_rmsd, "TM-ens": float(np.mean(best_tm)), "RMSD-ens": float(np.mean(best_rmsd)),
+                  "TM-div": ensemble.tm_diversity(samples)}
+    if lddt:
+        plddt = None
+        if Path(samples_path).name.endswith(".pdb") and Path(samples_path).is_file():
+            b = read_pdb_bfactors(samples_path)
+            if b.shape[0] == n_all:
+                b = b[keep]
+            if b.shape == samples.shape[:2] and np.any(b != 0):        # all zero: written without a confidence
+                plddt = b
+        report.update(lddt_report(samples, np.stack(targets), plddt, plddt_scale))
+    return report
 
 
 def main(argv=None) -> Path:
@@ -50,8 +83,10 @@ def main(argv=None) -> Path:
     ap.add_argument("--output", required=True, help="output directory")
     ap.add_argument("--max_models", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0, help="seed of the down-sampling to --max_models")
+    ap.add_argument("--lddt", action="store_true", help="add the CA-lDDT scores (no superposition) and the pLDDT agreement")
+    ap.add_argument("--plddt_scale", type=float, default=1.0, help="the samples' B-factors divided by this are pLDDT in [0, 1]")
     args = ap.parse_args(argv)
-    report = analyze(args.samples, args.targets, args.max_models, args.seed)
+    report = analyze(args.samples, args.targets, args.max_models, args.seed, args.lddt, args.plddt_scale)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

@@ -1,13 +1,13 @@
 """Cluster one sampled ensemble on the device and write its representatives.
 
-    python -m esmdiff_amd.cluster_ensemble --samples <multi-MODEL pdb> --cutoff <float> --output <dir> [--metric rmsd|tm]
+    python -m esmdiff_amd.cluster_ensemble --samples <multi-MODEL pdb> --cutoff <float> --output <dir> [--metric rmsd|tm|lddt]
                                            [--max_models N] [--seed 0]
 
 GROMOS clustering (esmdiff_amd/clustering.py) of the models' CA traces under an RMSD cutoff in Angstrom (--metric rmsd, the
-default) or a cutoff on the symmetric mean TM-score (--metric tm).  Writes two files into <output>:
+default) or a cutoff on the symmetric mean TM-score (--metric tm) or CA-lDDT (--metric lddt, no superposition).  Writes two files into <output>:
   <stem>.clusters.json   metric, cutoff, n, n_clusters, sizes, centres and models (0-based MODEL positions in the input: of the
                          cluster centres and of all n clustered models), labels (one per clustered model), and per cluster the
-                         mean and the maximum distance of its members to the centre (tm: distance = 1 - TM-score);
+                         mean and the maximum distance of its members to the centre (tm, lddt: distance = 1 - score);
   <stem>.clusters.pdb    the centre models in cluster order: MODEL k + 1 is the representative of cluster k, its ATOM / TER
                          records copied from the input.
 More than --max_models models (default: all are kept) are down-sampled without replacement from --seed, in input order.
@@ -28,9 +28,9 @@ from .pdbio import load_coords, merge_pdbfiles, split_pdbfile
 def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--samples", required=True, help="multi-MODEL PDB of the sampled ensemble")
-    ap.add_argument("--cutoff", required=True, type=float, help="neighbour cutoff: RMSD in Angstrom, or the TM-score with --metric tm")
+    ap.add_argument("--cutoff", required=True, type=float, help="neighbour cutoff: RMSD in Angstrom, or the TM-score / lDDT with --metric tm / lddt")
     ap.add_argument("--output", required=True, help="output directory")
-    ap.add_argument("--metric", choices=("rmsd", "tm"), default="rmsd")
+    ap.add_argument("--metric", choices=("rmsd", "tm", "lddt"), default="rmsd")
     ap.add_argument("--max_models", type=int, default=None, help="cluster at most this many models (default: all)")
     ap.add_argument("--seed", type=int, default=0, help="seed of the down-sampling to --max_models")
     return ap
@@ -38,9 +38,9 @@ def parser() -> argparse.ArgumentParser:
 
 def report(result, distances, models, metric: str, cutoff: float) -> dict:
     """The JSON document: `result` a Clustering of the models at input positions `models`, `distances` (n,) what
-    centre_distances gives (tm: the TM-score; the document holds 1 - TM)."""
+    centre_distances gives (tm, lddt: the score; the document holds 1 - score)."""
     labels, distances, models = np.asarray(result.labels), np.asarray(distances, np.float64), np.asarray(models)
-    if metric == "tm":
+    if metric in ("tm", "lddt"):
         distances = 1.0 - distances
     members = [distances[labels == k] for k in range(result.n_clusters)]
     out = {"metric": metric, "cutoff": float(cutoff), "n": int(len(labels)), "n_clusters": int(result.n_clusters),

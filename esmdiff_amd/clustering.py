@@ -12,7 +12,8 @@ the one with the most unassigned neighbours (ties: the lowest index) is the cent
 and all its unassigned neighbours; repeat.  csrc/cluster.hip holds the relation as a bit matrix and runs the whole loop in one
 launch; the matrix itself never has to exist in full.
 
-metric="tm" is [TMSCORE-RECALL], PARITY UNPINNED, as every TM-score of esmdiff_amd/ensemble.py (its module docstring)."""
+metric="tm" is [TMSCORE-RECALL], PARITY UNPINNED, as every TM-score of esmdiff_amd/ensemble.py (its module docstring).
+metric="lddt" (csrc/lddt.hip) needs no superposition and rests on no recalled program: integer counts, held exactly to numpy."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .ensemble import _check, _dev, _mask, _p, _stream
+from .ensemble import _check, _dev, _lddt_device, _mask, _p, _stream
 
 CLUSTER_MAX_N = N.CLUSTER_MAX_N
 TM_NOTE = "[TMSCORE-RECALL], parity unpinned"
@@ -108,9 +109,9 @@ def _rmsd_device(A, B, ma, mb) -> torch.Tensor:
 
 def _metric(metric: str) -> bool:
     """-> larger_is_closer"""
-    if metric not in ("rmsd", "tm"):
-        raise ValueError(f"metric should be 'rmsd' or 'tm', got {metric!r}")
-    return metric == "tm"
+    if metric not in ("rmsd", "tm", "lddt"):
+        raise ValueError(f"metric should be 'rmsd', 'tm' or 'lddt', got {metric!r}")
+    return metric != "rmsd"
 
 
 def cluster_ensemble(samples, cutoff: float, metric: str = "rmsd", mask=None, block_rows: int = 1024) -> Clustering:
@@ -124,13 +125,24 @@ def cluster_ensemble(samples, cutoff: float, metric: str = "rmsd", mask=None, bl
     metric="tm": cutoff on the symmetric mean 0.5 (tm[i, j] + tm[j, i]) of the TM-score, larger is closer.  The mean needs both
     triangles, so the FULL n x n TM matrix is built on the device (8 n^2 bytes, and one workgroup per ordered pair).
     [TMSCORE-RECALL], PARITY UNPINNED (esmdiff_amd/ensemble.py): the TM search restates the TMscore program's heuristic from
-    memory and has not been compared with the program."""
+    memory and has not been compared with the program.
+    metric="lddt": cutoff on the symmetric mean 0.5 (l[i, j] + l[j, i]) of the CA-lDDT (ensemble.lddt_matrix, default radius and
+    thresholds), larger is closer; a pair without a defined lDDT (NaN) is not a neighbour.  The same row-block path as the RMSD:
+    per block one launch for the block against all and one for all against the block, block_rows x n doubles at a time."""
     larger = _metric(metric)
     A = _dev(samples, "samples")
     n, L = A.shape[:2]
     _check_n(n, "cluster_ensemble")
     ma = _mask(A, mask)
     adj = _new_adj(n)
+    if metric == "lddt":
+        step = max(1, min(int(block_rows), n))
+        for r0 in range(0, n, step):
+            rows = slice(r0, min(r0 + step, n))
+            Ab, mab = A[rows], None if ma is None else ma[rows]
+            block = 0.5 * (_lddt_device(Ab, A, mab, ma) + _lddt_device(A, Ab, ma, mab).T)
+            _threshold(block.contiguous(), r0, n, cutoff, True, adj)
+        return _gromos(adj, n)
     if larger:
         tm = _tm_device(A, A, ma, ma)
         _threshold((0.5 * (tm + tm.T)).contiguous(), 0, n, cutoff, True, adj)
@@ -146,17 +158,20 @@ def cluster_ensemble(samples, cutoff: float, metric: str = "rmsd", mask=None, bl
     return _gromos(adj, n)
 
 
-def _to_states(A: torch.Tensor, B: torch.Tensor, ma, mb, larger: bool) -> torch.Tensor:
-    """(n, K) on the device: the RMSD of every A[i] to every B[k], or the symmetric mean of the two TM-scores."""
-    if larger:
+def _to_states(A: torch.Tensor, B: torch.Tensor, ma, mb, metric: str) -> torch.Tensor:
+    """(n, K) on the device: the RMSD of every A[i] to every B[k], or the symmetric mean of the two TM-scores / lDDTs."""
+    if metric == "lddt":
+        return 0.5 * (_lddt_device(A, B, ma, mb) + _lddt_device(B, A, mb, ma).T)
+    if metric == "tm":
         return 0.5 * (_tm_device(A, B, ma, mb) + _tm_device(B, A, mb, ma).T)
     return _rmsd_device(A, B, ma, mb)
 
 
 def centre_distances(samples, clustering: Clustering, metric: str = "rmsd", mask=None) -> np.ndarray:
     """Each structure's distance to the centre of its own cluster -> (n,): the RMSD in Angstrom (the centres themselves: 0 to
-    rounding), or for metric="tm" the symmetric mean TM-score ([TMSCORE-RECALL], parity unpinned).  One n x K launch and a gather."""
-    larger = _metric(metric)
+    rounding), or for metric="tm" the symmetric mean TM-score ([TMSCORE-RECALL], parity unpinned), for metric="lddt" the symmetric
+    mean lDDT.  One n x K launch (two for a similarity) and a gather."""
+    _metric(metric)
     A = _dev(samples, "samples")
     labels = np.asarray(clustering.labels)
     assert labels.shape == (A.shape[0],), f"the clustering is of {labels.shape[0]} structures, the samples are {A.shape[0]}"
@@ -164,20 +179,21 @@ def centre_distances(samples, clustering: Clustering, metric: str = "rmsd", mask
     centres = torch.as_tensor(np.asarray(clustering.centres), dtype=torch.int64, device="cuda")
     C = A[centres].contiguous()
     mc = None if ma is None else ma[centres].contiguous()
-    d = _to_states(A, C, ma, mc, larger)
+    d = _to_states(A, C, ma, mc, metric)
     return d.gather(1, torch.as_tensor(labels, dtype=torch.int64, device="cuda")[:, None])[:, 0].cpu().numpy()
 
 
 def state_populations(samples, states, cutoff=None, metric: str = "rmsd"):
     """Each sample goes to the nearest of K given states (K, L, 3) -> (assignment (n,) int32, populations (K,), distance (n,)):
     the state's index (ties: the lowest), the fraction of the n samples assigned to each state, and the sample's RMSD to its state
-    (metric="tm": the symmetric mean TM-score, and nearest means largest; [TMSCORE-RECALL], parity unpinned).  With a cutoff a
-    sample farther than it from every state (tm: below it) is assigned to none, -1, and the populations sum to less than one; so
-    is a sample with no defined distance to any state (NaN).  `distance` is to the nearest state either way."""
+    (metric="tm": the symmetric mean TM-score, and nearest means largest; [TMSCORE-RECALL], parity unpinned; metric="lddt": the
+    symmetric mean lDDT, nearest means largest).  With a cutoff a sample farther than it from every state (tm, lddt: below it) is
+    assigned to none, -1, and the populations sum to less than one; so is a sample with no defined distance to any state (NaN).
+    `distance` is to the nearest state either way."""
     larger = _metric(metric)
     A, S = _dev(samples, "samples"), _dev(states, "states")
     assert S.shape[1] == A.shape[1], f"structures of different lengths: {A.shape[1]} and {S.shape[1]} (the correspondence is residue to residue)"
-    d = _to_states(A, S, _mask(A, None), _mask(S, None), larger)
+    d = _to_states(A, S, _mask(A, None), _mask(S, None), metric)
     K = S.shape[0]
     worst = float("-inf") if larger else float("inf")
     key = torch.where(torch.isnan(d), torch.full_like(d, worst), d)

@@ -13,6 +13,9 @@ tests/ensemble_ref.py restates it on the host.  The TMscore binary is in no tree
 been compared with the program's.  The RMSD side IS pinned: tests/golden/g13_superposition.npz holds the outputs of the
 reference's own squared_deviation and of scipy's Rotation.align_vectors.
 
+The lDDT functions at the end (csrc/lddt.hip) need no superposition and no recalled program: the score is a ratio of integer counts
+of preserved distances, and those counts are held exactly to the numpy restatement tests/lddt_ref.py.
+
 Coordinates are CA traces (n, L, 3) in Angstrom: arrays, tensors, or a path (a multi-MODEL PDB or a directory of PDBs, read by
 pdbio.load_coords).  Residues with NaN coordinates are masked; `mask_*` arguments (n, L) mask more.  Results are numpy arrays /
 floats on the host."""
@@ -249,3 +252,94 @@ def apo_report(samples, struct1, struct2, mask1=None, mask2=None) -> dict:
             "tmpair": float((cross[0, 1] + cross[1, 0]) / 2),
             "rmsd": aligned_deviation(s1, s2, None if ms is None else ms[:1], None if ms is None else ms[1:])[0, 0],
             "rmsf": np.sqrt(np.mean(dev[iu] ** 2, axis=0)) if n > 1 else np.full(S.shape[1], np.nan)}
+
+
+# ---- lDDT: the superposition-free score (csrc/lddt.hip) ------------------------------------------------------------------
+LDDT_R0 = 15.0
+LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
+
+
+def _lddt_counts(A, B, ma, mb, n: int, m: int, per_residue: bool = False, r0: float = LDDT_R0, thresholds=LDDT_THRESHOLDS,
+                 seq_sep: int = 1):
+    """One esmdiff_lddt_pairs launch on device tensors (B None: A against itself) -> int32 device tensors kept (n, m),
+    total (m,), and with per_residue kept_res (n, m, L) and total_res (m, L) (else None, and never allocated)."""
+    L = A.shape[1]
+    thr = [float(t) for t in thresholds]
+    kept = torch.empty((n, m), dtype=torch.int32, device="cuda")
+    total = torch.empty((m,), dtype=torch.int32, device="cuda")
+    kept_res = torch.empty((n, m, L), dtype=torch.int32, device="cuda") if per_residue else None
+    total_res = torch.empty((m, L), dtype=torch.int32, device="cuda") if per_residue else None
+    code = N.lib().esmdiff_lddt_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), float(r0), (ctypes.c_double * len(thr))(*thr), len(thr),
+                                      int(seq_sep), _p(kept), _p(total), _p(kept_res), _p(total_res), _stream())
+    if code == -5:
+        raise RuntimeError(f"esmdiff_lddt_pairs: L = {L} is beyond the kernel's limit ({N.LDDT_MAX_L} residues: a model is staged in "
+                           f"LDS); there is no slow path")
+    if code == -1:
+        raise RuntimeError(f"esmdiff_lddt_pairs: invalid argument: L = {L} (at least 2), seq_sep = {seq_sep} (at least 1), "
+                           f"{len(thr)} thresholds (1 to {N.LDDT_MAX_THRESHOLDS})")
+    if code != 0:
+        raise RuntimeError(f"libesmdiff_hip esmdiff_lddt_pairs failed ({code})")
+    return kept, total, kept_res, total_res
+
+
+def _lddt_device(A, B, ma, mb, r0: float = LDDT_R0, thresholds=LDDT_THRESHOLDS, seq_sep: int = 1) -> torch.Tensor:
+    """lDDT (n, m) float64 on the device: kept / (n_thresholds total), NaN where the native has no pair."""
+    n, m = A.shape[0], (A if B is None else B).shape[0]
+    kept, total, _, _ = _lddt_counts(A, B, ma, mb, n, m, False, r0, thresholds, seq_sep)
+    return kept.to(torch.float64) / (len(thresholds) * total).to(torch.float64)[None]
+
+
+def lddt_matrix(models, natives=None, mask_models=None, mask_natives=None, per_residue: bool = False, r0: float = LDDT_R0,
+                thresholds=LDDT_THRESHOLDS, seq_sep: int = 1):
+    """CA-lDDT (Mariani et al. 2013) of every model against every native (natives = None: the models against themselves) -> (n, m)
+    float64, no superposition.  For native j the ordered residue pairs (a, b), |a - b| >= seq_sep, both resolved, closer than r0 in
+    the native are its pair set; a pair is kept once per threshold t with |d_model - d_native| < t (a pair whose model residue is
+    missing keeps nothing); the score is kept / (n_thresholds * pairs), pooled over the chain.  per_residue: also the (n, m, L) array
+    of the same ratio per residue a.  NaN where a native (a residue) has no pair.  The device returns the integer counts
+    (csrc/lddt.hip, equal to tests/lddt_ref.py's); the one division is done here."""
+    A, B, ma, mb, n, m = _pair_args(models, natives, mask_models, mask_natives)
+    kept, total, kept_res, total_res = _lddt_counts(A, B, ma, mb, n, m, per_residue, r0, thresholds, seq_sep)
+    nt = len(thresholds)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        score = kept.cpu().numpy() / (nt * total.cpu().numpy())[None]
+        if not per_residue:
+            return score
+        return score, kept_res.cpu().numpy() / (nt * total_res.cpu().numpy())[None]
+
+
+def lddt(model, native, mask_model=None, mask_native=None, r0: float = LDDT_R0, thresholds=LDDT_THRESHOLDS, seq_sep: int = 1) -> float:
+    """The lDDT of one (L, 3) CA trace against one native."""
+    return float(lddt_matrix(model, native, mask_model, mask_native, False, r0, thresholds, seq_sep)[0, 0])
+
+
+def lddt_ensemble(samples, natives) -> float:
+    """For every native the best sample's lDDT, averaged over the natives: tm_n_ensemble's TM-ensemble with lDDT for the TM-score."""
+    return float(np.mean(lddt_matrix(samples, natives).max(0)))
+
+
+def lddt_diversity(samples) -> float:
+    """The mean of the symmetric lDDT (l[i, j] + l[j, i]) / 2 over the sample pairs i < j (NaN for fewer than two samples)."""
+    l = lddt_matrix(samples)
+    iu = np.triu_indices(l.shape[0], 1)
+    return float(np.mean(0.5 * (l + l.T)[iu])) if len(iu[0]) else float("nan")
+
+
+def plddt_agreement(samples, native, plddt, scale: float = 1.0) -> dict:
+    """The decoder's per-residue confidence against what it predicts.  samples (n, L, 3), native (L, 3), plddt (n, L) as written
+    into the samples' B-factors, divided by `scale` to reach [0, 1] ->
+      observed (L,)    the mean over the samples of the per-residue lDDT against `native` (NaN: a residue without pairs)
+      predicted (L,)   the mean over the samples of plddt / scale
+      pearson_r        of the two over the residues where both are finite (NaN if either is constant)
+      mean_abs_diff    the mean |observed - predicted| over the same residues"""
+    _, res = lddt_matrix(samples, native, per_residue=True)
+    res = res[:, 0]
+    pred = np.asarray(plddt, np.float64) / float(scale)
+    if pred.ndim == 1:
+        pred = pred[None]
+    assert pred.shape == res.shape, f"plddt {pred.shape} does not match the samples {res.shape}"
+    observed, predicted = res.mean(0), pred.mean(0)
+    ok = np.isfinite(observed) & np.isfinite(predicted)
+    o, q = observed[ok] - observed[ok].mean(), predicted[ok] - predicted[ok].mean()
+    den = np.sqrt((o * o).sum() * (q * q).sum())
+    return {"observed": observed, "predicted": predicted, "pearson_r": float((o * q).sum() / den) if den > 0 else float("nan"),
+            "mean_abs_diff": float(np.mean(np.abs(observed[ok] - predicted[ok])))}

@@ -3,6 +3,7 @@
   read_pdb_backbone   what the CLI needs from ESMProtein.from_pdb (/root/reference/slm/sample_esmdiff.py:278-283):
                       the one-letter sequence of the first chain and its N/CA/C coordinates
   merge_pdbfiles      /root/reference/slm/utils/eval_utils.py:437-492 — one multi-MODEL file, 80-column lines
+  read_pdb_bfactors   the CA B-factors of every MODEL: the decoder's per-residue pLDDT as write_backbone_pdb stores it
   timer               /root/reference/slm/utils/eval_utils.py:24-34
 """
 from __future__ import annotations
@@ -200,6 +201,38 @@ def _backbone_coords_from_pdb(pdb_path, target_atoms=("N", "CA", "C")) -> np.nda
         raise ValueError(f"no backbone ATOM records in {pdb_path}")
     if len({m.shape for m in models}) != 1:
         raise ValueError(f"{pdb_path}: models of different lengths {sorted({m.shape[0] for m in models})}")
+    return np.stack(models, axis=0)
+
+
+def read_pdb_bfactors(path) -> np.ndarray:
+    """The CA B-factors (columns 61-66) of every MODEL of a PDB file (a file without MODEL records is one model) -> (n_models, L)
+    float64: where write_backbone_pdb puts the decoder's per-residue pLDDT.  The CA atoms are those _backbone_coords_from_pdb
+    reads (amino-acid residues, the first alternate location), so the rows line up with load_coords(path)."""
+    models, cur, first_alt = [], [], {}
+
+    def close():
+        if cur:
+            models.append(np.asarray(cur, dtype=np.float64))
+            cur.clear()
+
+    with open(path) as fh:
+        for line in fh:
+            name = line[:6].strip()
+            if name in ("MODEL", "ENDMDL"):
+                close()
+                first_alt.clear()
+            elif name in ("ATOM", "HETATM") and len(line) >= 54 and line[17:20].strip() in _AMINO_ACID_RESNAMES:
+                alt = line[16]
+                if alt != " " and first_alt.setdefault((line[21], line[22:27]), alt) != alt:
+                    continue
+                if line[12:16].strip() == "CA":
+                    field = line[60:66].strip()
+                    cur.append(float(field) if field else 0.0)
+    close()
+    if not models:
+        raise ValueError(f"no CA ATOM records in {path}")
+    if len({m.shape for m in models}) != 1:
+        raise ValueError(f"{path}: models of different lengths {sorted({m.shape[0] for m in models})}")
     return np.stack(models, axis=0)
 
 

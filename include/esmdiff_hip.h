@@ -536,6 +536,30 @@ int esmdiff_cluster_threshold(const double* d, int32_t rows, int32_t row0, int32
 int esmdiff_cluster_gromos(uint64_t* adj, int32_t n, int32_t* labels, int32_t* centres, int32_t* sizes, int32_t* n_clusters,
                            void* stream);
 
+/* All-pairs CA-lDDT (Mariani et al. 2013) of models against natives: superposition-free, local, and INTEGER — the counts of
+ * preserved distances, held exactly to the numpy restatement tests/lddt_ref.py.  (An addition; the ABI number stays.)  DESIGN.md
+ * §3.20 states the definition.  A f64 [n, L, 3] models, B f64 [m, L, 3] natives, residue to residue, device pointers; B == NULL:
+ * A against itself (m is ignored, maskB = maskA).  maskA u8 [n, L] / maskB u8 [m, L] on the device, or NULL (all valid); a masked
+ * coordinate is never read.  `thresholds` is a HOST array of n_thresholds (1 .. ESMDIFF_LDDT_MAX_THRESHOLDS) doubles; r0 the
+ * inclusion radius; seq_sep >= 1.
+ *   pair set of native j (ordered pairs):  (a, b) with |a - b| >= seq_sep, maskB[j, a] and maskB[j, b], and
+ *                                          dn = |B[j, a] - B[j, b]| < r0 (strict)
+ *   total_res i32 [m, L] (or NULL)        the number of b with (a, b) in the set;   total i32 [m] = its sum over a
+ *   kept_res i32 [n, m, L] (or NULL)      sum over the thresholds t of the number of b with (a, b) in the set, maskA[i, a] and
+ *                                          maskA[i, b], and | |A[i, a] - A[i, b]| - dn | < t (strict): a pair whose model residue
+ *                                          is missing keeps nothing and stays in `total`;   kept i32 [n, m] = its sum over a
+ * per-residue lDDT = kept_res / (n_thresholds total_res), global lDDT = kept / (n_thresholds total): the caller divides.
+ * Distances are sqrt((dx dx + dy dy) + dz dz) in float64, correctly rounded square root, no FMA contraction.  Every element of
+ * every output that is not NULL is written; nothing has to be zeroed by the caller.  Integer sums only: two runs are bit-identical
+ * and a pair's counts do not depend on the launch.  The call synchronises `stream`.
+ * n, m < 1, L < 2, seq_sep < 1 or a threshold count outside 1 .. 8 return ESMDIFF_E_INVALID; L > ESMDIFF_LDDT_MAX_L (one model of
+ * the longest chain, 96 KiB of float64 planes, has to fit in LDS) returns ESMDIFF_E_CAPACITY, before anything is launched. */
+#define ESMDIFF_LDDT_MAX_L 4096
+#define ESMDIFF_LDDT_MAX_THRESHOLDS 8
+int esmdiff_lddt_pairs(const double* A, int32_t n, const double* B, int32_t m, int32_t L, const uint8_t* maskA,
+                       const uint8_t* maskB, double r0, const double* thresholds, int32_t n_thresholds, int32_t seq_sep,
+                       int32_t* kept, int32_t* total, int32_t* kept_res, int32_t* total_res, void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
