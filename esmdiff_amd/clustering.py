@@ -17,12 +17,13 @@ metric="lddt" (csrc/lddt.hip) needs no superposition and rests on no recalled pr
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
 from . import _native as N
-from .ensemble import _check, _dev, _lddt_device, _mask, _p, _stream
+from . import pairs
 
 CLUSTER_MAX_N = N.CLUSTER_MAX_N
 TM_NOTE = "[TMSCORE-RECALL], parity unpinned"
@@ -38,9 +39,34 @@ class Clustering:
     n_clusters: int
 
 
-def _need_gpu():
-    if not torch.cuda.is_available():
-        raise RuntimeError("esmdiff_amd.clustering needs an MI355X (gfx950); there is no CPU fallback")
+class Metric(NamedTuple):
+    """device(X, Y, mx, my) -> (n, m) on the device, Y = None: X against itself.  one_sided: device(X, Y)[i, j] is normalised by
+    Y[j] alone, and the metric is the symmetric mean of the two readings."""
+    larger_is_closer: bool
+    one_sided: bool
+    device: Callable
+
+
+def _rmsd(X, Y, mx, my, out=None):
+    return pairs.superpose(X, Y, mx, my, False, ("rmsd",), None if out is None else {"rmsd": out})["rmsd"]
+
+
+METRICS = {"rmsd": Metric(False, False, _rmsd), "tm": Metric(True, True, pairs.tm), "lddt": Metric(True, True, pairs.lddt)}
+
+
+def _rule(metric: str) -> Metric:
+    if metric not in METRICS:
+        raise ValueError(f"metric should be 'rmsd', 'tm' or 'lddt', got {metric!r}")
+    return METRICS[metric]
+
+
+def _score(rule: Metric, X, Y, mx, my, out=None) -> torch.Tensor:
+    """(n, m) on the device: the metric of every X[i] to every Y[j] (Y = None: to every X[j], in one launch); `out`: the buffer a
+    two-sided metric's launch writes into."""
+    if not rule.one_sided:
+        return rule.device(X, Y, mx, my, out)
+    s = rule.device(X, Y, mx, my)
+    return 0.5 * (s + (s if Y is None else rule.device(Y, X, my, mx)).T)
 
 
 def _check_n(n: int, what: str):
@@ -48,25 +74,8 @@ def _check_n(n: int, what: str):
         raise ValueError(f"{what}: n = {n} structures, the clustering kernel takes 1 to {CLUSTER_MAX_N} (one count per structure in LDS)")
 
 
-def _code(code: int, what: str):
-    if code != 0:
-        raise RuntimeError(f"libesmdiff_hip {what} failed ({code})")
-
-
-def _new_adj(n: int) -> torch.Tensor:
-    return torch.zeros((n, (n + 63) // 64), dtype=torch.int64, device="cuda")
-
-
-def _threshold(block: torch.Tensor, row0: int, n: int, cutoff: float, larger_is_closer: bool, adj: torch.Tensor):
-    """block f64 (rows, n) on the device: rows row0 .. of the matrix -> their bits of adj."""
-    _code(N.lib().esmdiff_cluster_threshold(_p(block), block.shape[0], row0, n, float(cutoff), int(bool(larger_is_closer)), _p(adj),
-                                            _stream()), "esmdiff_cluster_threshold")
-
-
-def _gromos(adj: torch.Tensor, n: int) -> Clustering:
-    out = torch.empty((3, n), dtype=torch.int32, device="cuda")          # labels, centres, sizes
-    k = torch.zeros(1, dtype=torch.int32, device="cuda")
-    _code(N.lib().esmdiff_cluster_gromos(_p(adj), n, _p(out), _p(out, 4 * n), _p(out, 8 * n), _p(k), _stream()), "esmdiff_cluster_gromos")
+def _gromos(adj: torch.Tensor) -> Clustering:
+    out, k = pairs.gromos(adj)
     K = int(k.item())
     labels, centres, sizes = out.cpu().numpy()
     return Clustering(labels.copy(), centres[:K].copy(), sizes[:K].copy(), K)
@@ -81,37 +90,16 @@ def cluster_matrix(d, cutoff: float, larger_is_closer: bool = False, block_rows:
         raise ValueError(f"cluster_matrix takes a square matrix, got {shape}")
     n = int(shape[0])
     _check_n(n, "cluster_matrix")
-    _need_gpu()
+    if not torch.cuda.is_available():
+        raise RuntimeError("esmdiff_amd.clustering needs an MI355X (gfx950); there is no CPU fallback")
     if not torch.is_tensor(d):
         d = np.asarray(d)
-    adj = _new_adj(n)
+    adj = pairs.adjacency(n)
     for r0 in range(0, n, max(1, int(block_rows))):
         rows = d[r0:r0 + max(1, int(block_rows))]
         block = (rows if torch.is_tensor(rows) else torch.as_tensor(np.ascontiguousarray(rows))).to(device="cuda", dtype=torch.float64)
-        _threshold(block.contiguous(), r0, n, cutoff, larger_is_closer, adj)
-    return _gromos(adj, n)
-
-
-def _tm_device(A, B, ma, mb) -> torch.Tensor:
-    n, m, L = A.shape[0], B.shape[0], A.shape[1]
-    tm = torch.empty(n, m, dtype=torch.float64, device="cuda")
-    _check(N.lib().esmdiff_tm_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), _p(tm), None, None, _stream()), "esmdiff_tm_pairs", L)
-    return tm
-
-
-def _rmsd_device(A, B, ma, mb) -> torch.Tensor:
-    n, m, L = A.shape[0], B.shape[0], A.shape[1]
-    out = torch.empty(n, m, dtype=torch.float64, device="cuda")
-    _check(N.lib().esmdiff_superpose_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), 0, _p(out), None, None, None, _stream()),
-           "esmdiff_superpose_pairs", L)
-    return out
-
-
-def _metric(metric: str) -> bool:
-    """-> larger_is_closer"""
-    if metric not in ("rmsd", "tm", "lddt"):
-        raise ValueError(f"metric should be 'rmsd', 'tm' or 'lddt', got {metric!r}")
-    return metric != "rmsd"
+        pairs.threshold(block.contiguous(), r0, cutoff, larger_is_closer, adj)
+    return _gromos(adj)
 
 
 def cluster_ensemble(samples, cutoff: float, metric: str = "rmsd", mask=None, block_rows: int = 1024) -> Clustering:
@@ -128,58 +116,38 @@ def cluster_ensemble(samples, cutoff: float, metric: str = "rmsd", mask=None, bl
     memory and has not been compared with the program.
     metric="lddt": cutoff on the symmetric mean 0.5 (l[i, j] + l[j, i]) of the CA-lDDT (ensemble.lddt_matrix, default radius and
     thresholds), larger is closer; a pair without a defined lDDT (NaN) is not a neighbour.  The same row-block path as the RMSD:
-    per block one launch for the block against all and one for all against the block, block_rows x n doubles at a time."""
-    larger = _metric(metric)
-    A = _dev(samples, "samples")
-    n, L = A.shape[:2]
+    per block one launch for the block against all and one for all against the block (a block of all rows: one launch in all)."""
+    rule = _rule(metric)
+    A = pairs.coords(samples, "samples")
+    n = A.shape[0]
     _check_n(n, "cluster_ensemble")
-    ma = _mask(A, mask)
-    adj = _new_adj(n)
-    if metric == "lddt":
-        step = max(1, min(int(block_rows), n))
-        for r0 in range(0, n, step):
-            rows = slice(r0, min(r0 + step, n))
-            Ab, mab = A[rows], None if ma is None else ma[rows]
-            block = 0.5 * (_lddt_device(Ab, A, mab, ma) + _lddt_device(A, Ab, ma, mab).T)
-            _threshold(block.contiguous(), r0, n, cutoff, True, adj)
-        return _gromos(adj, n)
-    if larger:
-        tm = _tm_device(A, A, ma, ma)
-        _threshold((0.5 * (tm + tm.T)).contiguous(), 0, n, cutoff, True, adj)
-        return _gromos(adj, n)
-    step = max(1, min(int(block_rows), n))
-    buf = torch.empty((step, n), dtype=torch.float64, device="cuda")
-    fn = N.lib().esmdiff_superpose_pairs
+    ma = pairs.valid_mask(A, mask)
+    adj = pairs.adjacency(n)
+    # tm takes no row blocks: the symmetric mean of a block needs the block against all AND all against the block, every ordered
+    # pair would be scored twice and the time double; one full n x n launch scores each once (lddt pays that: its launch is cheap)
+    step = n if metric == "tm" else max(1, min(int(block_rows), n))
+    buf = None if rule.one_sided else torch.empty((step, n), dtype=torch.float64, device="cuda")
     for r0 in range(0, n, step):
-        rows = min(step, n - r0)
-        code = fn(_p(A, r0 * L * 24), rows, _p(A), n, L, _p(ma, r0 * L), _p(ma), 0, _p(buf), None, None, None, _stream())
-        _check(code, "esmdiff_superpose_pairs", L)
-        _threshold(buf[:rows], r0, n, cutoff, False, adj)
-    return _gromos(adj, n)
-
-
-def _to_states(A: torch.Tensor, B: torch.Tensor, ma, mb, metric: str) -> torch.Tensor:
-    """(n, K) on the device: the RMSD of every A[i] to every B[k], or the symmetric mean of the two TM-scores / lDDTs."""
-    if metric == "lddt":
-        return 0.5 * (_lddt_device(A, B, ma, mb) + _lddt_device(B, A, mb, ma).T)
-    if metric == "tm":
-        return 0.5 * (_tm_device(A, B, ma, mb) + _tm_device(B, A, mb, ma).T)
-    return _rmsd_device(A, B, ma, mb)
+        r1 = min(r0 + step, n)
+        Y, my = (None, None) if r1 - r0 == n else (A, ma)   # all rows: the ensemble against itself, one launch
+        block = _score(rule, A[r0:r1], Y, None if ma is None else ma[r0:r1], my, None if buf is None else buf[:r1 - r0])
+        pairs.threshold(block.contiguous(), r0, cutoff, rule.larger_is_closer, adj)
+    return _gromos(adj)
 
 
 def centre_distances(samples, clustering: Clustering, metric: str = "rmsd", mask=None) -> np.ndarray:
     """Each structure's distance to the centre of its own cluster -> (n,): the RMSD in Angstrom (the centres themselves: 0 to
     rounding), or for metric="tm" the symmetric mean TM-score ([TMSCORE-RECALL], parity unpinned), for metric="lddt" the symmetric
     mean lDDT.  One n x K launch (two for a similarity) and a gather."""
-    _metric(metric)
-    A = _dev(samples, "samples")
+    rule = _rule(metric)
+    A = pairs.coords(samples, "samples")
     labels = np.asarray(clustering.labels)
     assert labels.shape == (A.shape[0],), f"the clustering is of {labels.shape[0]} structures, the samples are {A.shape[0]}"
-    ma = _mask(A, mask)
+    ma = pairs.valid_mask(A, mask)
     centres = torch.as_tensor(np.asarray(clustering.centres), dtype=torch.int64, device="cuda")
     C = A[centres].contiguous()
     mc = None if ma is None else ma[centres].contiguous()
-    d = _to_states(A, C, ma, mc, metric)
+    d = _score(rule, A, C, ma, mc)
     return d.gather(1, torch.as_tensor(labels, dtype=torch.int64, device="cuda")[:, None])[:, 0].cpu().numpy()
 
 
@@ -190,11 +158,11 @@ def state_populations(samples, states, cutoff=None, metric: str = "rmsd"):
     symmetric mean lDDT, nearest means largest).  With a cutoff a sample farther than it from every state (tm, lddt: below it) is
     assigned to none, -1, and the populations sum to less than one; so is a sample with no defined distance to any state (NaN).
     `distance` is to the nearest state either way."""
-    larger = _metric(metric)
-    A, S = _dev(samples, "samples"), _dev(states, "states")
+    rule = _rule(metric)
+    A, S = pairs.coords(samples, "samples"), pairs.coords(states, "states")
     assert S.shape[1] == A.shape[1], f"structures of different lengths: {A.shape[1]} and {S.shape[1]} (the correspondence is residue to residue)"
-    d = _to_states(A, S, _mask(A, None), _mask(S, None), metric)
-    K = S.shape[0]
+    d = _score(rule, A, S, pairs.valid_mask(A, None), pairs.valid_mask(S, None))
+    K, larger = S.shape[0], rule.larger_is_closer
     worst = float("-inf") if larger else float("inf")
     key = torch.where(torch.isnan(d), torch.full_like(d, worst), d)
     best = key.max(1).values if larger else key.min(1).values

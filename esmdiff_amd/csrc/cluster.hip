@@ -161,8 +161,7 @@ int esmdiff_cluster_threshold(const double* d, int32_t rows, int32_t row0, int32
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(cluster_threshold_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d, rows, row0, n, W, cutoff,
                      larger_is_closer ? 1 : 0, (u64*)adj);
-  if (hipGetLastError() != hipSuccess) return ESMDIFF_E_HIP;
-  return hipStreamSynchronize(st) == hipSuccess ? 0 : ESMDIFF_E_HIP;
+  return finish_entry(st);
 }
 
 int esmdiff_cluster_gromos(uint64_t* adj, int32_t n, int32_t* labels, int32_t* centres, int32_t* sizes, int32_t* n_clusters,
@@ -177,8 +176,7 @@ int esmdiff_cluster_gromos(uint64_t* adj, int32_t n, int32_t* labels, int32_t* c
   if (hipGetLastError() != hipSuccess) return ESMDIFF_E_HIP;
   hipLaunchKernelGGL(cluster_gromos_kernel, dim3(1), dim3(LOOP_THREADS), (size_t)lds, st, (const u64*)adj, n, W, labels, centres,
                      sizes, n_clusters);
-  if (hipGetLastError() != hipSuccess) return ESMDIFF_E_HIP;
-  return hipStreamSynchronize(st) == hipSuccess ? 0 : ESMDIFF_E_HIP;
+  return finish_entry(st);
 }
 
 }  // extern "C"

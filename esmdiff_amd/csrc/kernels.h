@@ -1,5 +1,5 @@
 // kernels.h — internal launch functions of libesmdiff_hip.so (gfx950 only).
-// Every function enqueues on `stream` and returns the hipError_t of the launch.
+// Every launch function enqueues on `stream` and returns the hipError_t of the launch; finish_entry below is the one that waits.
 #pragma once
 #include <stdlib.h>
 #include <hip/hip_runtime.h>
@@ -24,5 +24,11 @@ struct EdGemmPartials {
   int S;
   int64_t stride;
 };
+
+// The tail of a C entry that returns when its work is done: the last launch's error, then the stream's -> 0 / ESMDIFF_E_HIP.
+inline int finish_entry(hipStream_t st) {
+  if (hipGetLastError() != hipSuccess) return ESMDIFF_E_HIP;
+  return hipStreamSynchronize(st) == hipSuccess ? 0 : ESMDIFF_E_HIP;
+}
 
 #include "kernels_ns.inc"

@@ -18,6 +18,7 @@
 // associative, two runs are bit-identical.  The per-residue outputs have exactly one writer each.
 #include <math.h>
 
+#include "ed_wave.h"
 #include "kernels.h"
 
 namespace ed {
@@ -39,12 +40,6 @@ struct LddtArgs {
   double thr[ESMDIFF_LDDT_MAX_THRESHOLDS];
   int n, m, L, tile, tiles, seq_sep, n_thr;
 };
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;
-}
 
 __device__ __forceinline__ double dist(double dx, double dy, double dz) { return sqrt((dx * dx + dy * dy) + dz * dz); }
 
@@ -192,8 +187,7 @@ int esmdiff_lddt_pairs(const double* A, int32_t n, const double* B, int32_t m, i
   const auto kernel = n_thresholds == 4 ? lddt_pairs_kernel<4> : lddt_pairs_kernel<0>;
   if (ensure_dynamic_lds((const void*)kernel, lds) != hipSuccess) return ESMDIFF_E_HIP;
   hipLaunchKernelGGL(kernel, dim3((unsigned)groups, chunks), dim3(LDDT_THREADS), (size_t)lds, st, p);
-  if (hipGetLastError() != hipSuccess) return ESMDIFF_E_HIP;
-  return hipStreamSynchronize(st) == hipSuccess ? 0 : ESMDIFF_E_HIP;
+  return finish_entry(st);
 }
 
 }  // extern "C"

@@ -228,7 +228,7 @@ int esmdiff_metrics_pwd(const double* ca, int32_t n, int32_t L, int32_t pwd_offs
   if (int r = pairs_to_device(s, L, pwd_offset, &row, &col, &D)) return r;
   if (D == 0) return ESMDIFF_E_INVALID;
   hipLaunchKernelGGL(pwd_kernel, dim3((D + 255) / 256, n), dim3(256), 0, st, ca, row, col, L, D, out);
-  return hipStreamSynchronize(st) == hipSuccess ? 0 : ESMDIFF_E_HIP;  // row / col are freed on return
+  return finish_entry(st);  // row / col are freed on return
 }
 
 int esmdiff_metrics_js_columns(const double* x_model, int32_t n_model, const double* w_model, const double* x_ref,

@@ -14,6 +14,7 @@
 // two runs are bit-identical, and a pair's result does not depend on which other pairs are in the launch.
 #include <math.h>
 
+#include "ed_wave.h"
 #include "kernels.h"
 
 namespace ed {
@@ -22,18 +23,6 @@ namespace {
 constexpr int TM_MAX_L = ESMDIFF_TM_MAX_L;
 constexpr int TM_MAX_LENGTHS = 12;       // La, La/2, ... > 4, then min(4, La): at most 10 entries for La <= 1280
 constexpr int TM_MAX_WIDEN = 16384;      // 0.5 A steps: 8 km; only non-finite coordinates get there
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;
-}
 
 // One rotation of the one-sided (Hestenes) Jacobi SVD: columns p and q of G = H V are rotated until orthogonal, V follows.
 template <int P, int Q>
@@ -434,8 +423,7 @@ int esmdiff_superpose_pairs(const double* A, int32_t n, const double* B, int32_t
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(superpose_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A, B, maskA, maskB, n, m, L,
                      allow_reflection ? 1 : 0, rmsd, sd, R, t);
-  if (hipGetLastError() != hipSuccess) return ESMDIFF_E_HIP;
-  return hipStreamSynchronize(st) == hipSuccess ? 0 : ESMDIFF_E_HIP;
+  return finish_entry(st);
 }
 
 int esmdiff_tm_pairs(const double* A, int32_t n, const double* B, int32_t m, int32_t L, const uint8_t* maskA,
@@ -449,8 +437,7 @@ int esmdiff_tm_pairs(const double* A, int32_t n, const double* B, int32_t m, int
   const int Lp = (L + 63) & ~63;
   hipLaunchKernelGGL(tm_pairs_kernel, dim3((unsigned)blocks), dim3(256), (size_t)6 * Lp * sizeof(double), st, A, B, maskA, maskB,
                      m, L, tm, R, t);
-  if (hipGetLastError() != hipSuccess) return ESMDIFF_E_HIP;
-  return hipStreamSynchronize(st) == hipSuccess ? 0 : ESMDIFF_E_HIP;
+  return finish_entry(st);
 }
 
 }  // extern "C"

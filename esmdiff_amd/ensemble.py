@@ -21,85 +21,11 @@ pdbio.load_coords).  Residues with NaN coordinates are masked; `mask_*` argument
 floats on the host."""
 from __future__ import annotations
 
-import ctypes
-import os
-from pathlib import Path
-from typing import Optional
-
 import numpy as np
 import torch
 
-from . import _native as N
-
-
-def _coords(x) -> np.ndarray:
-    if isinstance(x, (str, os.PathLike)):
-        from .pdbio import load_coords
-        return load_coords(Path(x), max_n_model=None, verbose=False)
-    return x
-
-
-def _dev(x, what: str = "coords") -> torch.Tensor:
-    if not torch.cuda.is_available():
-        raise RuntimeError("esmdiff_amd.ensemble needs an MI355X (gfx950); there is no CPU fallback")
-    x = _coords(x)
-    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-    if t.dim() == 2:
-        t = t[None]
-    if t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] == 0 or t.shape[1] == 0:
-        raise AssertionError(f"{what} should be (n, L, 3) CA coordinates, got {tuple(t.shape)}")
-    return t.to(device="cuda", dtype=torch.float64).contiguous()
-
-
-def _mask(t: torch.Tensor, mask) -> Optional[torch.Tensor]:
-    """u8 (n, L): resolved (no NaN coordinate) and not masked by the caller; None when every residue is valid."""
-    ok = ~torch.isnan(t).any(-1)
-    if mask is not None:
-        m = torch.as_tensor(np.asarray(mask) if not torch.is_tensor(mask) else mask).to("cuda").bool()
-        if m.dim() == 1:
-            m = m[None]
-        assert m.shape == ok.shape, f"mask {tuple(m.shape)} does not match the coordinates {tuple(ok.shape)}"
-        ok = ok & m
-    return None if bool(ok.all()) else ok.to(torch.uint8).contiguous()
-
-
-def _p(t: Optional[torch.Tensor], offset: int = 0):
-    return ctypes.c_void_p(0 if t is None else t.data_ptr() + offset)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _check(code: int, what: str, L: int):
-    if code == -5:
-        raise RuntimeError(f"{what}: L = {L} is beyond the kernel's limit ({N.TM_MAX_L} residues: both structures of a pair are "
-                           f"staged in LDS); there is no slow path")
-    if code != 0:
-        raise RuntimeError(f"libesmdiff_hip {what} failed ({code})")
-
-
-def _pair_args(a, b, mask_a, mask_b):
-    A = _dev(a)
-    ma = _mask(A, mask_a)
-    if b is None:
-        assert mask_b is None, "mask_b without b"
-        return A, None, ma, None, A.shape[0], A.shape[0]
-    B = _dev(b)
-    assert B.shape[1] == A.shape[1], f"structures of different lengths: {A.shape[1]} and {B.shape[1]} (the correspondence is residue to residue)"
-    return A, B, ma, _mask(B, mask_b), A.shape[0], B.shape[0]
-
-
-def _superpose(a, b, mask_a, mask_b, reflection: bool, want):
-    """One esmdiff_superpose_pairs launch -> {name: device tensor} for the names in `want` (rmsd, sd, R, t)."""
-    A, B, ma, mb, n, m = _pair_args(a, b, mask_a, mask_b)
-    L = A.shape[1]
-    shapes = {"rmsd": (n, m), "sd": (n, m, L), "R": (n, m, 3, 3), "t": (n, m, 3)}
-    out = {k: torch.empty(shapes[k], dtype=torch.float64, device="cuda") for k in want}
-    code = N.lib().esmdiff_superpose_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), int(bool(reflection)), _p(out.get("rmsd")),
-                                           _p(out.get("sd")), _p(out.get("R")), _p(out.get("t")), _stream())
-    _check(code, "esmdiff_superpose_pairs", L)
-    return out
+from . import pairs
+from .pairs import LDDT_R0, LDDT_THRESHOLDS  # noqa: F401  (the defaults of the lDDT functions below)
 
 
 def squared_deviation(xyz1, xyz2, reduction: str = "none"):
@@ -109,18 +35,15 @@ def squared_deviation(xyz1, xyz2, reduction: str = "none"):
     if reduction not in ("none", "rmsd"):
         raise NotImplementedError(reduction)
     as_np = not torch.is_tensor(xyz1)
-    A, B = _dev(xyz1, "xyz1"), _dev(xyz2, "xyz2")
+    A, B = pairs.coords(xyz1, "xyz1"), pairs.coords(xyz2, "xyz2")
     assert A.shape == B.shape, f"xyz1 {tuple(A.shape)} and xyz2 {tuple(B.shape)} differ"
     assert A.shape[1] > 1                                   # geo_utils.py:108
     nb, L = A.shape[:2]
-    out = torch.empty((nb, L) if reduction == "none" else (nb,), dtype=torch.float64, device="cuda")
-    fn, row = N.lib().esmdiff_superpose_pairs, L * 3 * 8
+    name = "sd" if reduction == "none" else "rmsd"
+    out = torch.empty((nb, 1, L) if reduction == "none" else (nb, 1), dtype=torch.float64, device="cuda")
     for k in range(nb):                                     # the reference's shape is pair k with pair k, not all against all
-        if reduction == "none":
-            code = fn(_p(A, k * row), 1, _p(B, k * row), 1, L, None, None, 1, None, _p(out, k * L * 8), None, None, _stream())
-        else:
-            code = fn(_p(A, k * row), 1, _p(B, k * row), 1, L, None, None, 1, _p(out, k * 8), None, None, None, _stream())
-        _check(code, "esmdiff_superpose_pairs", L)
+        pairs.superpose(A[k:k + 1], B[k:k + 1], None, None, True, (name,), {name: out[k:k + 1]})
+    out = out.squeeze(1)
     if as_np:
         return out.cpu().numpy()
     return out.to(xyz1.device)
@@ -129,12 +52,12 @@ def squared_deviation(xyz1, xyz2, reduction: str = "none"):
 def pairwise_rmsd(a, b=None, mask_a=None, mask_b=None, reflection: bool = False) -> np.ndarray:
     """RMSD after least-squares superposition of every a[i] onto every b[j] (b = None: a against itself) -> (n, m).
     reflection=False: proper rotations (scipy's align_vectors, the RMSD TMscore prints); True: the reference's geo_utils rule."""
-    return _superpose(a, b, mask_a, mask_b, reflection, ("rmsd",))["rmsd"].cpu().numpy()
+    return pairs.superpose(*pairs.pair_args(a, b, mask_a, mask_b), reflection, ("rmsd",))["rmsd"].cpu().numpy()
 
 
 def superposition(a, b=None, mask_a=None, mask_b=None, reflection: bool = False):
     """-> (R (n, m, 3, 3), t (n, m, 3)) with R a[i] + t ~ b[j]."""
-    out = _superpose(a, b, mask_a, mask_b, reflection, ("R", "t"))
+    out = pairs.superpose(*pairs.pair_args(a, b, mask_a, mask_b), reflection, ("R", "t"))
     return out["R"].cpu().numpy(), out["t"].cpu().numpy()
 
 
@@ -144,12 +67,8 @@ def aligned_deviation(a, b=None, mask_a=None, mask_b=None) -> np.ndarray:
     rotation only (scipy's align_vectors, proper) on the residues resolved in both.  With equal masks that is the Kabsch
     superposition; with different masks it is not, and it is reproduced as it stands: a rotation-only fit about the origin is the
     Kabsch fit of the point sets doubled with their mirror images through the origin (centroids 0, the same covariance twice),
-    so the kernel sees [x, -x] of length 2 L."""
-    A = _dev(a)
-    ma = _mask(A, mask_a)
-    B, mb = (A, ma) if b is None else (_dev(b), None)
-    if b is not None:
-        mb = _mask(B, mask_b)
+    so the kernel sees [x, -x] of length 2 L.  As everywhere here, unequal lengths of a and b and a mask_b without b are refused."""
+    A, B, ma, mb = pairs.pair_args(a, b, mask_a, mask_b)
     L = A.shape[1]
 
     def doubled(x, m):
@@ -159,11 +78,8 @@ def aligned_deviation(a, b=None, mask_a=None, mask_b=None) -> np.ndarray:
         return torch.cat([xc, -xc], dim=1).contiguous(), None if m is None else torch.cat([m, m], dim=1).contiguous()
 
     A2, ma2 = doubled(A, ma)
-    B2, mb2 = (A2, ma2) if b is None else doubled(B, mb)
-    n, m = A2.shape[0], B2.shape[0]
-    sd = torch.empty(n, m, 2 * L, dtype=torch.float64, device="cuda")
-    code = N.lib().esmdiff_superpose_pairs(_p(A2), n, _p(B2), m, 2 * L, _p(ma2), _p(mb2), 0, None, _p(sd), None, None, _stream())
-    _check(code, "esmdiff_superpose_pairs", L)
+    B2, mb2 = (None, None) if B is None else doubled(B, mb)
+    sd = pairs.superpose(A2, B2, ma2, mb2, False, ("sd",))["sd"]
     return torch.sqrt(sd[..., :L]).cpu().numpy()
 
 
@@ -171,15 +87,10 @@ def tm_matrix(models, natives=None, mask_models=None, mask_natives=None, return_
     """TM-score of every model against every native (natives = None: the models against themselves) -> (n, m), normalised by
     the native's number of valid residues.  [TMSCORE-RECALL], parity unpinned (module docstring).  return_transform: also R, t of
     the best superposition found (R model + t ~ native)."""
-    A, B, ma, mb, n, m = _pair_args(models, natives, mask_models, mask_natives)
-    L = A.shape[1]
-    tm = torch.empty(n, m, dtype=torch.float64, device="cuda")
-    R = torch.empty(n, m, 3, 3, dtype=torch.float64, device="cuda") if return_transform else None
-    t = torch.empty(n, m, 3, dtype=torch.float64, device="cuda") if return_transform else None
-    _check(N.lib().esmdiff_tm_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), _p(tm), _p(R), _p(t), _stream()), "esmdiff_tm_pairs", L)
+    out = pairs.tm(*pairs.pair_args(models, natives, mask_models, mask_natives), transform=return_transform)
     if return_transform:
-        return tm.cpu().numpy(), R.cpu().numpy(), t.cpu().numpy()
-    return tm.cpu().numpy()
+        return tuple(x.cpu().numpy() for x in out)
+    return out.cpu().numpy()
 
 
 def tm_score(model, native, mask_model=None, mask_native=None) -> float:
@@ -190,7 +101,7 @@ def tm_score(model, native, mask_model=None, mask_native=None) -> float:
 # ---- the reference's ensemble functions (tm_utils.py:62-154) -----------------------------------------------------------
 def tm_ensemble(samples, t1, t2) -> float:
     """tm_utils.py:62-86: 0.5 max_i TM(sample_i, t1) + 0.5 max_i TM(sample_i, t2)."""
-    natives = torch.cat([_dev(t1, "t1")[:1], _dev(t2, "t2")[:1]], dim=0)
+    natives = torch.cat([pairs.coords(t1, "t1")[:1], pairs.coords(t2, "t2")[:1]], dim=0)
     tm = tm_matrix(samples, natives)
     return float(0.5 * tm[:, 0].max() + 0.5 * tm[:, 1].max())
 
@@ -199,8 +110,8 @@ def tm_n_ensemble(samples, natives, max_n_model: int = 100, rng=0, verbose: bool
     """tm_utils.py:88-135: for every native the best TM-score and the best RMSD (the proper-rotation RMSD TMscore prints) over the
     samples -> (best_tm_list, best_rmsd_list).  More than max_n_model samples are down-sampled without replacement from `rng`
     (a numpy Generator or a seed; the reference draws from the global np.random)."""
-    S = _dev(samples, "samples")
-    K = _dev(natives, "natives")
+    S = pairs.coords(samples, "samples")
+    K = pairs.coords(natives, "natives")
     if S.shape[0] > max_n_model:
         gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
         keep = gen.choice(S.shape[0], max_n_model, replace=False)
@@ -232,8 +143,8 @@ def apo_report(samples, struct1, struct2, mask1=None, mask2=None) -> dict:
     sample pairs j < k, :252-255, :262), tmpair (mean of both normalisations of the two states, :267-272), rmsd (per-residue
     distance between the states after get_structures, :234-235) and rmsf (sqrt of the mean over sample pairs of the squared
     aligned deviation, :256-260)."""
-    S = _dev(samples, "samples")
-    s1, s2 = _dev(struct1, "struct1")[:1], _dev(struct2, "struct2")[:1]
+    S = pairs.coords(samples, "samples")
+    s1, s2 = pairs.coords(struct1, "struct1")[:1], pairs.coords(struct2, "struct2")[:1]
     states = torch.cat([s1, s2], dim=0)
     ms = None
     if mask1 is not None or mask2 is not None:
@@ -255,40 +166,6 @@ def apo_report(samples, struct1, struct2, mask1=None, mask2=None) -> dict:
 
 
 # ---- lDDT: the superposition-free score (csrc/lddt.hip) ------------------------------------------------------------------
-LDDT_R0 = 15.0
-LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
-
-
-def _lddt_counts(A, B, ma, mb, n: int, m: int, per_residue: bool = False, r0: float = LDDT_R0, thresholds=LDDT_THRESHOLDS,
-                 seq_sep: int = 1):
-    """One esmdiff_lddt_pairs launch on device tensors (B None: A against itself) -> int32 device tensors kept (n, m),
-    total (m,), and with per_residue kept_res (n, m, L) and total_res (m, L) (else None, and never allocated)."""
-    L = A.shape[1]
-    thr = [float(t) for t in thresholds]
-    kept = torch.empty((n, m), dtype=torch.int32, device="cuda")
-    total = torch.empty((m,), dtype=torch.int32, device="cuda")
-    kept_res = torch.empty((n, m, L), dtype=torch.int32, device="cuda") if per_residue else None
-    total_res = torch.empty((m, L), dtype=torch.int32, device="cuda") if per_residue else None
-    code = N.lib().esmdiff_lddt_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), float(r0), (ctypes.c_double * len(thr))(*thr), len(thr),
-                                      int(seq_sep), _p(kept), _p(total), _p(kept_res), _p(total_res), _stream())
-    if code == -5:
-        raise RuntimeError(f"esmdiff_lddt_pairs: L = {L} is beyond the kernel's limit ({N.LDDT_MAX_L} residues: a model is staged in "
-                           f"LDS); there is no slow path")
-    if code == -1:
-        raise RuntimeError(f"esmdiff_lddt_pairs: invalid argument: L = {L} (at least 2), seq_sep = {seq_sep} (at least 1), "
-                           f"{len(thr)} thresholds (1 to {N.LDDT_MAX_THRESHOLDS})")
-    if code != 0:
-        raise RuntimeError(f"libesmdiff_hip esmdiff_lddt_pairs failed ({code})")
-    return kept, total, kept_res, total_res
-
-
-def _lddt_device(A, B, ma, mb, r0: float = LDDT_R0, thresholds=LDDT_THRESHOLDS, seq_sep: int = 1) -> torch.Tensor:
-    """lDDT (n, m) float64 on the device: kept / (n_thresholds total), NaN where the native has no pair."""
-    n, m = A.shape[0], (A if B is None else B).shape[0]
-    kept, total, _, _ = _lddt_counts(A, B, ma, mb, n, m, False, r0, thresholds, seq_sep)
-    return kept.to(torch.float64) / (len(thresholds) * total).to(torch.float64)[None]
-
-
 def lddt_matrix(models, natives=None, mask_models=None, mask_natives=None, per_residue: bool = False, r0: float = LDDT_R0,
                 thresholds=LDDT_THRESHOLDS, seq_sep: int = 1):
     """CA-lDDT (Mariani et al. 2013) of every model against every native (natives = None: the models against themselves) -> (n, m)
@@ -297,8 +174,8 @@ def lddt_matrix(models, natives=None, mask_models=None, mask_natives=None, per_r
     missing keeps nothing); the score is kept / (n_thresholds * pairs), pooled over the chain.  per_residue: also the (n, m, L) array
     of the same ratio per residue a.  NaN where a native (a residue) has no pair.  The device returns the integer counts
     (csrc/lddt.hip, equal to tests/lddt_ref.py's); the one division is done here."""
-    A, B, ma, mb, n, m = _pair_args(models, natives, mask_models, mask_natives)
-    kept, total, kept_res, total_res = _lddt_counts(A, B, ma, mb, n, m, per_residue, r0, thresholds, seq_sep)
+    kept, total, kept_res, total_res = pairs.lddt_counts(*pairs.pair_args(models, natives, mask_models, mask_natives), per_residue, r0,
+                                                         thresholds, seq_sep)
     nt = len(thresholds)
     with np.errstate(invalid="ignore", divide="ignore"):
         score = kept.cpu().numpy() / (nt * total.cpu().numpy())[None]

@@ -1,0 +1,154 @@
+"""The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip and
+csrc/cluster.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+on the device out, no host transfer.  esmdiff_amd/ensemble.py and esmdiff_amd/clustering.py are the host-facing layers above it.
+Row blocks are contiguous slices (A[r0:r1]): a slice carries its own pointer, dtype and shape.  There is no CPU fallback."""
+from __future__ import annotations
+
+import ctypes
+import os
+from pathlib import Path
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _native as N
+
+LDDT_R0 = 15.0
+LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
+
+
+def coords(x, what: str = "coords") -> torch.Tensor:
+    """A path (pdbio.load_coords), an array or a tensor -> float64 (n, L, 3) on the device."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("esmdiff_amd.ensemble needs an MI355X (gfx950); there is no CPU fallback")
+    if isinstance(x, (str, os.PathLike)):
+        from .pdbio import load_coords
+        x = load_coords(Path(x), max_n_model=None, verbose=False)
+    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+    if t.dim() == 2:
+        t = t[None]
+    if t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] == 0 or t.shape[1] == 0:
+        raise AssertionError(f"{what} should be (n, L, 3) CA coordinates, got {tuple(t.shape)}")
+    return t.to(device="cuda", dtype=torch.float64).contiguous()
+
+
+def valid_mask(t: torch.Tensor, mask) -> Optional[torch.Tensor]:
+    """u8 (n, L): resolved (no NaN coordinate) and not masked by the caller; None when every residue is valid."""
+    ok = ~torch.isnan(t).any(-1)
+    if mask is not None:
+        m = torch.as_tensor(np.asarray(mask) if not torch.is_tensor(mask) else mask).to("cuda").bool()
+        if m.dim() == 1:
+            m = m[None]
+        assert m.shape == ok.shape, f"mask {tuple(m.shape)} does not match the coordinates {tuple(ok.shape)}"
+        ok = ok & m
+    return None if bool(ok.all()) else ok.to(torch.uint8).contiguous()
+
+
+def pair_args(a, b, mask_a, mask_b):
+    """-> A, B, ma, mb as every function below takes them; b = None: B and mb are None, a against itself."""
+    A = coords(a)
+    ma = valid_mask(A, mask_a)
+    if b is None:
+        assert mask_b is None, "mask_b without b"
+        return A, None, ma, None
+    B = coords(b)
+    assert B.shape[1] == A.shape[1], f"structures of different lengths: {A.shape[1]} and {B.shape[1]} (the correspondence is residue to residue)"
+    return A, B, ma, valid_mask(B, mask_b)
+
+
+def _p(t: Optional[torch.Tensor]):
+    assert t is None or t.is_contiguous(), "a row block should be a contiguous slice"
+    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _sizes(A: torch.Tensor, B: Optional[torch.Tensor]):
+    assert B is None or B.shape[1:] == A.shape[1:], f"structures of different lengths: {A.shape[1]} and {B.shape[1]}"
+    return A.shape[0], (A if B is None else B).shape[0], A.shape[1]
+
+
+def _new(shape, dtype=torch.float64) -> torch.Tensor:
+    return torch.empty(shape, dtype=dtype, device="cuda")
+
+
+def _check(entry: str, code: int, capacity=None, invalid=None):
+    """An entry's return code -> RuntimeError; capacity / invalid: what -5 / -1 mean for that entry, functions called only then."""
+    if code != 0:
+        text = {-5: capacity, -1: invalid}.get(code)
+        raise RuntimeError(text() if text else f"libesmdiff_hip {entry} failed ({code})")
+
+
+def superpose(A, B, ma, mb, reflection: bool, want, out=None) -> dict:
+    """One esmdiff_superpose_pairs launch -> {name: tensor} for the names in `want`: rmsd (n, m), sd (n, m, L), R (n, m, 3, 3),
+    t (n, m, 3).  out: {name: tensor} to write into instead of allocating (a caller's row-block buffer)."""
+    n, m, L = _sizes(A, B)
+    shapes = {"rmsd": (n, m), "sd": (n, m, L), "R": (n, m, 3, 3), "t": (n, m, 3)}
+    res = {k: out[k] if out and k in out else _new(shapes[k]) for k in want}
+    assert all(tuple(v.shape) == shapes[k] and v.dtype == torch.float64 for k, v in res.items()), f"the launch writes f64 {shapes}"
+    code = N.lib().esmdiff_superpose_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), int(bool(reflection)), _p(res.get("rmsd")),
+                                           _p(res.get("sd")), _p(res.get("R")), _p(res.get("t")), _stream())
+    _check("esmdiff_superpose_pairs", code, capacity=lambda: f"esmdiff_superpose_pairs: {n} x {m} pairs are more than one launch "
+                                                             f"takes (2^31 - 1 workgroups of 4 pairs); pass the rows in blocks")
+    return res
+
+
+def tm(A, B, ma, mb, transform: bool = False):
+    """One esmdiff_tm_pairs launch -> tm (n, m), normalised by B's valid residues; transform: (tm, R (n, m, 3, 3), t (n, m, 3))."""
+    n, m, L = _sizes(A, B)
+    score = _new((n, m))
+    R, t = (_new((n, m, 3, 3)), _new((n, m, 3))) if transform else (None, None)
+    code = N.lib().esmdiff_tm_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), _p(score), _p(R), _p(t), _stream())
+    _check("esmdiff_tm_pairs", code, capacity=lambda: f"esmdiff_tm_pairs: L = {L} is beyond the kernel's limit ({N.TM_MAX_L} "
+                                                      f"residues: both structures of a pair are staged in LDS); there is no slow path")
+    return (score, R, t) if transform else score
+
+
+def lddt_counts(A, B, ma, mb, per_residue: bool = False, r0: float = LDDT_R0, thresholds=LDDT_THRESHOLDS, seq_sep: int = 1):
+    """One esmdiff_lddt_pairs launch -> int32 tensors kept (n, m), total (m,), and with per_residue kept_res (n, m, L) and
+    total_res (m, L) (else None, and never allocated)."""
+    n, m, L = _sizes(A, B)
+    thr = [float(t) for t in thresholds]
+    kept, total = _new((n, m), torch.int32), _new((m,), torch.int32)
+    kept_res, total_res = (_new((n, m, L), torch.int32), _new((m, L), torch.int32)) if per_residue else (None, None)
+    code = N.lib().esmdiff_lddt_pairs(_p(A), n, _p(B), m, L, _p(ma), _p(mb), float(r0), (ctypes.c_double * len(thr))(*thr), len(thr),
+                                      int(seq_sep), _p(kept), _p(total), _p(kept_res), _p(total_res), _stream())
+    _check("esmdiff_lddt_pairs", code,
+           capacity=lambda: f"esmdiff_lddt_pairs: L = {L} is beyond the kernel's limit ({N.LDDT_MAX_L} residues: a model is staged "
+                            f"in LDS); there is no slow path",
+           invalid=lambda: f"esmdiff_lddt_pairs: invalid argument: L = {L} (at least 2), seq_sep = {seq_sep} (at least 1), "
+                           f"{len(thr)} thresholds (1 to {N.LDDT_MAX_THRESHOLDS})")
+    return kept, total, kept_res, total_res
+
+
+def lddt(A, B, ma, mb, r0: float = LDDT_R0, thresholds=LDDT_THRESHOLDS, seq_sep: int = 1) -> torch.Tensor:
+    """lDDT (n, m) float64: kept / (n_thresholds total), NaN where the native has no pair."""
+    kept, total, _, _ = lddt_counts(A, B, ma, mb, False, r0, thresholds, seq_sep)
+    return kept.to(torch.float64) / (len(thresholds) * total).to(torch.float64)[None]
+
+
+def adjacency(n: int) -> torch.Tensor:
+    """The empty neighbour relation of n structures: one bit per pair, int64 (n, ceil(n / 64))."""
+    return torch.zeros((n, (n + 63) // 64), dtype=torch.int64, device="cuda")
+
+
+def threshold(block: torch.Tensor, row0: int, cutoff: float, larger_is_closer: bool, adj: torch.Tensor):
+    """block f64 (rows, n): rows row0 .. of the n x n matrix -> their bits of adj (esmdiff_cluster_threshold)."""
+    rows, n = block.shape
+    assert block.dtype == torch.float64 and adj.dtype == torch.int64 and tuple(adj.shape) == (n, (n + 63) // 64)
+    _check("esmdiff_cluster_threshold", N.lib().esmdiff_cluster_threshold(_p(block), rows, row0, n, float(cutoff),
+                                                                          int(bool(larger_is_closer)), _p(adj), _stream()))
+
+
+def gromos(adj: torch.Tensor):
+    """esmdiff_cluster_gromos on the relation (symmetrised in place) -> int32 out (3, n): labels, centres, sizes, the last two
+    filled up to the number of clusters, and that number k (1,)."""
+    n = adj.shape[0]
+    assert adj.dtype == torch.int64 and tuple(adj.shape) == (n, (n + 63) // 64)
+    out, k = _new((3, n), torch.int32), _new((1,), torch.int32)             # the kernel writes k whatever it finds
+    code = N.lib().esmdiff_cluster_gromos(_p(adj), n, _p(out[0]), _p(out[1]), _p(out[2]), _p(k), _stream())
+    _check("esmdiff_cluster_gromos", code)
+    return out, k

@@ -195,6 +195,27 @@ def test_cluster_ensemble_recovers_three_states(cl, three_states):
     _same(cl.cluster_ensemble(Sn, CUTOFF), (got.labels, got.centres, got.sizes, 3))
 
 
+@pytest.mark.parametrize("metric", ["rmsd", "tm", "lddt"])
+def test_row_blocks_of_every_metric_equal_the_full_matrix(cl, metric):
+    """n = 7, L = 12: the smallest ensemble with a ragged last block at block_rows = 3; a NaN residue in row 0 keeps a mask live.
+    The cutoff is the median entry of the metric's own matrix; seed 5 was chosen on the CPU (tests/ensemble_ref.py,
+    tests/lddt_ref.py, tests/cluster_ref.py) so that every metric finds more than one cluster and fewer than seven."""
+    from esmdiff_amd import ensemble
+    S = E.ensemble(np.random.default_rng(5), 7, 12)
+    S[0, 4] = np.nan
+    d = {"rmsd": ensemble.pairwise_rmsd, "tm": ensemble.tm_matrix, "lddt": ensemble.lddt_matrix}[metric](S)
+    if metric != "rmsd":
+        d = 0.5 * (d + d.T)
+    cutoff = float(np.median(d[np.triu_indices(7, 1)]))
+    from_matrix = cl.cluster_matrix(d, cutoff, larger_is_closer=metric != "rmsd")
+    assert 1 < from_matrix.n_clusters < 7
+    whole = cl.cluster_ensemble(S, cutoff, metric=metric, block_rows=1024)
+    for block_rows in (1, 3, 7, 1024):
+        got = cl.cluster_ensemble(S, cutoff, metric=metric, block_rows=block_rows)
+        for want in (whole, from_matrix):
+            _same(got, (want.labels, want.centres, want.sizes, want.n_clusters), f"{metric} block_rows={block_rows}")
+
+
 # ---- 7. distances to centres and to given states ----------------------------------------------------------------------------
 def test_centre_distances_and_state_populations(cl, three_states):
     from esmdiff_amd import ensemble

@@ -195,8 +195,10 @@ def test_bit_identical_runs_and_launch_independence(ens):
     ma[0] = True
     tm1, tm2 = ens.tm_matrix(A, mask_models=ma), ens.tm_matrix(A, mask_models=ma)
     assert np.array_equal(tm1, tm2)
-    out1 = ens._superpose(A, None, ma, None, False, ("rmsd", "sd", "R", "t"))
-    out2 = ens._superpose(A, None, ma, None, False, ("rmsd", "sd", "R", "t"))
+    from esmdiff_amd import pairs
+    args = pairs.pair_args(A, None, ma, None)
+    out1 = pairs.superpose(*args, False, ("rmsd", "sd", "R", "t"))
+    out2 = pairs.superpose(*args, False, ("rmsd", "sd", "R", "t"))
     for k in out1:
         assert np.array_equal(out1[k].cpu().numpy(), out2[k].cpu().numpy(), equal_nan=True), k
     tm, rmsd = ens.tm_matrix(A), ens.pairwise_rmsd(A)

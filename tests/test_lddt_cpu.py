@@ -121,7 +121,7 @@ def test_read_pdb_bfactors(tmp_path):
 
 def test_metric_and_parsers_know_lddt():
     from esmdiff_amd import analyze_ensemble, cluster_ensemble, clustering
-    assert clustering._metric("lddt") is True and clustering._metric("rmsd") is False
+    assert clustering.METRICS["lddt"].larger_is_closer is True and clustering.METRICS["rmsd"].larger_is_closer is False
     a = cluster_ensemble.parser().parse_args(["--samples", "x.pdb", "--cutoff", "0.7", "--output", "o", "--metric", "lddt"])
     assert a.metric == "lddt"
     assert "--lddt" in analyze_ensemble.__doc__

@@ -7,15 +7,15 @@
 The ensemble: `states` independent random-walk CA chains, every member one of them (uniformly drawn) plus Gaussian noise, rigidly
 moved.  Per n:
   call      wall clock of cluster_ensemble, numpy in / Clustering out (upload, the block loop, the clustering loop, download);
-  legs      the same block loop written out on device tensors, HIP events around each C-ABI call (the entries synchronise the
-            stream themselves): all-pairs (esmdiff_superpose_pairs per row block), threshold (esmdiff_cluster_threshold per row
-            block), loop (esmdiff_cluster_gromos: the symmetrisation and the persistent clustering kernel);
+  legs      the same block loop written out on device tensors, HIP events around each esmdiff_amd.pairs call: one C-ABI call (the
+            entries synchronise the stream themselves) and, for the loop leg, the allocation of its two outputs; no other launch.
+            all-pairs (esmdiff_superpose_pairs per row block), threshold (esmdiff_cluster_threshold per row block), loop
+            (esmdiff_cluster_gromos: the symmetrisation and the persistent clustering kernel);
   singletons the loop leg again on the relation of a cutoff below every distance: K = n clusters, the most iterations the loop
             kernel can run;
   host      for n <= host_max_n: the naive NumPy restatement of the test suite (tests/cluster_ref.py) on the matrix
             ensemble.pairwise_rmsd returns, timed on this machine's host, and compared with the device's result."""
 import argparse
-import ctypes
 import json
 import statistics
 import sys
@@ -27,7 +27,7 @@ import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-from esmdiff_amd import _native as N, clustering, ensemble  # noqa: E402
+from esmdiff_amd import clustering, ensemble, pairs  # noqa: E402
 from tests import cluster_ref as C, ensemble_ref as E  # noqa: E402
 
 
@@ -38,31 +38,27 @@ def make(rng, n, L, states, noise):
 
 
 def timed(fn):
+    """-> ms between HIP events around fn(), and what it returned."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    assert fn() == 0
+    got = fn()
     e1.record()
     e1.synchronize()
-    return e0.elapsed_time(e1)
+    return e0.elapsed_time(e1), got
 
 
 def legs(X, cutoff, block_rows):
     """-> ms of the three legs, and the result."""
-    lib = N.lib()
-    p = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off)    # noqa: E731
     A = torch.as_tensor(X).cuda().contiguous()
-    n, L = A.shape[:2]
-    adj = torch.zeros((n, (n + 63) // 64), dtype=torch.int64, device="cuda")
+    n = A.shape[0]
+    adj = pairs.adjacency(n)
     buf = torch.empty((min(block_rows, n), n), dtype=torch.float64, device="cuda")
     ms = {"all_pairs": 0.0, "threshold": 0.0}
     for r0 in range(0, n, block_rows):
-        rows = min(block_rows, n - r0)
-        ms["all_pairs"] += timed(lambda: lib.esmdiff_superpose_pairs(p(A, r0 * L * 24), rows, p(A), n, L, None, None, 0, p(buf), None, None,
-                                                                     None, None))
-        ms["threshold"] += timed(lambda: lib.esmdiff_cluster_threshold(p(buf), rows, r0, n, cutoff, 0, p(adj), None))
-    out = torch.empty((3, n), dtype=torch.int32, device="cuda")
-    k = torch.zeros(1, dtype=torch.int32, device="cuda")
-    ms["loop"] = timed(lambda: lib.esmdiff_cluster_gromos(p(adj), n, p(out), p(out, 4 * n), p(out, 8 * n), p(k), None))
+        block = buf[:min(block_rows, n - r0)]
+        ms["all_pairs"] += timed(lambda: pairs.superpose(A[r0:r0 + block.shape[0]], A, None, None, False, ("rmsd",), {"rmsd": block}))[0]
+        ms["threshold"] += timed(lambda: pairs.threshold(block, r0, cutoff, False, adj))[0]
+    ms["loop"], (out, k) = timed(lambda: pairs.gromos(adj))
     return ms, out.cpu().numpy(), int(k.item())
 
 

@@ -22,7 +22,7 @@ ap.add_argument("--no-host", action="store_true")
 args = ap.parse_args()
 OUT = Path(args.out)
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-from esmdiff_amd import ensemble
+from esmdiff_amd import ensemble, pairs
 from tests import lddt_ref as R
 
 out = {"device": torch.cuda.get_device_name(0), "cases": []}
@@ -46,13 +46,13 @@ def device_case(n, m, L, reps):
         call.append(time.perf_counter() - t)
         torch.cuda.synchronize()
         t = time.perf_counter()
-        kept, total, _, _ = ensemble._lddt_counts(a, b, None, None, n, m)      # the launch alone: synchronises the stream
+        kept, total, _, _ = pairs.lddt_counts(a, b, None, None)                # the launch alone: synchronises the stream
         kern.append(time.perf_counter() - t)
     total = total.cpu().numpy()
-    pairs = n * m * L * L
+    ordered = n * m * L * L
     case = {"n": n, "m": m, "L": L, "reps": reps, "lddt_matrix_s": sorted(call), "launch_s": sorted(kern),
-            "ordered_pairs": pairs, "pairs_inside_r0_fraction": float(total.sum() / (m * L * (L - 1))),
-            "ordered_pairs_per_s_median": pairs / float(np.median(kern)),
+            "ordered_pairs": ordered, "pairs_inside_r0_fraction": float(total.sum() / (m * L * (L - 1))),
+            "ordered_pairs_per_s_median": ordered / float(np.median(kern)),
             "scored_pairs_per_s_median": float(n * total.sum()) / float(np.median(kern))}
     out["cases"].append(case)
     print(json.dumps(case), flush=True)

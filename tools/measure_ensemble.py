@@ -4,11 +4,11 @@ ordered ones) and the same pairs through the host restatement (tests/ensemble_re
 
     python tools/measure_ensemble.py [--n 100] [--L 256] [--repeats 7] [--host_pairs 24] [--out profiles/ensemble_timing.json]
 
-Kernel time: HIP events around the raw C-ABI call on tensors already on the device (the entry synchronises the stream itself).
+Kernel time: HIP events around the esmdiff_amd.pairs call on tensors already on the device: one C-ABI call (the entry synchronises
+the stream itself) and the allocation of its output.
 Call time: wall clock of esmdiff_amd.ensemble.tm_matrix / pairwise_rmsd with numpy in and numpy out (upload, launch, download).
 The reference's way — one `TMscore -seq` subprocess per pair — cannot be timed: the program is in no tree this project can reach."""
 import argparse
-import ctypes
 import json
 import statistics
 import subprocess
@@ -21,7 +21,7 @@ import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-from esmdiff_amd import _native as N, ensemble  # noqa: E402
+from esmdiff_amd import ensemble, pairs  # noqa: E402
 from tests import ensemble_ref as E  # noqa: E402
 
 
@@ -43,24 +43,21 @@ def main():
     rng = np.random.default_rng(0)
     X = E.ensemble(rng, a.n, a.L, noise=2.0)
     Xd = torch.as_tensor(X).cuda()
-    tm = torch.empty(a.n, a.n, dtype=torch.float64, device="cuda")
-    rm = torch.empty(a.n, a.n, dtype=torch.float64, device="cuda")
-    p = lambda t: ctypes.c_void_p(t.data_ptr())    # noqa: E731
-    lib = N.lib()
-    launches = {
-        "tm_pairs": lambda: lib.esmdiff_tm_pairs(p(Xd), a.n, None, 0, a.L, None, None, p(tm), None, None, None),
-        "superpose_pairs": lambda: lib.esmdiff_superpose_pairs(p(Xd), a.n, None, 0, a.L, None, None, 0, p(rm), None, None, None, None),
+    launches = {                                                        # one C entry each; what it returns stays on the device
+        "tm_pairs": lambda: pairs.tm(Xd, None, None, None),
+        "superpose_pairs": lambda: pairs.superpose(Xd, None, None, None, False, ("rmsd",))["rmsd"],
     }
     calls = {"tm_pairs": lambda: ensemble.tm_matrix(X), "superpose_pairs": lambda: ensemble.pairwise_rmsd(X)}
     res = {"n": a.n, "L": a.L, "ordered_pairs": a.n * a.n, "distinct_pairs": a.n * (a.n - 1) // 2, "repeats": a.repeats,
            "device": torch.cuda.get_device_name(0), "clocks_before": clocks()}
+    launched = {}
     for name, fn in launches.items():
-        assert fn() == 0                                             # warm-up (code object load)
+        fn()                                                         # warm-up (code object load)
         ms = []
         for _ in range(a.repeats):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            assert fn() == 0
+            out = fn()
             e1.record()
             e1.synchronize()
             ms.append(e0.elapsed_time(e1))
@@ -69,6 +66,7 @@ def main():
             t0 = time.perf_counter()
             calls[name]()
             wall.append((time.perf_counter() - t0) * 1e3)
+        launched[name] = out.cpu().numpy()
         res[name] = {"kernel_ms_median": statistics.median(ms), "kernel_ms_min": min(ms), "kernel_ms_max": max(ms),
                      "call_ms_median": statistics.median(wall), "kernel_ms_all": ms}
     # the host restatement on a subsample of the distinct pairs, extrapolated linearly to all of them
@@ -81,7 +79,7 @@ def main():
     host_rm = [E.superpose_pair(X[i], X[j])[0] for i, j in pick]
     t_rm = time.perf_counter() - t0
     scale = len(iu) / len(pick)
-    tmh, rmh = tm.cpu().numpy(), rm.cpu().numpy()
+    tmh, rmh = launched["tm_pairs"], launched["superpose_pairs"]
     res["host_restatement"] = {"pairs_timed": len(pick), "tm_s_per_pair": t_tm / len(pick), "rmsd_s_per_pair": t_rm / len(pick),
                                "tm_s_extrapolated_to_distinct_pairs": t_tm * scale, "rmsd_s_extrapolated_to_distinct_pairs": t_rm * scale,
                                "max_abs_tm_difference": float(max(abs(tmh[i, j] - v) for (i, j), v in zip(pick, host_tm))),
