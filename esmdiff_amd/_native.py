@@ -63,6 +63,7 @@ EXPORTS = [
     "esmdiff_superpose_pairs", "esmdiff_tm_pairs",
     "esmdiff_cluster_threshold", "esmdiff_cluster_gromos",
     "esmdiff_lddt_pairs",
+    "esmdiff_describe_gemm_choice", "esmdiff_gemm_workspace_floats",
 ]
 LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
 TM_MAX_L = 1280                              # ESMDIFF_TM_MAX_L
@@ -167,6 +168,8 @@ def lib():
     L.esmdiff_split_weight.argtypes = [vp, vp, i32, i32, i32, c_f32p]
     L.esmdiff_gemm_split.argtypes = [vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, f32, i32, vp]
     L.esmdiff_gemm_bf16_ws.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]
+    L.esmdiff_describe_gemm_choice.argtypes = [i32, i32, i32, ctypes.c_int64] + [ctypes.POINTER(i32)] * 4
+    L.esmdiff_gemm_workspace_floats.argtypes = [vp, c_i64p]
     for n in EXPORTS:
         if n not in ("esmdiff_engine_destroy", "esmdiff_last_error", "esmdiff_encoder_destroy", "esmdiff_encoder_last_error"):
             getattr(L, n).restype = ctypes.c_int
@@ -174,6 +177,14 @@ def lib():
         raise RuntimeError("libesmdiff_hip.so ABI version mismatch")
     _lib = L
     return L
+
+
+def gemm_choice(M: int, N: int, K: int, ws_floats: int = 0) -> dict:
+    """esmdiff_describe_gemm_choice: which GEMM launch (M, N, K) gets, from the launcher's own dispatcher; runs no kernel.
+    {"w4": the 256x256 kernel, "rows": rows per tile, "S": K slices, "stages": LDS stages}."""
+    v = [ctypes.c_int32(0) for _ in range(4)]
+    check(lib().esmdiff_describe_gemm_choice(M, N, K, int(ws_floats), *[ctypes.byref(x) for x in v]))
+    return {"w4": bool(v[0].value), "rows": int(v[1].value), "S": int(v[2].value), "stages": int(v[3].value)}
 
 
 def build_info() -> str:

@@ -1648,6 +1648,25 @@ int esmdiff_gemm_bf16_ws(esmdiff_engine* e, const void* A, const void* W, void* 
   return 0;
 }
 
+int esmdiff_describe_gemm_choice(int32_t M, int32_t N, int32_t K, int64_t ws_floats, int32_t* w4_out, int32_t* rows_out,
+                                 int32_t* splits_out, int32_t* stages_out) {
+  if (!w4_out || !rows_out || !splits_out || !stages_out || M <= 0 || N <= 0 || K <= 0 || N % 128 || K % 64 || ws_floats < 0)
+    return ESMDIFF_E_INVALID;
+  int w4 = 0, rows = 0, S = 0, stages = 0;
+  ed::describe_gemm_choice(M, N, K, (size_t)ws_floats, &w4, &rows, &S, &stages);
+  *w4_out = w4;
+  *rows_out = rows;
+  *splits_out = S;
+  *stages_out = stages;
+  return 0;
+}
+
+int esmdiff_gemm_workspace_floats(const esmdiff_engine* e, int64_t* floats_out) {
+  if (!e || !floats_out) return ESMDIFF_E_INVALID;
+  *floats_out = e->gemm_ws[0].partial ? (int64_t)e->gemm_ws[0].partial_floats : 0;
+  return 0;
+}
+
 #ifdef ED_DEBUG   // measurement aid (scratch/bench_gemm.py), not a switch
 int esmdiff_gemm_bf16_timed(const void* A, const void* W, void* out, const float* bias, int32_t M, int32_t N,
                             int32_t K, int32_t ldc, int32_t n_valid, float alpha, int32_t epilogue, int32_t iters,

@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const bf16_t* __restr
       }
     }
   }
-  (void)n_valid;
+  (void)n_valid;  // not a bound: columns n_valid .. ldc-1 are written (padded weight rows + bias), see kernels_ns.inc
 }
 
 // split-K second pass: out = epi(sum_s partial[s]) ; one thread = 4 consecutive output columns of one row
@@ -358,12 +358,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // `partial` (S planes of pstride floats, row stride N), reduced by splitk_reduce_kernel unless keep_partials.
 static hipError_t launch_tiles(const bf16_t* A, const bf16_t* W, void* out, const float* bias, int M, int N, int K,
                                int ldc, int n_valid, float alpha, int epilogue, hipStream_t stream, int mi, int S,
-                               float* partial, int64_t pstride, bool keep_partials) {
+                               int nst, float* partial, int64_t pstride, bool keep_partials) {
   const int bm = 64 * mi;
   const int tiles_m = (M + bm - 1) / bm, tiles_n = N / BN;
-  // four-stage ring with one workgroup per CU while everything is resident at once; two stages x two (or more)
-  // workgroups per CU beyond that
-  const bool four = tiles_m * tiles_n * S <= 256;
+  const bool four = nst == 4;  // tile_stages(), through choose_gemm() or launch_gemm_partials()
   dim3 grid(tiles_m * tiles_n * S), block(256);
   const int w_nt = tiles_m <= 8;          // few row tiles per weight tile: stream the weights non-temporally
   const int w_rs = K, w_ks = BK;          // W strides: row, K-tile, 128-row block (row-major [N, K])
@@ -410,13 +408,21 @@ static int small_tile_mi(int M, int N, int S) {
 }
 
 // Which kernel a shape runs on — ONE function for the launcher and for the text esmdiff_describe_plan prints beside the results
+// and for the numbers esmdiff_describe_gemm_choice hands the tests
 // (two copies of the rule drift apart as soon as one is edited).
-//   w4      the 256x256 four-wave kernel (gemm256w4.hip; one persistent workgroup per CU)
+//   w4      the 256x256 four-wave kernel (gemm256w4.hip; one persistent workgroup per CU, its own two 64 KiB stages)
 //   mi, S   else: this file's 128-column kernel with 64 * mi rows per tile and S K-slices (S > 1 needs the split-K workspace)
+//   nst     ... and its LDS stage count, tile_stages()
 struct GemmChoice {
   bool w4;
-  int mi, S;
+  int mi, S, nst;
 };
+// LDS stages of the 128-column kernel: the four-stage ring with one workgroup per CU while everything is resident at once; two
+// stages x two (or more) workgroups per CU beyond that
+static int tile_stages(int M, int N, int mi, int S) {
+  const int bm = 64 * mi;
+  return ((M + bm - 1) / bm) * (N / BN) * S <= 256 ? 4 : 2;
+}
 static GemmChoice choose_gemm(int M, int N, int K, bool has_ws, size_t ws_floats) {
   // Tile selection: the 256x256 kernel once it has >= 128 tiles to hand out, the 128x128 kernel otherwise.  Measured crossovers
   // (us, 128 vs 256): N = 1536, K = 4096: M = 4128 67 / 81, M = 6192 109 / 87; N = 4608: M = 1032 28 / 37, M = 2064 48 / 42;
@@ -432,7 +438,7 @@ static GemmChoice choose_gemm(int M, int N, int K, bool has_ws, size_t ws_floats
   const int t256m = (M + 255) / 256, t256 = t256m * (N / 256);
   if (N % 256 == 0 && K % (2 * BK) == 0 && K >= 6 * BK &&
       (t256 >= 128 || (t256 >= 72 && t256m >= 12)))
-    return GemmChoice{true, 2, 1};
+    return GemmChoice{true, 2, 1, 2};
   const int tiles_n = N / BN;
   // split-K factor, a function of (N, K) only: for K >= 2048 (FFN-down) the largest divisor of K/64 that is <= 8 and
   // keeps tiles_n * S <= 96.  Measured (us per launch, M = 240 / 774): FFN-down K = 4096 S = 8: 42 -> 17 / 41 -> 35;
@@ -448,7 +454,8 @@ static GemmChoice choose_gemm(int M, int N, int K, bool has_ws, size_t ws_floats
       }
     if ((size_t)S * (size_t)((M + 127) / 128) * 128 * N > ws_floats) S = 1;
   }
-  return GemmChoice{false, M < small_max_rows() ? small_tile_mi(M, N, S) : 2, S};
+  const int mi = M < small_max_rows() ? small_tile_mi(M, N, S) : 2;
+  return GemmChoice{false, mi, S, tile_stages(M, N, mi, S)};
 }
 
 hipError_t launch_gemm_bf16(const bf16_t* A, const bf16_t* W, void* out, const float* bias, int M, int N,
@@ -460,7 +467,7 @@ hipError_t launch_gemm_bf16(const bf16_t* A, const bf16_t* W, void* out, const f
   const GemmChoice c = choose_gemm(M, N, K, has_ws, has_ws ? ws->partial_floats : 0);
   if (c.w4) return launch_gemm256w4_bf16(A, W, out, bias, M, N, K, ldc, alpha, epilogue, stream);
   const int64_t pstride = (int64_t)((M + 127) / 128) * 128 * N;
-  return launch_tiles(A, W, out, bias, M, N, K, ldc, n_valid, alpha, epilogue, stream, c.mi, c.S,
+  return launch_tiles(A, W, out, bias, M, N, K, ldc, n_valid, alpha, epilogue, stream, c.mi, c.S, c.nst,
                       c.S > 1 ? ws->partial : nullptr, pstride, false);
 }
 
@@ -471,6 +478,15 @@ void describe_gemm(int M, int N, int K, size_t ws_floats, char* out, size_t cap)
   if (c.w4) snprintf(out, cap, "256x256w4");
   else if (c.S > 1) snprintf(out, cap, "128x%d/S%d", 64 * c.mi, c.S);
   else snprintf(out, cap, "128x%d", 64 * c.mi);
+}
+
+// The same choice as numbers (esmdiff_describe_gemm_choice): rows per tile (256 for the 256x256 kernel), K slices, LDS stages.
+void describe_gemm_choice(int M, int N, int K, size_t ws_floats, int* w4, int* rows, int* S, int* stages) {
+  const GemmChoice c = choose_gemm(M, N, K, ws_floats > 0, ws_floats);
+  *w4 = c.w4 ? 1 : 0;
+  *rows = c.w4 ? 256 : 64 * c.mi;
+  *S = c.S;
+  *stages = c.nst;
 }
 
 // ---- residual-branch linears of the small-batch path ------------------------------------------------------------
@@ -495,7 +511,8 @@ hipError_t launch_gemm_partials(const bf16_t* A, const bf16_t* W, const GemmWork
   if ((size_t)S * pstride > ws->partial_floats) return hipErrorInvalidValue;
   *res = GemmPartials{ws->partial, S, pstride};
   // (S = 1 still goes through `partial`: one raw f32 plane)
-  return launch_tiles(A, W, nullptr, nullptr, M, N, K, N, N, 1.f, ESMDIFF_EPI_BF16, stream, small_tile_mi(M, N, S), S,
+  const int mi = small_tile_mi(M, N, S);
+  return launch_tiles(A, W, nullptr, nullptr, M, N, K, N, N, 1.f, ESMDIFF_EPI_BF16, stream, mi, S, tile_stages(M, N, mi, S),
                       ws->partial, pstride, true);
 }
 

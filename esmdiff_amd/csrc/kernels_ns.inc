@@ -68,6 +68,8 @@ hipError_t launch_gibbs_step_rows(int64_t* x, const int64_t* seq, const float* l
 // out = epilogue(A[M,K] · W[N,K]^T); K % 64 == 0, N % 128 == 0 (weights are padded at load time).
 // ws (optional): split-K workspace for the small-M path — room for f32 partial tiles, owned by ONE launch queue
 // (concurrent launches need their own).  Without it every tile runs its whole K range.
+// n_valid is informative only: neither kernel reads it.  ESMDIFF_EPI_BIAS_F32 skips a 4-column group only when it would cross
+// ldc; columns n_valid .. ldc-1 are written from the (zero-padded) weight rows and the bias, so the caller allocates ldc for them.
 using GemmWorkspace = ::EdGemmWorkspace;   // (one type for both operand-type builds, kernels.h)
 hipError_t launch_gemm_bf16(const bf16_t* A, const bf16_t* W, void* out, const float* bias, int M, int N,
                             int K, int ldc, int n_valid, float alpha, int epilogue, hipStream_t stream,
@@ -75,6 +77,8 @@ hipError_t launch_gemm_bf16(const bf16_t* A, const bf16_t* W, void* out, const f
 
 // the kernel launch_gemm_bf16 would pick for (M, N, K), as text
 void describe_gemm(int M, int N, int K, size_t ws_floats, char* out, size_t cap);
+// ... and as numbers: 256x256 kernel or not, rows per tile, K slices, LDS stages (esmdiff_describe_gemm_choice)
+void describe_gemm_choice(int M, int N, int K, size_t ws_floats, int* w4, int* rows, int* S, int* stages);
 
 // Row count below which a (sub-)batch takes the small-batch path (DESIGN 3.8).
 inline int small_max_rows() {

@@ -586,15 +586,26 @@ class Engine:
         self._frames = (r, t, m)   # keep the staging tensors alive until the async copies have run
 
     def gemm(self, A: torch.Tensor, W: torch.Tensor, epilogue: int, *, bias: Optional[torch.Tensor] = None,
-             alpha: float = 1.0) -> torch.Tensor:
-        """bf16-output GEMM exactly as the forward issues it (esmdiff_gemm_bf16_ws: split-K workspace attached)."""
+             alpha: float = 1.0, out: Optional[torch.Tensor] = None, n_valid: Optional[int] = None) -> torch.Tensor:
+        """The GEMM exactly as the forward issues it (esmdiff_gemm_bf16_ws: split-K workspace attached).  `out`: the output
+        buffer (its row stride is ldc); required for the f32 epilogues, a fresh bf16 tensor otherwise."""
         M, K = A.shape
         Nn = W.shape[0]
         assert A.dtype == W.dtype == torch.bfloat16 and A.is_contiguous() and W.is_contiguous() and W.shape[1] == K
-        out = torch.empty(M, Nn // 2 if epilogue == N.EPI_SWIGLU_BF16 else Nn, dtype=torch.bfloat16, device=A.device)
+        if out is None:
+            if epilogue in (N.EPI_RESID_F32, N.EPI_BIAS_F32):
+                raise ValueError("f32 epilogues need an explicit `out`")
+            out = torch.empty(M, Nn // 2 if epilogue == N.EPI_SWIGLU_BF16 else Nn, dtype=torch.bfloat16, device=A.device)
         self._chk(self._lib.esmdiff_gemm_bf16_ws(self._h, _ptr(A), _ptr(W), _ptr(out), _ptr(bias), M, Nn, K, out.stride(0),
-                                                 Nn, float(alpha), epilogue, _stream()))
+                                                 Nn if n_valid is None else n_valid, float(alpha), epilogue, _stream()))
         return out
+
+    @property
+    def gemm_workspace_floats(self) -> int:
+        """Floats in the split-K workspace `gemm` hands its launch (esmdiff_gemm_workspace_floats); 0 for float32 engines."""
+        n = ctypes.c_int64(0)
+        self._chk(self._lib.esmdiff_gemm_workspace_floats(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def set_gibbs_options(self, strategy: str = "entropy", invalid_ids=()) -> None:
         """GenerationConfig.strategy ("entropy" | "random") and .invalid_ids for the following gibbs steps

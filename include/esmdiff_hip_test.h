@@ -20,8 +20,13 @@ typedef enum {
   ESMDIFF_EPI_RESID_F32 = 1,  /* out f32 [M,N] += acc * alpha   (residual stream)   */
   ESMDIFF_EPI_SWIGLU_BF16 = 2,/* W rows interleaved gate/up in blocks of 32; out bf16 [M,N/2] */
   ESMDIFF_EPI_BIAS_GELU_BF16 = 3, /* out bf16 = gelu(acc + bias[N])                 */
-  ESMDIFF_EPI_BIAS_F32 = 4    /* out f32 [M,ldc] = acc + bias, columns >= n_valid skipped */
+  ESMDIFF_EPI_BIAS_F32 = 4    /* out f32 [M,ldc] = acc + bias; a 4-column group is skipped only when it would cross ldc */
 } esmdiff_gemm_epilogue;
+
+/* n_valid is not a bound of these kernels (neither the 128-column nor the 256x256 one reads it): with ESMDIFF_EPI_BIAS_F32 every
+ * 4-column group that ends at or before ldc is stored, so columns n_valid .. ldc-1 receive acc + bias like the others (with zero
+ * weight rows from n_valid up, as the engine pads them: the bias).  ldc % 4 == 0 and the caller allocates ldc columns per row;
+ * nothing is written at or past ldc.  (esmdiff_gemm_f32 below does stop at n_valid.) */
 
 int esmdiff_gemm_bf16(const void* A, const void* W, void* out, const float* bias, int32_t M, int32_t N,
                       int32_t K, int32_t ldc, int32_t n_valid, float alpha, int32_t epilogue, void* stream);
@@ -59,6 +64,17 @@ int esmdiff_gemm_split(const void* a2, const float* rs, const void* w2, float w_
 int esmdiff_gemm_bf16_ws(esmdiff_engine* eng, const void* A, const void* W, void* out, const float* bias, int32_t M,
                          int32_t N, int32_t K, int32_t ldc, int32_t n_valid, float alpha, int32_t epilogue,
                          void* stream);
+
+/* What launch of esmdiff_gemm_bf16 / _f16 / _bf16_ws a shape gets, as numbers and without running anything: answered by the
+ * dispatcher the launcher itself calls (csrc/gemm.hip: choose_gemm).  ws_floats: size of the split-K workspace the launch would be
+ * handed (0: none, as esmdiff_gemm_bf16 and _f16 run).  M > 0, N % 128 == 0, K % 64 == 0.
+ *   *w4_out      1: the four-wave 256x256 kernel (csrc/gemm256w4.hip), then rows = 256, splits = 1, stages = 2;  0: the 128-column kernel
+ *   *rows_out    rows per tile (64 or 128)      *splits_out  K slices S (> 1: slices + the fixed-order reduce kernel)
+ *   *stages_out  LDS stages (4: the counted-vmcnt ring, 2: double buffer) */
+int esmdiff_describe_gemm_choice(int32_t M, int32_t N, int32_t K, int64_t ws_floats, int32_t* w4_out, int32_t* rows_out,
+                                 int32_t* splits_out, int32_t* stages_out);
+/* Floats in the split-K workspace esmdiff_gemm_bf16_ws hands its launch (0: the engine has none): the ws_floats of that engine. */
+int esmdiff_gemm_workspace_floats(const esmdiff_engine* eng, int64_t* floats_out);
 
 /* The small-batch form of a residual branch (M < 1152 rows; csrc/engine.hip::forward): the branch linear A[M,K] W[N,K]^T
  * is left as S raw f32 K-slice planes in the engine's workspace (S = *splits_out, a function of N and K only) and the
