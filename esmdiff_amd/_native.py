@@ -63,13 +63,21 @@ EXPORTS = [
     "esmdiff_superpose_pairs", "esmdiff_tm_pairs",
     "esmdiff_cluster_threshold", "esmdiff_cluster_gromos",
     "esmdiff_lddt_pairs",
+    "esmdiff_flex_pair_msf", "esmdiff_flex_fit", "esmdiff_flex_moments",
     "esmdiff_describe_gemm_choice", "esmdiff_gemm_workspace_floats",
 ]
 LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
 TM_MAX_L = 1280                              # ESMDIFF_TM_MAX_L
+
 CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
 OPT_STREAMS, OPT_DUAL_MIN_TOKENS = 1, 2      # esmdiff_option
+
+
+def flex_pair_slots(n: int) -> int:
+    """ESMDIFF_FLEX_PAIR_SLOTS: the partial sums esmdiff_flex_pair_msf keeps per residue (12 bytes each, in the caller's scratch)."""
+    rows = (n + 1) // 2
+    return 4 * rows * min(16, max(1, 2048 // rows))
 
 
 def lib_path() -> Path:
@@ -149,6 +157,9 @@ def lib():
     L.esmdiff_cluster_threshold.argtypes = [vp, i32, i32, i32, f64, i32, vp, vp]
     L.esmdiff_cluster_gromos.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.esmdiff_lddt_pairs.argtypes = [vp, i32, vp, i32, i32, vp, vp, f64, f64p, i32, i32, vp, vp, vp, vp, vp]
+    L.esmdiff_flex_pair_msf.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.c_int64, vp]
+    L.esmdiff_flex_fit.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.esmdiff_flex_moments.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.esmdiff_encoder_create.argtypes = [i32] * 9 + [ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.esmdiff_encoder_destroy.argtypes = [vp]
     L.esmdiff_encoder_destroy.restype = None

@@ -1,7 +1,7 @@
 """Evaluate one sampled ensemble against its target structures on the device.
 
     python -m esmdiff_amd.analyze_ensemble --samples <multi-MODEL pdb> --targets a.pdb [b.pdb ...] --output <dir> [--max_models 100]
-                                           [--lddt] [--plddt_scale 1.0]
+                                           [--lddt] [--plddt_scale 1.0] [--flex] [--pca_components 3]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
@@ -11,7 +11,13 @@ TM-scores are [TMSCORE-RECALL], parity unpinned (esmdiff_amd/ensemble.py).
 CA-lDDT per target, averaged), lddt_div (the mean symmetric lDDT over sample pairs), best_lddt / best_lddt_model / best_lddt_residue
 (per target: the best sample's lDDT, its position among the analysed samples, its per-residue lDDT) and, when the samples' PDB
 carries B-factors (the decoder's pLDDT, divided by --plddt_scale), plddt_agreement: per target the per-residue mean observed lDDT,
-the mean predicted one, their Pearson r and the mean absolute difference."""
+the mean predicted one, their Pearson r and the mean absolute difference.
+--flex adds a "flex" block (esmdiff_amd/flexibility.py, csrc/flex.hip): the mean structure of the samples (n_iter, converged, mean,
+rmsd_to_mean), the RMSF about it (rmsf), the reference's pairwise RMSF (pair_rmsf), and the Cartesian PCA of the samples superposed
+on the mean (pca: explained_variance, explained_variance_ratio, projections of the samples, target_projections; --pca_components
+modes).  With exactly two targets also resflex (Pearson / Spearman / Kendall between the report's apo-holo deviation `rmsd` and its
+`rmsf`, the reference's per-target numbers), resflex_mean_structure (the same against the mean-structure RMSF) and
+displacement_overlap (the share of the displacement between the two targets that the leading modes span, cumulative)."""
 from __future__ import annotations
 
 import argparse
@@ -20,7 +26,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import ensemble
+from . import ensemble, flexibility
 from .pdbio import load_coords, read_pdb_bfactors
 
 
@@ -48,7 +54,23 @@ def lddt_report(samples, targets, plddt=None, plddt_scale: float = 1.0) -> dict:
     return out
 
 
-def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0) -> dict:
+def flex_report(samples, targets, report: dict, pca_components: int = 3) -> dict:
+    """The --flex block: samples (n, L, 3), targets (K, L, 3), report: what analyze computed so far (two targets: apo_report's)."""
+    ms = flexibility.mean_structure(samples)
+    out = {"n_iter": ms.n_iter, "converged": ms.converged, "rmsd_to_mean": ms.rmsd_to_mean, "mean": ms.mean, "rmsf": ms.rmsf,
+           "pair_rmsf": flexibility.pair_rmsf(samples)}
+    p = flexibility.pca(samples, n_components=pca_components)
+    out["pca"] = {"explained_variance": p.explained_variance, "explained_variance_ratio": p.explained_variance_ratio,
+                  "projections": p.projections, "target_projections": p.project(targets)}
+    if len(targets) == 2:
+        out["resflex"] = flexibility.flexibility_correlation(report["rmsd"], report["rmsf"])
+        out["resflex_mean_structure"] = flexibility.flexibility_correlation(report["rmsd"], ms.rmsf)
+        out["displacement_overlap"] = p.displacement_overlap(targets[0], targets[1])
+    return out
+
+
+def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0,
+            flex: bool = False, pca_components: int = 3) -> dict:
     samples = load_coords(Path(samples_path), max_n_model=None, verbose=False)
     n_all, keep = len(samples), np.arange(len(samples))
     if len(samples) > max_models:
@@ -73,10 +95,12 @@ def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, ld
             if b.shape == samples.shape[:2] and np.any(b != 0):        # all zero: written without a confidence
                 plddt = b
         report.update(lddt_report(samples, np.stack(targets), plddt, plddt_scale))
+    if flex:
+        report["flex"] = flex_report(samples, np.stack(targets), report, pca_components)
     return report
 
 
-def main(argv=None) -> Path:
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--samples", required=True, help="multi-MODEL PDB of the sampled ensemble")
     ap.add_argument("--targets", required=True, nargs="+", help="target structures, one PDB each (same sequence as the samples)")
@@ -85,8 +109,14 @@ def main(argv=None) -> Path:
     ap.add_argument("--seed", type=int, default=0, help="seed of the down-sampling to --max_models")
     ap.add_argument("--lddt", action="store_true", help="add the CA-lDDT scores (no superposition) and the pLDDT agreement")
     ap.add_argument("--plddt_scale", type=float, default=1.0, help="the samples' B-factors divided by this are pLDDT in [0, 1]")
-    args = ap.parse_args(argv)
-    report = analyze(args.samples, args.targets, args.max_models, args.seed, args.lddt, args.plddt_scale)
+    ap.add_argument("--flex", action="store_true", help="add the mean structure, RMSF, pairwise RMSF, PCA and the ResFlex correlations")
+    ap.add_argument("--pca_components", type=int, default=3, help="modes of the --flex PCA")
+    return ap
+
+
+def main(argv=None) -> Path:
+    args = parser().parse_args(argv)
+    report = analyze(args.samples, args.targets, args.max_models, args.seed, args.lddt, args.plddt_scale, args.flex, args.pca_components)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

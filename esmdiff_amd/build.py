@@ -44,6 +44,7 @@ UNITS = {
     "metrics": ["-ffp-contract=off"],
     "superpose": [],          # float64 only: the shipped code objects hold no packed op (the scan of tests/test_host_cpu.py passes without geom's flags)
     "cluster": [],            # integers only (ballots, popcounts, LDS atomics)
+    "flex": [],               # float64 only, as superpose (csrc/ed_kabsch.h is shared with it)
     "lddt": ["-ffp-contract=off"],       # float64 distances, integer counts, equal to numpy's: no FMA (tests/lddt_ref.py)
 }
 # The MFMA kernels, the row kernels that feed them and the weight conversion are compiled a SECOND time with f16 operands

@@ -1,6 +1,7 @@
-"""The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip and
-csrc/cluster.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
-on the device out, no host transfer.  esmdiff_amd/ensemble.py and esmdiff_amd/clustering.py are the host-facing layers above it.
+"""The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
+csrc/cluster.hip and csrc/flex.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
+host-facing layers above it.
 Row blocks are contiguous slices (A[r0:r1]): a slice carries its own pointer, dtype and shape.  There is no CPU fallback."""
 from __future__ import annotations
 
@@ -152,3 +153,49 @@ def gromos(adj: torch.Tensor):
     code = N.lib().esmdiff_cluster_gromos(_p(adj), n, _p(out[0]), _p(out[1]), _p(out[2]), _p(k), _stream())
     _check("esmdiff_cluster_gromos", code)
     return out, k
+
+
+def _flex_sizes(A: torch.Tensor, mask: Optional[torch.Tensor]):
+    assert A.dim() == 3 and A.shape[-1] == 3 and A.dtype == torch.float64, f"f64 (n, L, 3) coordinates, got {A.dtype} {tuple(A.shape)}"
+    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == tuple(A.shape[:2])), "the mask is u8 (n, L)"
+    return A.shape[0], A.shape[1]
+
+
+def _flex_invalid(entry: str, n: int, L: int):
+    return lambda: f"{entry}: invalid argument: n = {n} (at least 1), L = {L} (at least 2)"
+
+
+def pair_msf(A, ma):
+    """One esmdiff_flex_pair_msf call -> sum_sq f64 (L,), count i64 (L,): over the pairs i < j of A (n, L, 3) fitted on the residues
+    valid in both, the sum of each residue's squared deviation and the number of pairs it was valid in.  The (n, n, L) deviations are
+    never stored: the scratch holds N.flex_pair_slots(n) partial sums per residue."""
+    n, L = _flex_sizes(A, ma)
+    sum_sq, count = _new((L,)), _new((L,), torch.int64)
+    size = N.flex_pair_slots(n) * L * 12
+    scratch = _new((size // 4,), torch.int32)
+    code = N.lib().esmdiff_flex_pair_msf(_p(A), n, L, _p(ma), _p(sum_sq), _p(count), _p(scratch), size, _stream())
+    _check("esmdiff_flex_pair_msf", code, invalid=_flex_invalid("esmdiff_flex_pair_msf", n, L),
+           capacity=lambda: f"esmdiff_flex_pair_msf: a scratch of {size} bytes is too small for n = {n}, L = {L}")
+    return sum_sq, count
+
+
+def fit(A, ma, ref, mref):
+    """One esmdiff_flex_fit call: every A[i] fitted onto ref (L, 3) on the residues valid in both (mref u8 (L,) or None) ->
+    aligned f64 (n, L, 3) (the whole structure moved; a NaN coordinate stays NaN), rmsd f64 (n,).  Fewer than 2 common residues: NaN."""
+    n, L = _flex_sizes(A, ma)
+    assert ref.dtype == torch.float64 and tuple(ref.shape) == (L, 3), f"the reference is f64 ({L}, 3), got {tuple(ref.shape)}"
+    assert mref is None or (mref.dtype == torch.uint8 and tuple(mref.shape) == (L,)), "the reference's mask is u8 (L,)"
+    aligned, rmsd = _new((n, L, 3)), _new((n,))
+    code = N.lib().esmdiff_flex_fit(_p(A), n, L, _p(ma), _p(ref), _p(mref), _p(aligned), _p(rmsd), _stream())
+    _check("esmdiff_flex_fit", code, invalid=_flex_invalid("esmdiff_flex_fit", n, L))
+    return aligned, rmsd
+
+
+def moments(X, mask):
+    """One esmdiff_flex_moments call -> mean f64 (L, 3), msf f64 (L,), count i32 (L,): per residue, over the structures valid there,
+    the mean position and the mean squared distance from it (NaN where count is 0)."""
+    n, L = _flex_sizes(X, mask)
+    mean, msf, count = _new((L, 3)), _new((L,)), _new((L,), torch.int32)
+    code = N.lib().esmdiff_flex_moments(_p(X), n, L, _p(mask), _p(mean), _p(msf), _p(count), _stream())
+    _check("esmdiff_flex_moments", code, invalid=_flex_invalid("esmdiff_flex_moments", n, L))
+    return mean, msf, count

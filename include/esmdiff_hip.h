@@ -560,6 +560,36 @@ int esmdiff_lddt_pairs(const double* A, int32_t n, const double* B, int32_t m, i
                        const uint8_t* maskB, double r0, const double* thresholds, int32_t n_thresholds, int32_t seq_sep,
                        int32_t* kept, int32_t* total, int32_t* kept_res, int32_t* total_res, void* stream);
 
+/* Residue flexibility of an ensemble (float64, device pointers in and out; each call synchronises `stream`): DESIGN.md §3.21.
+ * (An addition; the ABI number stays.)  A f64 [n, L, 3] CA traces, residue to residue; maskA u8 [n, L] or NULL (all valid): a masked
+ * coordinate is never read into a sum (it may be NaN).  Every fit is the proper rotation (det R = +1) of esmdiff_superpose_pairs.
+ * n < 1 or L < 2 return ESMDIFF_E_INVALID before anything is launched; there is no limit on L.  No float atomics: the order of every
+ * sum is a function of (n, L) alone (csrc/flex.hip states it), so two runs are bit-identical.
+ *
+ * esmdiff_flex_pair_msf: the reference's pairwise "RMSF" (analysis/apo_analysis.py:252-260) without its [n, n, L] array.  For every
+ * pair i < j, a_i is fitted onto a_j on the residues valid in both; the squared deviation of every such residue is added to
+ * sum_sq f64 [L] and 1 to count i64 [L].  A pair with fewer than 2 common residues contributes nothing and is not counted.  The
+ * per-pair deviations never reach memory: each wave of the launch keeps one partial sum per residue in `scratch`, and a second pass
+ * adds the partials in a fixed order.  scratch: at least ESMDIFF_FLEX_PAIR_SLOTS(n) * L * 12 bytes on the device, 8-byte aligned,
+ * need not be zeroed (f64 [slots, L] partial sums, then i32 [slots, L] partial counts); a smaller scratch_bytes, or scratch == NULL,
+ * returns ESMDIFF_E_CAPACITY.  n = 1 has no pair: sum_sq = 0, count = 0.
+ *
+ * esmdiff_flex_fit: every A[i] fitted onto ONE reference ref f64 [L, 3] (mask_ref u8 [L] or NULL) on the residues valid in both.
+ * aligned f64 [n, L, 3] (or NULL): the whole transformed structure, masked residues included (a NaN coordinate stays NaN);
+ * rmsd f64 [n] (or NULL): over the common residues.  Fewer than 2 common residues: NaN everywhere for that structure.
+ *
+ * esmdiff_flex_moments: per residue l, over the structures i with mask[i, l] (NULL: all): mean f64 [L, 3] the mean position,
+ * msf f64 [L] the mean squared distance from that mean (two passes: the mean first, then the deviations), count i32 [L] the number
+ * of structures; count = 0 gives NaN in mean and msf. */
+#define ESMDIFF_FLEX_PAIR_CHUNKS(n) (2048 / (((n) + 1) / 2) < 1 ? 1 : (2048 / (((n) + 1) / 2) > 16 ? 16 : 2048 / (((n) + 1) / 2)))
+#define ESMDIFF_FLEX_PAIR_SLOTS(n) ((int64_t)4 * (((n) + 1) / 2) * ESMDIFF_FLEX_PAIR_CHUNKS(n))
+int esmdiff_flex_pair_msf(const double* A, int32_t n, int32_t L, const uint8_t* maskA, double* sum_sq, int64_t* count, void* scratch,
+                          int64_t scratch_bytes, void* stream);
+int esmdiff_flex_fit(const double* A, int32_t n, int32_t L, const uint8_t* maskA, const double* ref, const uint8_t* mask_ref,
+                     double* aligned, double* rmsd, void* stream);
+int esmdiff_flex_moments(const double* X, int32_t n, int32_t L, const uint8_t* mask, double* mean, double* msf, int32_t* count,
+                         void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
