@@ -36,19 +36,26 @@ thread_local std::string g_create_error;
 
 enum Section { S_EMBED = 0, S_LN, S_QKV, S_QKROPE, S_ATTN, S_OUT, S_FFN_UP, S_FFN_DOWN, S_HEAD, S_SAMPLER, S_COUNT };
 
-struct SplitW {
-  uint16_t* w = nullptr;
+// One linear's weight, held in the one form its engine runs it in.  create_engine chooses the form per group of weights
+// (body_form / head_form / plain_form), load_linear fills the slot, and the forwards dispatch on `form`.  An accessor of
+// another form than the slot's gives null.
+struct Linear {
+  // W16: the engine's 16-bit type (bf16, or f16 on an f16 engine), the FFN-up's rows interleaved gate / up.  F32 (csrc/strict.hip):
+  // float32 in the checkpoint's own row order, no padding, no interleave.  SPLIT (csrc/gemm_split.hip): scaled f16 plane
+  // triples, and inv = 1 / scale.
+  enum Form : uint8_t { NONE, W16, F32, SPLIT };
+  Form form = NONE;
+  void* w = nullptr;
   float inv = 1.f;
+  const bf16_t* w16() const { return form == W16 ? static_cast<const bf16_t*>(w) : nullptr; }
+  const float* f32() const { return form == F32 ? static_cast<const float*>(w) : nullptr; }
+  const uint16_t* split() const { return form == SPLIT ? static_cast<const uint16_t*>(w) : nullptr; }
 };
 
 struct Layer {
-  float *ln1_w, *ln1_b, *q_ln_w, *k_ln_w, *ln2_w, *ln2_b;
-  bf16_t *w_qkv, *w_out, *w_up, *w_down;
-  // precision = F32 (csrc/strict.hip): the linears as float32 in the checkpoint's own row order (no SwiGLU interleave)
-  float *fw_qkv, *fw_out, *fw_up, *fw_down;
-  // precision = F32_SPLIT (csrc/gemm_split.hip): the linears as scaled f16 [lo | hi] plane pairs + 1 / scale
-  SplitW s_qkv, s_out, s_up, s_down;
-  // ... and the power-of-two operand scales of the split attention (attention_split.hip), from rigorous bounds at create
+  float *ln1_w = nullptr, *ln1_b = nullptr, *q_ln_w = nullptr, *k_ln_w = nullptr, *ln2_w = nullptr, *ln2_b = nullptr;
+  Linear w_qkv, w_out, w_up, w_down;
+  // F32_SPLIT: the power-of-two operand scales of the split attention (attention_split.hip), from rigorous bounds at create
   float att_qk = 1.f, att_v = 1.f;
 };
 
@@ -64,7 +71,7 @@ struct esmdiff_engine {
   std::vector<Layer> layers;
   float *e_seq = nullptr, *e_struct = nullptr, *cvec = nullptr;
   float *final_ln_w = nullptr;
-  bf16_t *head_w0 = nullptr, *head_w3 = nullptr;
+  Linear head_w0, head_w3;   // head_w3: rows padded to vocab_pad except as F32
   float *head_b0 = nullptr, *head_ln_w = nullptr, *head_ln_b = nullptr, *head_b3 = nullptr;
   float *sig_w1 = nullptr, *sig_b1 = nullptr, *sig_w2 = nullptr, *sig_b2 = nullptr;
   float *rope_cos = nullptr, *rope_sin = nullptr;
@@ -72,11 +79,12 @@ struct esmdiff_engine {
   // decoder only (kind 1): esm's plddt_head = RegressionHead(d, 50) on the same final hidden state (optional weights)
   bool has_plddt = false;
   int plddt_bins = 0, ld_plddt = 0;
-  bf16_t *pl_w0 = nullptr, *pl_w3 = nullptr;
+  Linear pl_w0, pl_w3;
   // decoder only: esm's pairwise_classification_head (PairwisePredictionHead(d, 128, 128, 224 bins, no bias)); only the
   // 64 predicted-aligned-error bins (rows 160..223 of linear2) are evaluated: pTM and the PAE matrix (csrc/pairwise.hip)
   bool has_pair = false;
-  bf16_t *pw_down = nullptr, *pw_l1 = nullptr, *pw_l2 = nullptr, *pair_qk = nullptr;
+  Linear pw_down, pw_l1, pw_l2;   // W16 or F32, never SPLIT
+  bf16_t* pair_qk = nullptr;
   float *pw_ln_w = nullptr, *pw_ln_b = nullptr, *zeros128 = nullptr, *tm_rows = nullptr, *ptm_dev = nullptr;
   bf16_t *pair_x = nullptr, *pair_h = nullptr;   // pair rows of a chunk of samples (allocated on first use)
   float* pair_logits = nullptr;
@@ -86,7 +94,7 @@ struct esmdiff_engine {
   bool has_geom = false;
   int v_heads = 0;  // rows of geom_attn.proj.weight / 15
   float *g_snorm_w = nullptr, *g_wrot = nullptr, *g_wdist = nullptr;
-  bf16_t *g_proj = nullptr, *g_out = nullptr;
+  Linear g_proj, g_out;   // SPLIT only as a pair: when both shapes fit the split GEMM
   bf16_t *gp = nullptr, *gctx = nullptr;
   float *f_rot = nullptr, *f_trans = nullptr;
   uint8_t* f_mask = nullptr;
@@ -119,20 +127,18 @@ struct esmdiff_engine {
   int n_streams = 2;         // esmdiff_set_option(ESMDIFF_OPT_STREAMS): sub-batch launch queues of the 16-bit forward
   ed::GemmWorkspace gemm_ws[4] = {};  // split-K partials of the small-M GEMM path, one per launch queue
   ed::GemmWorkspace gemm_ws2[4] = {}; // ... a second set: the out-projection's K slices stay live next to the FFN-down's
-  // precision = ESMDIFF_PRECISION_F32: float32 weights / activations (forward_strict); the bf16 members above stay null
+  // precision = ESMDIFF_PRECISION_F32: float32 weights / activations (forward_strict); the 16-bit workspace above stays null
   bool strict = false;
   // precision = ESMDIFF_PRECISION_F32_SPLIT: forward_strict with every large linear as three f16 MFMA passes over split
   // operands (gemm_split.hip); a2 / rs: the split activation rows feeding the next linear and their row scales
   bool split = false;
   bool f16 = false;          // precision = ESMDIFF_PRECISION_F16: the bf16 engine's launch sequence on the ed16 kernels
   bool head_split = false;   // bf16 engine with esmdiff_config.head_precision = 1: final LayerNorm + head on the split kernels
-  SplitW s_head0, s_head3, s_pl0, s_pl3, s_gproj, s_gout;
   uint16_t* a2 = nullptr;
   float* rs = nullptr;
   uint32_t* scratch_bits = nullptr;
-  float *fhead_w0 = nullptr, *fhead_w3 = nullptr, *fpl_w0 = nullptr, *fpl_w3 = nullptr, *fpw_down = nullptr;
-  float *fg_proj = nullptr, *fg_out = nullptr, *fgp = nullptr, *fgctx = nullptr;
-  float *fpw_l1 = nullptr, *fpw_l2 = nullptr, *fpair_x = nullptr, *fpair_h = nullptr;   // pairwise head in float32
+  float *fgp = nullptr, *fgctx = nullptr;
+  float *fpair_x = nullptr, *fpair_h = nullptr;   // pairwise head in float32
   float *fh = nullptr, *fh2 = nullptr, *fqkv = nullptr, *fq = nullptr, *fk = nullptr, *fctx = nullptr, *fgu = nullptr,   // (fgu: F32 engines only)
         *fmid = nullptr, *fpair_qk = nullptr;
   // step-0 sharing (esmdiff_set_step0_sharing): when every sample of a sampling call starts from identical inputs, the first
@@ -221,38 +227,58 @@ int need(esmdiff_engine* e, const Table& t, const std::string& name, std::initia
   return 0;
 }
 
-int load_f32(esmdiff_engine* e, const Table& t, const std::string& name, std::initializer_list<int64_t> shape, float** dst) {
+// vectors and embeddings: float32, the tail up to pad_to elements zero
+int load_f32(esmdiff_engine* e, const Table& t, const std::string& name, std::initializer_list<int64_t> shape, float** dst,
+             int64_t pad_to = 0) {
   const esmdiff_weight* w;
   if (int r = need(e, t, name, shape, &w)) return r;
-  if (int r = dalloc(e, dst, (size_t)numel(w))) return r;
-  HIP_TRY(e, launch_to_f32(w->data, w->dtype, *dst, numel(w), 0));
+  const int64_t n = numel(w), n_p = pad_to > n ? pad_to : n;
+  if (int r = dalloc(e, dst, (size_t)n_p, n_p != n)) return r;
+  HIP_TRY(e, launch_to_f32(w->data, w->dtype, *dst, n, 0));
   return 0;
 }
 
-int load_bf16(esmdiff_engine* e, const Table& t, const std::string& name, std::initializer_list<int64_t> shape,
-              bf16_t** dst, int64_t pad_rows_to = 0) {
+// A linear's weight [rows, K] into its slot in the given form.  W16 and SPLIT zero-pad the rows to pad_rows and, with
+// swiglu_h = FH, interleave the FFN-up's gate / up rows for the SwiGLU epilogue; F32 does neither (launch_gemm_f32 bounds
+// its rows and the SwiGLU is its own pass).  SPLIT: planes [rows_p, 3 K] + the inverse scale.
+int load_linear(esmdiff_engine* e, const Table& t, const std::string& name, std::initializer_list<int64_t> shape, Linear::Form form,
+                Linear* dst, int64_t pad_rows = 0, int swiglu_h = 0) {
   const esmdiff_weight* w;
   if (int r = need(e, t, name, shape, &w)) return r;
-  int64_t n = numel(w);
-  int64_t rows = w->shape[0], cols = n / rows;
-  int64_t rows_p = pad_rows_to > rows ? pad_rows_to : rows;
-  if (int r = dalloc(e, dst, (size_t)(rows_p * cols), rows_p != rows)) return r;
-  HIP_TRY(e, e->f16 ? ed16::launch_to_bf16(w->data, w->dtype, *dst, n, 0) : ed::launch_to_bf16(w->data, w->dtype, *dst, n, 0));   // the engine's 16-bit type
+  const int64_t n = numel(w), rows = w->shape[0], K = n / rows;
+  const int64_t rows_p = form != Linear::F32 && pad_rows > rows ? pad_rows : rows;
+  if (form == Linear::SPLIT) {
+    if (K % 128 || rows_p % 256) return fail(e, ESMDIFF_E_SHAPE, "weight '%s': [%lld, %lld] does not fit the split GEMM (rows %% 256, K %% 128)", name.c_str(), (long long)rows_p, (long long)K);
+    uint16_t* p;
+    if (int r = dalloc(e, &p, (size_t)(rows_p * 3 * K), rows_p != rows)) return r;
+    dst->w = p;
+    HIP_TRY(e, split_weight(w->data, w->dtype, p, rows, (int)K, e->scratch_bits, &dst->inv, swiglu_h));
+  } else if (form == Linear::F32) {
+    float* p;
+    if (int r = dalloc(e, &p, (size_t)n)) return r;
+    dst->w = p;
+    HIP_TRY(e, launch_to_f32(w->data, w->dtype, p, n, 0));
+  } else {
+    bf16_t* p;
+    if (int r = dalloc(e, &p, (size_t)(rows_p * K), rows_p != rows)) return r;
+    dst->w = p;
+    if (swiglu_h) {
+      if ((e->f16 ? ed16::launch_interleave_swiglu(w->data, w->dtype, p, swiglu_h, (int)K, 0) : ed::launch_interleave_swiglu(w->data, w->dtype, p, swiglu_h, (int)K, 0)) != hipSuccess)
+        return fail(e, ESMDIFF_E_HIP, "interleave_swiglu launch failed");
+    } else {
+      HIP_TRY(e, e->f16 ? ed16::launch_to_bf16(w->data, w->dtype, p, n, 0) : ed::launch_to_bf16(w->data, w->dtype, p, n, 0));
+    }
+  }
+  dst->form = form;
   return 0;
 }
 
-// precision = F32_SPLIT: a linear's weight as split f16 planes [rows padded to pad_rows_to, 2K] + its inverse scale
-int load_split(esmdiff_engine* e, const Table& t, const std::string& name, std::initializer_list<int64_t> shape, SplitW* dst,
-               int64_t pad_rows_to = 0, int interleave_h = 0) {
-  const esmdiff_weight* w;
-  if (int r = need(e, t, name, shape, &w)) return r;
-  const int64_t rows = w->shape[0], K = numel(w) / rows;
-  const int64_t rows_p = pad_rows_to > rows ? pad_rows_to : rows;
-  if (K % 128 || rows_p % 256) return fail(e, ESMDIFF_E_SHAPE, "weight '%s': [%lld, %lld] does not fit the split GEMM (rows %% 256, K %% 128)", name.c_str(), (long long)rows_p, (long long)K);
-  if (int r = dalloc(e, &dst->w, (size_t)(rows_p * 3 * K), rows_p != rows)) return r;
-  HIP_TRY(e, split_weight(w->data, w->dtype, dst->w, rows, (int)K, e->scratch_bits, &dst->inv, interleave_h));
-  return 0;
-}
+// The form of a group of weights, chosen once at create.  plain_form, the engine's non-split form: the pairwise head always, and
+// block 0's geometric pair unless BOTH its shapes fit the split GEMM (create_engine).  body_form: the block stack's linears and
+// the second (pLDDT / sequence) head's.  head_form: the output head's, SPLIT also under head_precision = 1.
+Linear::Form plain_form(const esmdiff_engine* e) { return e->strict ? Linear::F32 : Linear::W16; }
+Linear::Form body_form(const esmdiff_engine* e) { return e->split ? Linear::SPLIT : plain_form(e); }
+Linear::Form head_form(const esmdiff_engine* e) { return e->head_split ? Linear::SPLIT : body_form(e); }
 
 // RAII-less section timer: when profiling, records an event before/after each launch.
 struct Prof {
@@ -356,7 +382,7 @@ struct Part {
   const float *f_rot, *f_trans;
   const uint8_t* f_mask;
   const int32_t* lens;   // ragged batch: this sub-batch's lengths (device), else null
-  int B;
+  int b0, B;             // first sample of the sub-batch in the batch, and how many
   hipStream_t st;
   const ed::GemmWorkspace* gws;
   const ed::GemmWorkspace* gws2;
@@ -371,7 +397,7 @@ Part make_part(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, float
               e->gp ? e->gp + t0 * 15 * e->v_heads : nullptr, e->gctx ? e->gctx + t0 * 3 * e->v_heads : nullptr,
               e->a2 ? e->a2 + t0 * 3 * D : nullptr, e->rs ? e->rs + t0 : nullptr, e->fh2 ? e->fh2 + t0 * D : nullptr,
               e->f_rot ? e->f_rot + t0 * 9 : nullptr, e->f_trans ? e->f_trans + t0 * 3 : nullptr,
-              e->f_mask ? e->f_mask + t0 : nullptr, e->cur_lens ? e->cur_lens + b0 : nullptr, nb, st,
+              e->f_mask ? e->f_mask + t0 : nullptr, e->cur_lens ? e->cur_lens + b0 : nullptr, b0, nb, st,
               e->gemm_ws[queue].partial ? &e->gemm_ws[queue] : nullptr,
               e->gemm_ws2[queue].partial ? &e->gemm_ws2[queue] : nullptr};
 }
@@ -427,6 +453,21 @@ int shared_forward_batch(const esmdiff_engine* e, int B, int L) {
 // precision = F32: the same network in float32 end to end (csrc/strict.hip).  One stream, one launch per op, residual
 // adds in the branch GEMMs' epilogues as x + r / scaling_factor (esm's own expression).  Sections are timed like the
 // bf16 path's.  Block 0's geometric branch runs between the attention and the FFN branch while frames are set.
+// A forward on np launch queues — the caller's stream and side[0 .. np - 2]: the side streams start after everything enqueued
+// on the caller's stream so far (fork), and the caller's stream goes on after everything they ran (join).
+int fork_streams(esmdiff_engine* e, hipStream_t st, int np) {
+  if (np > 1) HIP_TRY(e, hipEventRecord(e->ev_fork, st));
+  for (int pi = 1; pi < np; ++pi) HIP_TRY(e, hipStreamWaitEvent(e->side[pi - 1], e->ev_fork, 0));
+  return 0;
+}
+int join_streams(esmdiff_engine* e, hipStream_t st, int np) {
+  for (int pi = 1; pi < np; ++pi) {
+    HIP_TRY(e, hipEventRecord(e->ev_join[pi - 1], e->side[pi - 1]));
+    HIP_TRY(e, hipStreamWaitEvent(st, e->ev_join[pi - 1], 0));
+  }
+  return 0;
+}
+
 struct SPart {   // one sub-batch of a strict forward: the engine's float32 workspace at a row offset, on its own stream
   const int64_t *seq, *xtok;
   float *x, *fh, *fh2, *fqkv, *fq, *fk, *fctx, *fgu, *fmid, *fgp, *fgctx, *fpair_qk, *logits, *pl_logits;   // fgu: F32 engines only
@@ -435,7 +476,7 @@ struct SPart {   // one sub-batch of a strict forward: the engine's float32 work
   const float *f_rot, *f_trans;
   const uint8_t* f_mask;
   const int32_t* lens;   // ragged batch: this sub-batch's lengths (device), else null
-  int B;
+  int b0, B;             // first sample of the sub-batch in the batch, and how many
   hipStream_t st;
 };
 
@@ -461,21 +502,23 @@ static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int
   Prof p{e, st};
   // K-sliced residual linears: only where the slicing constraints hold for this model (3 D / 3 and 3 FH / 4 multiples of 128)
   // this part's slice planes: the parts of a two-stream forward use disjoint regions (4 planes of its padded rows each)
-  float* const skp = e->sk_parts ? e->sk_parts + (size_t)4 * D * ((size_t)round_up((int)((w.x - e->x) / D), 256) + (w.x != e->x ? 256 : 0)) : nullptr;
+  float* const skp = e->sk_parts ? e->sk_parts + (size_t)4 * D * ((size_t)round_up(w.b0 * L, 256) + (w.b0 ? 256 : 0)) : nullptr;
   const bool sk = sp && e->splitk_small && e->sk_parts && M <= kSplitkMaxRows && e->kind == 0 && D % 128 == 0 && (3 * FH) % 512 == 0 &&
                   D >= 384 && 3 * FH / 4 >= 384;
   if (e->kind == 1) RUN(S_EMBED, launch_gather_rows(w.xtok, e->e_struct, w.x, M, D, ESMDIFF_VOCAB, st));
   else RUN(S_EMBED, launch_embed(w.seq, w.xtok, e->e_seq, e->e_struct, e->cvec, cond, w.x, B, L, D, st, e->sigma_rows > 1 ? D : 0));
-#define LIN(section, sw, fw, A32, lda, Kdim, out, bias, n_rows, ldc, n_valid, div, epi)                                  \
-  do {                                                                                                                   \
-    if (sp && (sw).w) RUN(section, launch_gemm256w4_split(a2, rs, (sw).w, (sw).inv, out, bias, M, round_up(n_rows, 256), Kdim, ldc, div, epi, st)); \
-    else RUN(section, launch_gemm_f32(A32, lda, fw, out, bias, M, n_rows, Kdim, ldc, n_valid, div, epi, st));             \
-  } while (0)
+  // a linear by its slot's form: SPLIT reads the split rows (a2, rs) the kernel before it wrote, F32 the float32 rows A32
+  auto lin = [&](int section, const Linear& W, const float* A32, int lda, int Kdim, float* out, const float* bias, int n_rows, int ldc,
+                 int n_valid, float div, int epi) -> int {
+    if (W.form == Linear::SPLIT) RUN(section, launch_gemm256w4_split(a2, rs, W.split(), W.inv, out, bias, M, round_up(n_rows, 256), Kdim, ldc, div, epi, st));
+    else RUN(section, launch_gemm_f32(A32, lda, W.f32(), out, bias, M, n_rows, Kdim, ldc, n_valid, div, epi, st));
+    return 0;
+  };
   for (int i = 0; i < c.n_layers; ++i) {
     const Layer& ly = e->layers[i];
     if (sp) RUN(S_LN, launch_layernorm_split(w.x, ly.ln1_w, ly.ln1_b, a2, rs, nullptr, M, D, 0, st));
     else RUN(S_LN, launch_layernorm_f32(w.x, ly.ln1_w, ly.ln1_b, w.fh, M, D, st));
-    LIN(S_QKV, ly.s_qkv, ly.fw_qkv, w.fh, D, D, w.fqkv, nullptr, 3 * D, 3 * D, 3 * D, 1.f, ESMDIFF_F32EPI_STORE);
+    if (int r = lin(S_QKV, ly.w_qkv, w.fh, D, D, w.fqkv, nullptr, 3 * D, 3 * D, 3 * D, 1.f, ESMDIFF_F32EPI_STORE)) return r;
     if (sp) {   // float32-grade attention on the f16 MFMA: q / k / v as [hi | lo] rows in fq / fk / fh (attention_split.hip)
       uint16_t *q2 = reinterpret_cast<uint16_t*>(w.fq), *k2 = reinterpret_cast<uint16_t*>(w.fk), *v2 = reinterpret_cast<uint16_t*>(w.fh);
       RUN(S_QKROPE, launch_qk_norm_rope_split(w.fqkv, ly.q_ln_w, ly.k_ln_w, e->rope_cos, e->rope_sin, q2, k2, B, L, H,
@@ -488,19 +531,19 @@ static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int
       RUN(S_ATTN, launch_attention_f32(w.fq, w.fk, w.fqkv, w.fctx, B, L, H, st, w.lens));
     }
     if (sk) {
-      RUN(S_OUT, launch_gemm256w4_splitk(a2, ly.s_out.w, ly.s_out.inv, skp, M, D, D, 3, st));
+      RUN(S_OUT, launch_gemm256w4_splitk(a2, ly.w_out.split(), ly.w_out.inv, skp, M, D, D, 3, st));
       RUN(S_OUT, launch_splitk_reduce_resid(skp, rs, w.x, M, D, 3, c.residue_scale, st));
     } else {
-      LIN(S_OUT, ly.s_out, ly.fw_out, w.fctx, D, D, w.x, nullptr, D, D, D, c.residue_scale, ESMDIFF_F32EPI_RESID_DIV);
+      if (int r = lin(S_OUT, ly.w_out, w.fctx, D, D, w.x, nullptr, D, D, D, c.residue_scale, ESMDIFF_F32EPI_RESID_DIV)) return r;
     }
     if (i == 0 && geom) {   // x = x + geom_attn(s_norm(x), frames) / scaling_factor
-      const bool gs = sp && e->s_gproj.w;
+      const bool gs = e->g_proj.form == Linear::SPLIT;   // (an F32_SPLIT engine whose v_heads do not fit runs this branch as F32)
       if (gs) RUN(S_LN, launch_layernorm_split(w.x, e->g_snorm_w, nullptr, a2, rs, nullptr, M, D, 0, st));
       else RUN(S_LN, launch_layernorm_f32(w.x, e->g_snorm_w, nullptr, w.fh, M, D, st));
-      LIN(S_ATTN, e->s_gproj, e->fg_proj, w.fh, D, D, w.fgp, nullptr, 15 * VH, 15 * VH, 15 * VH, 1.f, ESMDIFF_F32EPI_STORE);
+      if (int r = lin(S_ATTN, e->g_proj, w.fh, D, D, w.fgp, nullptr, 15 * VH, 15 * VH, 15 * VH, 1.f, ESMDIFF_F32EPI_STORE)) return r;
       RUN(S_ATTN, launch_geom_attention_f32(w.fgp, w.f_rot, w.f_trans, w.f_mask, e->g_wrot, e->g_wdist, w.fgctx, B, L, VH, st));
       if (gs) RUN(S_ATTN, launch_split_rows(w.fgctx, 3 * VH, a2, rs, M, 3 * VH, st));
-      LIN(S_ATTN, e->s_gout, e->fg_out, w.fgctx, 3 * VH, 3 * VH, w.x, nullptr, D, D, D, c.residue_scale, ESMDIFF_F32EPI_RESID_DIV);
+      if (int r = lin(S_ATTN, e->g_out, w.fgctx, 3 * VH, 3 * VH, w.x, nullptr, D, D, D, c.residue_scale, ESMDIFF_F32EPI_RESID_DIV)) return r;
     }
     if (sp) RUN(S_LN, launch_layernorm_split(w.x, ly.ln2_w, ly.ln2_b, a2, rs, nullptr, M, D, 0, st));
     else RUN(S_LN, launch_layernorm_f32(w.x, ly.ln2_w, ly.ln2_b, w.fh, M, D, st));
@@ -508,19 +551,19 @@ static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int
       // split FFN-up with the SwiGLU in its epilogue: reads the LayerNorm's split row (a2: [M, 3 D]), writes mid as f32 [M, FH];
       // split_rows then makes the FFN-down operand with every row's own power-of-two scale (r05: not a per-layer bound, see
       // gemm256w4.hip) — [M, 2 FH] of gate / up values never exist in memory
-      RUN(S_FFN_UP, launch_gemm256w4_split(a2, rs, ly.s_up.w, ly.s_up.inv, w.fmid, nullptr, M, 2 * FH, D, FH, 1.f, 4, st));
+      RUN(S_FFN_UP, launch_gemm256w4_split(a2, rs, ly.w_up.split(), ly.w_up.inv, w.fmid, nullptr, M, 2 * FH, D, FH, 1.f, 4, st));
       RUN(S_FFN_UP, launch_split_rows(w.fmid, FH, a2, rs, M, FH, st));
       if (sk) {
-        RUN(S_FFN_DOWN, launch_gemm256w4_splitk(a2, ly.s_down.w, ly.s_down.inv, skp, M, D, FH, 4, st));
+        RUN(S_FFN_DOWN, launch_gemm256w4_splitk(a2, ly.w_down.split(), ly.w_down.inv, skp, M, D, FH, 4, st));
         RUN(S_FFN_DOWN, launch_splitk_reduce_resid(skp, rs, w.x, M, D, 4, c.residue_scale, st));
       } else {
-        RUN(S_FFN_DOWN, launch_gemm256w4_split(a2, rs, ly.s_down.w, ly.s_down.inv, w.x, nullptr, M, D, FH, D,
+        RUN(S_FFN_DOWN, launch_gemm256w4_split(a2, rs, ly.w_down.split(), ly.w_down.inv, w.x, nullptr, M, D, FH, D,
                                                c.residue_scale, ESMDIFF_F32EPI_RESID_DIV, st));
       }
     } else {   // f32 engine: gate / up rows [M, 2 FH] in memory, SwiGLU as its own pass
-      RUN(S_FFN_UP, launch_gemm_f32(w.fh, D, ly.fw_up, w.fgu, nullptr, M, 2 * FH, D, 2 * FH, 2 * FH, 1.f, ESMDIFF_F32EPI_STORE, st));
+      RUN(S_FFN_UP, launch_gemm_f32(w.fh, D, ly.w_up.f32(), w.fgu, nullptr, M, 2 * FH, D, 2 * FH, 2 * FH, 1.f, ESMDIFF_F32EPI_STORE, st));
       RUN(S_FFN_UP, launch_swiglu_f32(w.fgu, w.fmid, M, FH, st));
-      RUN(S_FFN_DOWN, launch_gemm_f32(w.fmid, FH, ly.fw_down, w.x, nullptr, M, D, FH, D, D, c.residue_scale, ESMDIFF_F32EPI_RESID_DIV, st));
+      RUN(S_FFN_DOWN, launch_gemm_f32(w.fmid, FH, ly.w_down.f32(), w.x, nullptr, M, D, FH, D, D, c.residue_scale, ESMDIFF_F32EPI_RESID_DIV, st));
     }
   }
   if (sp) {
@@ -528,27 +571,26 @@ static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int
     // (the same erff expression on the same f32 value).  The final norm's f32 rows are kept only for the 128-wide pairwise
     // down-projection, which stays on the exact-f32 kernel.
     RUN(S_LN, launch_layernorm_split(w.x, e->final_ln_w, nullptr, a2, rs, e->has_pair ? w.fh : nullptr, M, D, 0, st));
-    RUN(S_HEAD, launch_gemm256w4_split(a2, rs, e->s_head0.w, e->s_head0.inv, w.fh2, e->head_b0, M, D, D, D, 1.f, ESMDIFF_F32EPI_STORE, st));
-    if (e->has_plddt) RUN(S_HEAD, launch_gemm256w4_split(a2, rs, e->s_pl0.w, e->s_pl0.inv, w.fctx, e->pl_b0, M, D, D, D, 1.f, ESMDIFF_F32EPI_STORE, st));
-    if (e->has_pair) RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->fpw_down, w.fpair_qk, nullptr, M, 128, D, 128, 128, 1.f, ESMDIFF_F32EPI_STORE, st));
+    RUN(S_HEAD, launch_gemm256w4_split(a2, rs, e->head_w0.split(), e->head_w0.inv, w.fh2, e->head_b0, M, D, D, D, 1.f, ESMDIFF_F32EPI_STORE, st));
+    if (e->has_plddt) RUN(S_HEAD, launch_gemm256w4_split(a2, rs, e->pl_w0.split(), e->pl_w0.inv, w.fctx, e->pl_b0, M, D, D, D, 1.f, ESMDIFF_F32EPI_STORE, st));
+    if (e->has_pair) RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->pw_down.f32(), w.fpair_qk, nullptr, M, 128, D, 128, 128, 1.f, ESMDIFF_F32EPI_STORE, st));
     RUN(S_LN, launch_layernorm_split(w.fh2, e->head_ln_w, e->head_ln_b, a2, rs, nullptr, M, D, 1, st));
-    RUN(S_HEAD, launch_gemm256w4_split(a2, rs, e->s_head3.w, e->s_head3.inv, logits, e->head_b3, M, e->vocab_pad, D, ld, 1.f, ESMDIFF_F32EPI_STORE, st));
+    RUN(S_HEAD, launch_gemm256w4_split(a2, rs, e->head_w3.split(), e->head_w3.inv, logits, e->head_b3, M, e->vocab_pad, D, ld, 1.f, ESMDIFF_F32EPI_STORE, st));
     if (e->has_plddt) {
       RUN(S_LN, launch_layernorm_split(w.fctx, e->pl_ln_w, e->pl_ln_b, a2, rs, nullptr, M, D, 1, st));
-      RUN(S_HEAD, launch_gemm256w4_split(a2, rs, e->s_pl3.w, e->s_pl3.inv, w.pl_logits, e->pl_b3, M, 256, D, e->ld_plddt, 1.f, ESMDIFF_F32EPI_STORE, st));
+      RUN(S_HEAD, launch_gemm256w4_split(a2, rs, e->pl_w3.split(), e->pl_w3.inv, w.pl_logits, e->pl_b3, M, 256, D, e->ld_plddt, 1.f, ESMDIFF_F32EPI_STORE, st));
     }
     return 0;
   }
-#undef LIN
   RUN(S_LN, launch_layernorm_f32(w.x, e->final_ln_w, nullptr, w.fh, M, D, st));
-  RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->fhead_w0, w.fh2, e->head_b0, M, D, D, D, D, 1.f, ESMDIFF_F32EPI_BIAS_GELU, st));
-  if (e->has_plddt) RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->fpl_w0, w.fctx, e->pl_b0, M, D, D, D, D, 1.f, ESMDIFF_F32EPI_BIAS_GELU, st));
+  RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->head_w0.f32(), w.fh2, e->head_b0, M, D, D, D, D, 1.f, ESMDIFF_F32EPI_BIAS_GELU, st));
+  if (e->has_plddt) RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->pl_w0.f32(), w.fctx, e->pl_b0, M, D, D, D, D, 1.f, ESMDIFF_F32EPI_BIAS_GELU, st));
   if (e->has_pair)     // the pairwise confidence head's down-projection (q | k, 64 + 64 columns per token), float32 like the rest
-    RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->fpw_down, w.fpair_qk, nullptr, M, 128, D, 128, 128, 1.f, ESMDIFF_F32EPI_STORE, st));
+    RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->pw_down.f32(), w.fpair_qk, nullptr, M, 128, D, 128, 128, 1.f, ESMDIFF_F32EPI_STORE, st));
   RUN(S_LN, launch_layernorm_f32(w.fh2, e->head_ln_w, e->head_ln_b, w.fh, M, D, st));
   if (e->has_plddt) RUN(S_LN, launch_layernorm_f32(w.fctx, e->pl_ln_w, e->pl_ln_b, w.fq, M, D, st));
-  RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->fhead_w3, logits, e->head_b3, M, c.vocab_out, D, ld, c.vocab_out, 1.f, ESMDIFF_F32EPI_STORE, st));
-  if (e->has_plddt) RUN(S_HEAD, launch_gemm_f32(w.fq, D, e->fpl_w3, w.pl_logits, e->pl_b3, M, e->plddt_bins, D, e->ld_plddt, e->plddt_bins, 1.f, ESMDIFF_F32EPI_STORE, st));
+  RUN(S_HEAD, launch_gemm_f32(w.fh, D, e->head_w3.f32(), logits, e->head_b3, M, c.vocab_out, D, ld, c.vocab_out, 1.f, ESMDIFF_F32EPI_STORE, st));
+  if (e->has_plddt) RUN(S_HEAD, launch_gemm_f32(w.fq, D, e->pl_w3.f32(), w.pl_logits, e->pl_b3, M, e->plddt_bins, D, e->ld_plddt, e->plddt_bins, 1.f, ESMDIFF_F32EPI_STORE, st));
   return 0;
 }
 
@@ -580,21 +622,12 @@ int forward_strict(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, c
                       off(e->fctx, D), off(e->fgu, 2 * FH), off(e->fmid, FH), off(e->fgp, 15 * e->v_heads), off(e->fgctx, 3 * e->v_heads),
                       off(e->fpair_qk, 128), logits + t0 * ld, off(e->pl_logits, e->ld_plddt), e->a2 ? e->a2 + t0 * WS : nullptr,
                       e->rs ? e->rs + t0 : nullptr, e->f_rot ? e->f_rot + t0 * 9 : nullptr, e->f_trans ? e->f_trans + t0 * 3 : nullptr,
-                      e->f_mask ? e->f_mask + t0 : nullptr, e->cur_lens ? e->cur_lens + b0 : nullptr, b1 - b0, pi == 0 ? st : e->side[pi - 1]};
+                      e->f_mask ? e->f_mask + t0 : nullptr, e->cur_lens ? e->cur_lens + b0 : nullptr, b0, b1 - b0, pi == 0 ? st : e->side[pi - 1]};
   }
-  if (np > 1) {
-    HIP_TRY(e, hipEventRecord(e->ev_fork, st));
-    HIP_TRY(e, hipStreamWaitEvent(e->side[0], e->ev_fork, 0));
-  }
-  for (int pi = 0; pi < np; ++pi) {   // (per-sample sigmas: the part's first conditioning row)
-    const int64_t b0 = (int64_t)B * pi / np;
-    if (int r = strict_part(e, parts[pi], cond && e->sigma_rows > 1 ? cond + b0 * D : cond, ld, L)) return r;
-  }
-  if (np > 1) {
-    HIP_TRY(e, hipEventRecord(e->ev_join[0], e->side[0]));
-    HIP_TRY(e, hipStreamWaitEvent(st, e->ev_join[0], 0));
-  }
-  return 0;
+  if (int r = fork_streams(e, st, np)) return r;
+  for (int pi = 0; pi < np; ++pi)   // (per-sample sigmas: the part's first conditioning row)
+    if (int r = strict_part(e, parts[pi], cond && e->sigma_rows > 1 ? cond + (int64_t)parts[pi].b0 * D : cond, ld, L)) return r;
+  return join_streams(e, st, np);
 }
 
 #define KN ed
@@ -863,6 +896,7 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
   if (cfg->head_precision != 0 && cfg->head_precision != 1)
     return (delete e, fail(nullptr, ESMDIFF_E_INVALID, "head_precision %d: 0 (as precision) or 1 (float32 grade)", cfg->head_precision));
   const bool strict = e->strict, split = e->split, head_split = e->head_split;
+  const Linear::Form bf = body_form(e), hf = head_form(e), pf = plain_form(e);
   if (split && (D % 128 || FH % 128))
     return (delete e, fail(nullptr, ESMDIFF_E_INVALID, "precision F32_SPLIT needs d_model and ffn_hidden to be multiples of 128"));
   auto bail = [&](int code) {
@@ -894,11 +928,7 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     const std::string b = stack + "blocks." + std::to_string(i) + ".";
     TRY(load_f32(e, t, b + "attn.layernorm_qkv.0.weight", {D}, &ly.ln1_w));
     TRY(load_f32(e, t, b + "attn.layernorm_qkv.0.bias", {D}, &ly.ln1_b));
-    ly.w_qkv = ly.w_out = ly.w_up = ly.w_down = nullptr;
-    ly.fw_qkv = ly.fw_out = ly.fw_up = ly.fw_down = nullptr;
-    if (split) TRY(load_split(e, t, b + "attn.layernorm_qkv.1.weight", {3 * D, D}, &ly.s_qkv));
-    else if (strict) TRY(load_f32(e, t, b + "attn.layernorm_qkv.1.weight", {3 * D, D}, &ly.fw_qkv));
-    else TRY(load_bf16(e, t, b + "attn.layernorm_qkv.1.weight", {3 * D, D}, &ly.w_qkv));
+    TRY(load_linear(e, t, b + "attn.layernorm_qkv.1.weight", {3 * D, D}, bf, &ly.w_qkv));
     TRY(load_f32(e, t, b + "attn.q_ln.weight", {D}, &ly.q_ln_w));
     TRY(load_f32(e, t, b + "attn.k_ln.weight", {D}, &ly.k_ln_w));
     if (split) {   // |q|, |k| <= sqrt(2 (D - 1)) max|ln weight| (LayerNorm + rotation); |v| <= (sqrt(D) max|g| + |b|_2) max_row |W_v row|_2
@@ -922,45 +952,22 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
       ly.att_qk = pow2_below(30000.f / (sqrtf(2.f * D) * wmax));
       ly.att_v = pow2_below(30000.f / ((sqrtf((float)D) * gmax + sqrtf(b2)) * rn));
     }
-    if (split) TRY(load_split(e, t, b + "attn.out_proj.weight", {D, D}, &ly.s_out));
-    else if (strict) TRY(load_f32(e, t, b + "attn.out_proj.weight", {D, D}, &ly.fw_out));
-    else TRY(load_bf16(e, t, b + "attn.out_proj.weight", {D, D}, &ly.w_out));
+    TRY(load_linear(e, t, b + "attn.out_proj.weight", {D, D}, bf, &ly.w_out));
     TRY(load_f32(e, t, b + "ffn.0.weight", {D}, &ly.ln2_w));
     TRY(load_f32(e, t, b + "ffn.0.bias", {D}, &ly.ln2_b));
-    if (split) {
-      // FFN-up with the SwiGLU fused into the split GEMM's epilogue (rows interleaved gate / up; mid leaves it as f32 and is split
-      // with its row's own scale, forward_strict)
-      TRY(load_split(e, t, b + "ffn.1.weight", {2 * FH, D}, &ly.s_up, 0, FH));
-      TRY(load_split(e, t, b + "ffn.3.weight", {D, FH}, &ly.s_down));
-    } else if (strict) {
-      TRY(load_f32(e, t, b + "ffn.1.weight", {2 * FH, D}, &ly.fw_up));
-      TRY(load_f32(e, t, b + "ffn.3.weight", {D, FH}, &ly.fw_down));
-    } else {
-      const esmdiff_weight* w;
-      TRY(need(e, t, b + "ffn.1.weight", {2 * FH, D}, &w));
-      TRY(dalloc(e, &ly.w_up, (size_t)2 * FH * D));
-      if ((e->f16 ? ed16::launch_interleave_swiglu(w->data, w->dtype, ly.w_up, FH, D, 0) : ed::launch_interleave_swiglu(w->data, w->dtype, ly.w_up, FH, D, 0)) != hipSuccess)
-        return bail(fail(e, ESMDIFF_E_HIP, "interleave_swiglu launch failed"));
-      TRY(load_bf16(e, t, b + "ffn.3.weight", {D, FH}, &ly.w_down));
-    }
+    // FFN-up with the SwiGLU in the GEMM's epilogue: rows interleaved gate / up (W16, and SPLIT: mid leaves it as f32 and is split
+    // with its row's own scale, forward_strict); F32 keeps the checkpoint's order
+    TRY(load_linear(e, t, b + "ffn.1.weight", {2 * FH, D}, bf, &ly.w_up, 0, FH));
+    TRY(load_linear(e, t, b + "ffn.3.weight", {D, FH}, bf, &ly.w_down));
   }
   TRY(load_f32(e, t, stack + "norm.weight", {D}, &e->final_ln_w));
-  if (split || head_split) TRY(load_split(e, t, head0 + "weight", {D, D}, &e->s_head0));
-  else if (strict) TRY(load_f32(e, t, head0 + "weight", {D, D}, &e->fhead_w0));
-  else TRY(load_bf16(e, t, head0 + "weight", {D, D}, &e->head_w0));
+  TRY(load_linear(e, t, head0 + "weight", {D, D}, hf, &e->head_w0));
   TRY(load_f32(e, t, head0 + "bias", {D}, &e->head_b0));
   TRY(load_f32(e, t, head2 + "weight", {D}, &e->head_ln_w));
   TRY(load_f32(e, t, head2 + "bias", {D}, &e->head_ln_b));
   e->vocab_pad = round_up(V, 256);  // 4101 -> 4352: 17 column tiles of the 256x256 kernel (the 128x128 kernel took 0.40 ms at M = 25 800)
-  if (split || head_split) TRY(load_split(e, t, head3 + "weight", {V, D}, &e->s_head3, e->vocab_pad));
-  else if (strict) TRY(load_f32(e, t, head3 + "weight", {V, D}, &e->fhead_w3));
-  else TRY(load_bf16(e, t, head3 + "weight", {V, D}, &e->head_w3, e->vocab_pad));
-  {
-    const esmdiff_weight* w;
-    TRY(need(e, t, head3 + "bias", {V}, &w));
-    TRY(dalloc(e, &e->head_b3, (size_t)e->vocab_pad, true));
-    if (launch_to_f32(w->data, w->dtype, e->head_b3, V, 0) != hipSuccess) return bail(fail(e, ESMDIFF_E_HIP, "to_f32 failed"));
-  }
+  TRY(load_linear(e, t, head3 + "weight", {V, D}, hf, &e->head_w3, e->vocab_pad));
+  TRY(load_f32(e, t, head3 + "bias", {V}, &e->head_b3, e->vocab_pad));
   if (kind == 1) TRY(load_f32(e, t, "embed.weight", {ESMDIFF_VOCAB, D}, &e->e_struct));
   {
     // A second RegressionHead(d, n) (Linear, GELU, LayerNorm, Linear) on the same normalised hidden state: the decoder's pLDDT
@@ -974,34 +981,24 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
       if (head_split) return bail(fail(e, ESMDIFF_E_INVALID, "a sequence head and head_precision = 1 together are not built: use precision f32 / f32_split or head_precision 0"));
       e->plddt_bins = nb;
       e->ld_plddt = split ? 256 : round_up(nb, 4);   // the split GEMM has no column bound: its output row holds all N_pad columns
-      if (split) TRY(load_split(e, t, sh + "0.weight", {D, D}, &e->s_pl0));
-      else if (strict) TRY(load_f32(e, t, sh + "0.weight", {D, D}, &e->fpl_w0));
-      else TRY(load_bf16(e, t, sh + "0.weight", {D, D}, &e->pl_w0));
+      TRY(load_linear(e, t, sh + "0.weight", {D, D}, bf, &e->pl_w0));
       TRY(load_f32(e, t, sh + "0.bias", {D}, &e->pl_b0));
       TRY(load_f32(e, t, sh + "2.weight", {D}, &e->pl_ln_w));
       TRY(load_f32(e, t, sh + "2.bias", {D}, &e->pl_ln_b));
-      if (split) TRY(load_split(e, t, sh + "3.weight", {nb, D}, &e->s_pl3, 256));
-      else if (strict) TRY(load_f32(e, t, sh + "3.weight", {nb, D}, &e->fpl_w3));
-      else TRY(load_bf16(e, t, sh + "3.weight", {nb, D}, &e->pl_w3, 128));
-      const esmdiff_weight* w;
-      TRY(need(e, t, sh + "3.bias", {nb}, &w));
-      TRY(dalloc(e, &e->pl_b3, (size_t)128, true));
-      if (launch_to_f32(w->data, w->dtype, e->pl_b3, nb, 0) != hipSuccess) return bail(fail(e, ESMDIFF_E_HIP, "to_f32 failed"));
+      TRY(load_linear(e, t, sh + "3.weight", {nb, D}, bf, &e->pl_w3, split ? 256 : 128));   // one column tile of its GEMM
+      TRY(load_f32(e, t, sh + "3.bias", {nb}, &e->pl_b3, 128));
       e->has_plddt = true;
     }
   }
   if (kind == 1) {
     if (t.find("pairwise_classification_head.linear2.weight")) {
       const std::string ph = "pairwise_classification_head.";
-      if (strict) TRY(load_f32(e, t, ph + "downproject.weight", {128, D}, &e->fpw_down));
-      else TRY(load_bf16(e, t, ph + "downproject.weight", {128, D}, &e->pw_down));
-      if (strict) TRY(load_f32(e, t, ph + "linear1.weight", {128, 128}, &e->fpw_l1));
-      else TRY(load_bf16(e, t, ph + "linear1.weight", {128, 128}, &e->pw_l1));
+      TRY(load_linear(e, t, ph + "downproject.weight", {128, D}, pf, &e->pw_down));
+      TRY(load_linear(e, t, ph + "linear1.weight", {128, 128}, pf, &e->pw_l1));
       TRY(load_f32(e, t, ph + "norm.weight", {128}, &e->pw_ln_w));
       TRY(load_f32(e, t, ph + "norm.bias", {128}, &e->pw_ln_b));
-      // rows [distogram 64 | direction 96 | PAE 64]; padded so that the 128-row GEMM tile starting at row 160 stays inside
-      if (strict) TRY(load_f32(e, t, ph + "linear2.weight", {224, 128}, &e->fpw_l2));
-      else TRY(load_bf16(e, t, ph + "linear2.weight", {224, 128}, &e->pw_l2, 384));
+      // rows [distogram 64 | direction 96 | PAE 64]; padded so that the 128-row W16 GEMM tile starting at row 160 stays inside
+      TRY(load_linear(e, t, ph + "linear2.weight", {224, 128}, pf, &e->pw_l2, 384));
       TRY(dalloc(e, &e->zeros128, (size_t)128, true));
       e->has_pair = true;
     }
@@ -1022,16 +1019,9 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     if (VH <= 0 || (15 * VH) % 128 || (3 * VH) % 64) return bail(fail(e, ESMDIFF_E_INVALID, "geom_attn v_heads=%d unsupported", VH));
     e->v_heads = VH;
     TRY(load_f32(e, t, ga + "s_norm.weight", {D}, &e->g_snorm_w));
-    if (split && (15 * VH) % 256 == 0 && (3 * VH) % 128 == 0) {
-      TRY(load_split(e, t, ga + "proj.weight", {15 * VH, D}, &e->s_gproj));
-      TRY(load_split(e, t, ga + "out_proj.weight", {D, 3 * VH}, &e->s_gout));
-    } else if (strict) {
-      TRY(load_f32(e, t, ga + "proj.weight", {15 * VH, D}, &e->fg_proj));
-      TRY(load_f32(e, t, ga + "out_proj.weight", {D, 3 * VH}, &e->fg_out));
-    } else {
-      TRY(load_bf16(e, t, ga + "proj.weight", {15 * VH, D}, &e->g_proj));
-      TRY(load_bf16(e, t, ga + "out_proj.weight", {D, 3 * VH}, &e->g_out));
-    }
+    const Linear::Form gf = split && (15 * VH) % 256 == 0 && (3 * VH) % 128 == 0 ? Linear::SPLIT : pf;
+    TRY(load_linear(e, t, ga + "proj.weight", {15 * VH, D}, gf, &e->g_proj));
+    TRY(load_linear(e, t, ga + "out_proj.weight", {D, 3 * VH}, gf, &e->g_out));
     TRY(load_f32(e, t, ga + "rotation_scale_per_head", {VH}, &e->g_wrot));
     TRY(load_f32(e, t, ga + "distance_scale_per_head", {VH}, &e->g_wdist));
     if (hipDeviceSynchronize() != hipSuccess) return bail(fail(e, ESMDIFF_E_HIP, "geom weight conversion failed"));
@@ -1238,17 +1228,17 @@ static int pairwise_confidence(esmdiff_engine* e, const int64_t* tokens, float* 
     if (rows > 0x7fffffffll) return fail(e, ESMDIFF_E_INVALID, "pairwise head: too many pair rows in one chunk");
     if (e->strict) {   // linear1 -> GELU -> LayerNorm -> linear2[PAE rows 160..223], all float32 (no biases in this head)
       HIP_TRY(e, launch_pair_features_f32(e->fpair_qk + (int64_t)b0 * L * 128, e->fpair_x, nb, L, st));
-      HIP_TRY(e, launch_gemm_f32(e->fpair_x, 128, e->fpw_l1, e->fpair_h, nullptr, (int)rows, 128, 128, 128, 128, 1.f, ESMDIFF_F32EPI_BIAS_GELU, st));
+      HIP_TRY(e, launch_gemm_f32(e->fpair_x, 128, e->pw_l1.f32(), e->fpair_h, nullptr, (int)rows, 128, 128, 128, 128, 1.f, ESMDIFF_F32EPI_BIAS_GELU, st));
       HIP_TRY(e, launch_layernorm_f32(e->fpair_h, e->pw_ln_w, e->pw_ln_b, e->fpair_x, (int)rows, 128, st));
-      HIP_TRY(e, launch_gemm_f32(e->fpair_x, 128, e->fpw_l2 + 160 * 128, e->pair_logits, nullptr, (int)rows, 64, 128, 64, 64, 1.f, ESMDIFF_F32EPI_STORE, st));
+      HIP_TRY(e, launch_gemm_f32(e->fpair_x, 128, e->pw_l2.f32() + 160 * 128, e->pair_logits, nullptr, (int)rows, 64, 128, 64, 64, 1.f, ESMDIFF_F32EPI_STORE, st));
       HIP_TRY(e, launch_pae_tm(e->pair_logits, tokens + (int64_t)b0 * L, e->tm_rows + (int64_t)b0 * L, pae ? pae + (int64_t)b0 * LL : nullptr,
                                ptm + b0, nb, L, 31.0f, st));
       continue;
     }
     HIP_TRY(e, launch_pair_features(e->pair_qk + (int64_t)b0 * L * 128, e->pair_x, nb, L, st));
-    HIP_TRY(e, launch_gemm_bf16(e->pair_x, e->pw_l1, e->pair_h, e->zeros128, (int)rows, 128, 128, 128, 128, 1.f, ESMDIFF_EPI_BIAS_GELU_BF16, st));
+    HIP_TRY(e, launch_gemm_bf16(e->pair_x, e->pw_l1.w16(), e->pair_h, e->zeros128, (int)rows, 128, 128, 128, 128, 1.f, ESMDIFF_EPI_BIAS_GELU_BF16, st));
     HIP_TRY(e, launch_layernorm_bf16_in(e->pair_h, e->pw_ln_w, e->pw_ln_b, e->pair_x, (int)rows, 128, st));
-    HIP_TRY(e, launch_gemm_bf16(e->pair_x, e->pw_l2 + 160 * 128, e->pair_logits, e->zeros128, (int)rows, 128, 128, 64, 64, 1.f, ESMDIFF_EPI_BIAS_F32, st));
+    HIP_TRY(e, launch_gemm_bf16(e->pair_x, e->pw_l2.w16() + 160 * 128, e->pair_logits, e->zeros128, (int)rows, 128, 128, 64, 64, 1.f, ESMDIFF_EPI_BIAS_F32, st));
     HIP_TRY(e, launch_pae_tm(e->pair_logits, tokens + (int64_t)b0 * L, e->tm_rows + (int64_t)b0 * L, pae ? pae + (int64_t)b0 * LL : nullptr,
                              ptm + b0, nb, L, 31.0f, st));
   }
