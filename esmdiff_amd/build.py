@@ -22,6 +22,10 @@ INCLUDE = PKG.parent / "include"
 
 UNITS = {
     "engine": [],
+    "engine_forward": [],
+    "engine_sample": [],
+    "engine_decode": [],
+    "engine_test": [],
     "gemm": [],
     "gemm256w4": [],
     "gemm256w4_split": [],    # f16 plane triples whatever the 16-bit operand type: not in F16_UNITS

@@ -1,5 +1,5 @@
 // engine_forward.inc — the launch sequence of one forward of the 16-bit-operand engine (bf16 or f16), included twice by
-// engine.hip with KN = ed (the bf16 build of the kernels) and KN = ed16 (the f16 build of the same sources, ed_half.h); the
+// engine_forward.hip with KN = ed (the bf16 build of the kernels) and KN = ed16 (the f16 build of the same sources, ed_half.h); the
 // split head (gemm_split.hip) and the few f32-only kernels exist once and resolve through either namespace's declarations.
 static int ED_FWD_NAME(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, const float* t_freq_dev, float* logits,
                        int ld, int B, int L, hipStream_t st) {

@@ -1,0 +1,242 @@
+// engine_test.hip — the kernel-level entries of include/esmdiff_hip_test.h: single launchers behind a C signature, for the test
+// suite and the measurement tools.  No product path calls them.
+#include "engine.h"
+
+using namespace ed;
+using namespace eng;
+
+// The result of a test entry's launch: 0, or the launcher's error with hipErrorInvalidValue (a shape it refuses) as the caller's.
+static int launched(esmdiff_engine* e, hipError_t s, const char* name) {
+  if (s == hipSuccess) return 0;
+  return fail(e, s == hipErrorInvalidValue ? ESMDIFF_E_INVALID : ESMDIFF_E_HIP, "%s: %s", name, hipGetErrorString(s));
+}
+
+extern "C" {
+
+int esmdiff_gemm_bf16(const void* A, const void* W, void* out, const float* bias, int32_t M, int32_t N, int32_t K,
+                      int32_t ldc, int32_t n_valid, float alpha, int32_t epilogue, void* stream) {
+  if (!A || !W || !out) return ESMDIFF_E_INVALID;
+  hipError_t s = launch_gemm_bf16((const bf16_t*)A, (const bf16_t*)W, out, bias, M, N, K, ldc, n_valid, alpha, epilogue,
+                                  (hipStream_t)stream);
+  return launched(nullptr, s, "gemm");
+}
+
+int esmdiff_gemm_f16(const void* A, const void* W, void* out, const float* bias, int32_t M, int32_t N, int32_t K,
+                     int32_t ldc, int32_t n_valid, float alpha, int32_t epilogue, void* stream) {
+  if (!A || !W || !out) return ESMDIFF_E_INVALID;
+  hipError_t s = ed16::launch_gemm_bf16((const bf16_t*)A, (const bf16_t*)W, out, bias, M, N, K, ldc, n_valid, alpha, epilogue,
+                                        (hipStream_t)stream);
+  return launched(nullptr, s, "gemm_f16");
+}
+
+int esmdiff_gemm_f32(const float* A, int32_t lda, const float* W, float* out, const float* bias, int32_t M, int32_t N,
+                     int32_t K, int32_t ldc, int32_t n_valid, float div, int32_t epilogue, void* stream) {
+  if (!A || !W || !out) return ESMDIFF_E_INVALID;
+  hipError_t s = launch_gemm_f32(A, lda, W, out, bias, M, N, K, ldc, n_valid, div, epilogue, (hipStream_t)stream);
+  return launched(nullptr, s, "gemm_f32");
+}
+
+int esmdiff_split_rows(const float* src, int32_t ld, void* a2, float* rs, int32_t M, int32_t K, void* stream) {
+  if (!src || !a2 || !rs) return ESMDIFF_E_INVALID;
+  hipError_t s = launch_split_rows(src, ld, (uint16_t*)a2, rs, M, K, (hipStream_t)stream);
+  return launched(nullptr, s, "split_rows");
+}
+
+int esmdiff_split_weight(const float* src, void* w2, int32_t N, int32_t N_pad, int32_t K, float* inv_scale_out) {
+  if (!src || !w2 || !inv_scale_out || N <= 0 || N_pad < N || N_pad % 256 || K <= 0 || K % 128) return ESMDIFF_E_INVALID;
+  uint32_t* bits = nullptr;
+  if (hipMalloc(&bits, 4) != hipSuccess) return fail(nullptr, ESMDIFF_E_HIP, "split_weight: hipMalloc failed");
+  hipError_t s = hipSuccess;
+  if (N_pad > N) s = hipMemset((uint16_t*)w2 + (size_t)N * 3 * K, 0, (size_t)(N_pad - N) * 3 * K * 2);
+  if (s == hipSuccess) s = split_weight(src, ESMDIFF_F32, (uint16_t*)w2, N, K, bits, inv_scale_out);
+  if (s == hipSuccess) s = hipDeviceSynchronize();
+  hipFree(bits);
+  if (s != hipSuccess) return fail(nullptr, ESMDIFF_E_HIP, "split_weight: %s", hipGetErrorString(s));
+  return 0;
+}
+
+int esmdiff_gemm_split(const void* a2, const float* rs, const void* w2, float w_inv_scale, float* out, const float* bias,
+                       int32_t M, int32_t N, int32_t K, int32_t ldc, float div, int32_t epilogue, void* stream) {
+  if (!a2 || !w2 || !out) return ESMDIFF_E_INVALID;
+  hipError_t s = launch_gemm256w4_split((const uint16_t*)a2, rs, (const uint16_t*)w2, w_inv_scale, out, bias, M, N, K, ldc, div,
+                                        epilogue, (hipStream_t)stream);
+  return launched(nullptr, s, "gemm_split");
+}
+
+int esmdiff_gemm_bf16_ws(esmdiff_engine* e, const void* A, const void* W, void* out, const float* bias, int32_t M,
+                         int32_t N, int32_t K, int32_t ldc, int32_t n_valid, float alpha, int32_t epilogue, void* stream) {
+  if (!e || !A || !W || !out) return ESMDIFF_E_INVALID;
+  hipError_t s = launch_gemm_bf16((const bf16_t*)A, (const bf16_t*)W, out, bias, M, N, K, ldc, n_valid, alpha, epilogue,
+                                  (hipStream_t)stream, e->gemm_ws[0].partial ? &e->gemm_ws[0] : nullptr);
+  return launched(e, s, "gemm");
+}
+
+int esmdiff_describe_gemm_choice(int32_t M, int32_t N, int32_t K, int64_t ws_floats, int32_t* w4_out, int32_t* rows_out,
+                                 int32_t* splits_out, int32_t* stages_out) {
+  if (!w4_out || !rows_out || !splits_out || !stages_out || M <= 0 || N <= 0 || K <= 0 || N % 128 || K % 64 || ws_floats < 0)
+    return ESMDIFF_E_INVALID;
+  int w4 = 0, rows = 0, S = 0, stages = 0;
+  ed::describe_gemm_choice(M, N, K, (size_t)ws_floats, &w4, &rows, &S, &stages);
+  *w4_out = w4;
+  *rows_out = rows;
+  *splits_out = S;
+  *stages_out = stages;
+  return 0;
+}
+
+int esmdiff_gemm_workspace_floats(const esmdiff_engine* e, int64_t* floats_out) {
+  if (!e || !floats_out) return ESMDIFF_E_INVALID;
+  *floats_out = e->gemm_ws[0].partial ? (int64_t)e->gemm_ws[0].partial_floats : 0;
+  return 0;
+}
+
+#ifdef ED_DEBUG   // measurement aid (scratch/bench_gemm.py), not a switch
+int esmdiff_gemm_bf16_timed(const void* A, const void* W, void* out, const float* bias, int32_t M, int32_t N,
+                            int32_t K, int32_t ldc, int32_t n_valid, float alpha, int32_t epilogue, int32_t iters,
+                            float* ms_out, void* stream) {
+  if (!ms_out || iters <= 0) return ESMDIFF_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  hipEvent_t a, b;
+  hipEventCreate(&a);
+  hipEventCreate(&b);
+  int r = esmdiff_gemm_bf16(A, W, out, bias, M, N, K, ldc, n_valid, alpha, epilogue, stream);  // warm-up
+  hipEventRecord(a, st);
+  for (int i = 0; i < iters && r == 0; ++i) r = esmdiff_gemm_bf16(A, W, out, bias, M, N, K, ldc, n_valid, alpha, epilogue, stream);
+  hipEventRecord(b, st);
+  hipEventSynchronize(b);
+  float ms = 0;
+  hipEventElapsedTime(&ms, a, b);
+  *ms_out = ms / iters;
+  hipEventDestroy(a);
+  hipEventDestroy(b);
+  return r;
+}
+#endif  // ED_DEBUG
+
+int esmdiff_branch_linear_layernorm(esmdiff_engine* e, const void* A, const void* W, float* x, float alpha, const float* w,
+                                    const float* b, void* y, int32_t M, int32_t N, int32_t K, int32_t* splits_out,
+                                    void* stream) {
+  if (!e || !A || !W || !x || !w || !y) return ESMDIFF_E_INVALID;
+  if (!e->gemm_ws[0].partial) return fail(e, ESMDIFF_E_INVALID, "engine has no split-K workspace (f32 / f32_split engines have none)");
+  ed::GemmPartials P{};
+  hipError_t s = launch_gemm_partials((const bf16_t*)A, (const bf16_t*)W, &e->gemm_ws[0], M, N, K, (hipStream_t)stream, &P);
+  if (s == hipSuccess) s = launch_add_partials_layernorm_bf16(x, P, N, alpha, w, b, (bf16_t*)y, M, N, (hipStream_t)stream);
+  if (int r = launched(e, s, "branch linear + layernorm")) return r;
+  if (splits_out) *splits_out = P.S;
+  return 0;
+}
+
+int esmdiff_layernorm_bf16(const float* x, const float* w, const float* b, void* y, int32_t M, int32_t D, void* stream) {
+  if (!x || !w || !y) return ESMDIFF_E_INVALID;
+  hipError_t s = launch_layernorm_bf16(x, w, b, (bf16_t*)y, M, D, (hipStream_t)stream);
+  if (s != hipSuccess) return fail(nullptr, ESMDIFF_E_HIP, "layernorm: %s", hipGetErrorString(s));
+  return 0;
+}
+
+int esmdiff_attention_bf16(esmdiff_engine* e, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* ctx,
+                           int32_t B, int32_t L, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (!qkv || !q_ln_w || !k_ln_w || !ctx) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (e->strict || e->f16) return fail(e, ESMDIFF_E_INVALID, "esmdiff_attention_bf16 needs a bf16 engine (this one is float32 or f16)");
+  if (int r = check_bl(e, B, L)) return r;
+  HIP_TRY(e, launch_qk_norm_rope((const bf16_t*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, e->q, e->k, B, L,
+                                 e->cfg.n_heads, (hipStream_t)stream));
+  HIP_TRY(e, launch_attention(e->q, e->k, (const bf16_t*)qkv, (bf16_t*)ctx, B, L, e->cfg.n_heads, (hipStream_t)stream));
+  return 0;
+}
+
+int esmdiff_attention_f16(esmdiff_engine* e, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* ctx,
+                          int32_t B, int32_t L, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (!qkv || !q_ln_w || !k_ln_w || !ctx) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (!e->f16) return fail(e, ESMDIFF_E_INVALID, "esmdiff_attention_f16 needs an f16 engine");
+  if (int r = check_bl(e, B, L)) return r;
+  HIP_TRY(e, ed16::launch_qk_norm_rope((const bf16_t*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, e->q, e->k, B, L,
+                                       e->cfg.n_heads, (hipStream_t)stream));
+  HIP_TRY(e, ed16::launch_attention(e->q, e->k, (const bf16_t*)qkv, (bf16_t*)ctx, B, L, e->cfg.n_heads, (hipStream_t)stream));
+  return 0;
+}
+
+int esmdiff_attention_ragged(esmdiff_engine* e, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* ctx,
+                             const int32_t* lens, int32_t B, int32_t L, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (!qkv || !q_ln_w || !k_ln_w || !ctx) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (e->kind != 0) return fail(e, ESMDIFF_E_INVALID, "esmdiff_attention_ragged needs an ESM3 engine");
+  if (int r = check_bl(e, B, L)) return r;
+  hipStream_t st = (hipStream_t)stream;
+  const int H = e->cfg.n_heads, D = e->cfg.d_model;
+  const int32_t* dl = nullptr;
+  if (lens) {   // host lengths -> the engine's sub-batch length buffer (validated here: the kernels index with them)
+    for (int b = 0; b < B; ++b)
+      if (lens[b] < 1 || lens[b] > L) return fail(e, ESMDIFF_E_INVALID, "lens[%d] = %d outside 1..L (%d)", b, lens[b], L);
+    HIP_TRY(e, hipStreamSynchronize(st));
+    HIP_TRY(e, hipMemcpy(e->lens_sub_dev, lens, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
+    dl = e->lens_sub_dev;
+  }
+  if (e->strict && e->split) {   // f32 qkv -> split q / k / v rows (unit scales) -> float32-grade attention on the f16 MFMA
+    uint16_t *q2 = reinterpret_cast<uint16_t*>(e->fq), *k2 = reinterpret_cast<uint16_t*>(e->fk), *v2 = reinterpret_cast<uint16_t*>(e->fh);
+    HIP_TRY(e, launch_qk_norm_rope_split((const float*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, q2, k2, B, L, H,
+                                         0.18033688011112042f /* log2(e) / 8 */, 1.0f, st));
+    HIP_TRY(e, launch_v_split((const float*)qkv, v2, B * L, D, 1.0f, st));
+    HIP_TRY(e, launch_attention_split(q2, k2, v2, (float*)ctx, B, L, H, 1.0f, 1.0f, st, dl));
+  } else if (e->strict) {
+    HIP_TRY(e, launch_qk_norm_rope_f32((const float*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, e->fq, e->fk, B, L, H, st));
+    HIP_TRY(e, launch_attention_f32(e->fq, e->fk, (const float*)qkv, (float*)ctx, B, L, H, st, dl));
+  } else {
+    HIP_TRY(e, ED_KN(e->f16, launch_qk_norm_rope((const bf16_t*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, e->q, e->k, B, L, H, st)));
+    HIP_TRY(e, ED_KN(e->f16, launch_attention(e->q, e->k, (const bf16_t*)qkv, (bf16_t*)ctx, B, L, H, st, dl)));
+  }
+  if (lens) HIP_TRY(e, hipStreamSynchronize(st));   // the next call may rewrite lens_sub_dev
+  return 0;
+}
+
+int esmdiff_qk_norm_rope(esmdiff_engine* e, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* q, void* k,
+                         int32_t B, int32_t L, int32_t H, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (!qkv || !q_ln_w || !k_ln_w || !q || !k) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (e->strict) return fail(e, ESMDIFF_E_INVALID, "esmdiff_qk_norm_rope needs a bf16 or f16 engine (this one is float32)");
+  if (H <= 0 || H > 32) return fail(e, ESMDIFF_E_INVALID, "H=%d: 1 .. 32 heads of 64", H);
+  if (int r = check_bl(e, B, L)) return r;   // the rotary tables hold max_len positions
+  HIP_TRY(e, ED_KN(e->f16, launch_qk_norm_rope((const bf16_t*)qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, (bf16_t*)q, (bf16_t*)k, B, L, H,
+                                               (hipStream_t)stream)));
+  return 0;
+}
+
+int esmdiff_add_layernorm(int32_t dtype, float* x, const void* delta, const void* delta2, int32_t write_x, const float* w,
+                          const float* b, void* y, int32_t M, int32_t D, void* stream) {
+  if (!x || !w || !y) return fail(nullptr, ESMDIFF_E_INVALID, "add_layernorm: null pointer");
+  if (dtype != 0 && dtype != 1) return fail(nullptr, ESMDIFF_E_INVALID, "add_layernorm: dtype %d (0 bf16, 1 f16)", dtype);
+  if (M <= 0 || D <= 0) return fail(nullptr, ESMDIFF_E_INVALID, "add_layernorm: M=%d D=%d must be positive", M, D);
+  return launched(nullptr, ED_KN(dtype, launch_add_layernorm_bf16(x, (const bf16_t*)delta, (const bf16_t*)delta2, write_x, w, b, (bf16_t*)y, M, D,
+                                                                  (hipStream_t)stream)), "add_layernorm");
+}
+
+int esmdiff_geom_attention(const void* P, int32_t dtype, const float* rot, const float* trans, const uint8_t* has_frame,
+                           const float* rotation_scale, const float* distance_scale, void* out, int32_t B, int32_t L,
+                           int32_t VH, void* stream) {
+  if (!P || !rot || !trans || !has_frame || !rotation_scale || !distance_scale || !out)
+    return fail(nullptr, ESMDIFF_E_INVALID, "geom_attention: null pointer");
+  if (dtype < 0 || dtype > 2) return fail(nullptr, ESMDIFF_E_INVALID, "geom_attention: dtype %d (0 bf16, 1 f16, 2 f32)", dtype);
+  if (B <= 0 || L <= 0 || VH <= 0) return fail(nullptr, ESMDIFF_E_INVALID, "geom_attention: B=%d L=%d VH=%d must be positive", B, L, VH);
+  if (L > 3200) return fail(nullptr, ESMDIFF_E_INVALID, "geom_attention: L=%d exceeds the kernel's 150 KB of LDS (L <= 3200)", L);
+  std::vector<float> hw(2 * (size_t)VH);
+  std::copy(rotation_scale, rotation_scale + VH, hw.begin());
+  std::copy(distance_scale, distance_scale + VH, hw.begin() + VH);
+  softplus_host(hw.data(), 2 * VH);
+  float* dw = nullptr;
+  if (hipMalloc(&dw, hw.size() * sizeof(float)) != hipSuccess) return fail(nullptr, ESMDIFF_E_HIP, "geom_attention: hipMalloc failed");
+  const hipStream_t st = (hipStream_t)stream;
+  hipError_t s = hipMemcpyAsync(dw, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice, st);
+  if (s == hipSuccess) {
+    if (dtype == 2)
+      s = ed::launch_geom_attention_f32((const float*)P, rot, trans, has_frame, dw, dw + VH, (float*)out, B, L, VH, st);
+    else
+      s = ED_KN(dtype == 1, launch_geom_attention((const bf16_t*)P, rot, trans, has_frame, dw, dw + VH, (bf16_t*)out, B, L, VH, st));
+  }
+  const hipError_t s2 = hipStreamSynchronize(st);   // synchronous: the scale buffer and the host copy die here
+  if (s == hipSuccess) s = s2;
+  hipFree(dw);
+  return launched(nullptr, s, "geom_attention");
+}
+
+}  // extern "C"

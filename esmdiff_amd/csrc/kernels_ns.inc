@@ -1,5 +1,5 @@
 // kernels_ns.inc — the launch functions of one operand-type build of the kernels; included by kernels.h (namespace ed) and,
-// in engine.hip, a second time with `#define ed ed16` for the f16 build of the same sources (ed_half.h).  No include guard.
+// in engine.h, a second time with `#define ed ed16` for the f16 build of the same sources (ed_half.h).  No include guard.
 namespace ed {
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device only: once per (kernel, device), thread-safe,

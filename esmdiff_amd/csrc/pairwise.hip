@@ -2,7 +2,7 @@
 //
 // What the reference's decode path returns as decoder_output["ptm"] / ["predicted_aligned_error"]
 // (/root/reference/slm/models/utils.py:64-76 -> esm StructureTokenDecoder.decode [ESM-RECALL]):
-//   qk = downproject(x)                      [B, L, 128]   (engine.hip issues this GEMM next to the other heads)
+//   qk = downproject(x)                      [B, L, 128]   (the engine's forward issues this GEMM next to the other heads)
 //   f(i, j) = [ q_j * k_i | q_j - k_i ]      128 features of the pair (i, j), q = qk[..., :64], k = qk[..., 64:]
 //   logits = linear2(LayerNorm(GELU(linear1 f)))   -> the 64 predicted-aligned-error bins (rows 160..223 of linear2)
 //   p = softmax(logits) over the bins; pairs with a special token on either side: uniform

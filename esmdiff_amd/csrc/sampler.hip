@@ -65,7 +65,7 @@ __global__ __launch_bounds__(NT) void ddpm_step_kernel(int64_t* __restrict__ x, 
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
   // logits_period > 0: sample b reads the logits of sample b % logits_period (step-0 sharing: every sample of the batch
-  // had identical inputs, engine.hip::esmdiff_ddpm_sample); the noise stays keyed by the sample's own index
+  // had identical inputs, engine_sample.hip::esmdiff_ddpm_sample); the noise stays keyed by the sample's own index
   const int lrow = logits_period > 0 ? ((row / L) % logits_period) * L + (row % L) : row;
   const float* z = logits + (int64_t)lrow * ld;
 

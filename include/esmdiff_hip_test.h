@@ -76,7 +76,7 @@ int esmdiff_describe_gemm_choice(int32_t M, int32_t N, int32_t K, int64_t ws_flo
 /* Floats in the split-K workspace esmdiff_gemm_bf16_ws hands its launch (0: the engine has none): the ws_floats of that engine. */
 int esmdiff_gemm_workspace_floats(const esmdiff_engine* eng, int64_t* floats_out);
 
-/* The small-batch form of a residual branch (M < 1152 rows; csrc/engine.hip::forward): the branch linear A[M,K] W[N,K]^T
+/* The small-batch form of a residual branch (M < 1152 rows; csrc/engine_forward.hip::forward): the branch linear A[M,K] W[N,K]^T
  * is left as S raw f32 K-slice planes in the engine's workspace (S = *splits_out, a function of N and K only) and the
  * LayerNorm kernel that follows sums them:  x[M,N] f32 += alpha * (A W^T);  y bf16 [M,N] = LayerNorm(x) * w (+ b).
  * N = d_model of the engine's shapes (N % 128 == 0, N <= 2048), K % 64 == 0.  Not re-entrant per engine. */

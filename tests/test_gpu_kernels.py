@@ -693,7 +693,7 @@ def test_attention_long_chain():
 @pytest.mark.parametrize("B,L", [(2, 60), (3, 258), (8, 110), (8, 290), (5, 258)])
 def test_forward_logits_vs_oracle(tiny, B, L):
     # (8,110): 880 tokens, two streams of small-batch halves; (8,290): 2320 tokens, two streams on the regular path;
-    # (5,258): 1290 tokens, one stream on the regular path — the engine's stream / path switches (engine.hip::forward)
+    # (5,258): 1290 tokens, one stream on the regular path — the engine's stream / path switches (engine_forward.hip::forward)
     from esmdiff_amd.schedule import ddpm_schedule
     cfg, sd, eng, net, emb = tiny
     g = torch.Generator().manual_seed(L)
@@ -898,7 +898,7 @@ def test_structure_encoder_vs_oracle(B, L, precision):
 
 
 def test_two_stream_forward_is_bitwise_identical(tiny, monkeypatch):
-    """The engine runs the two halves of a large batch on two HIP streams (engine.hip::forward).  Samples are
+    """The engine runs the two halves of a large batch on two HIP streams (engine_forward.hip::forward).  Samples are
     independent and every kernel's per-row arithmetic does not depend on the tiling, so logits and sampled ids must
     be bit-identical to the single-stream run, including odd B and repeated fork/join inside the sampling loop."""
     from esmdiff_amd.engine import Engine
