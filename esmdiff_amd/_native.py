@@ -65,6 +65,9 @@ EXPORTS = [
     "esmdiff_lddt_pairs",
     "esmdiff_flex_pair_msf", "esmdiff_flex_fit", "esmdiff_flex_moments",
     "esmdiff_describe_gemm_choice", "esmdiff_gemm_workspace_floats",
+    "esmdiff_dim6_to_backbone", "esmdiff_plddt_mean", "esmdiff_pair_features", "esmdiff_pae_tm",
+    "esmdiff_decoder_set_pair_chunk_bytes",
+    "esmdiff_encoder_knn", "esmdiff_encoder_neighbourhood", "esmdiff_encoder_nearest_code",
 ]
 LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
 TM_MAX_L = 1280                              # ESMDIFF_TM_MAX_L
@@ -181,6 +184,14 @@ def lib():
     L.esmdiff_gemm_bf16_ws.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]
     L.esmdiff_describe_gemm_choice.argtypes = [i32, i32, i32, ctypes.c_int64] + [ctypes.POINTER(i32)] * 4
     L.esmdiff_gemm_workspace_floats.argtypes = [vp, c_i64p]
+    L.esmdiff_dim6_to_backbone.argtypes = [vp, i32, vp, i32, f32, vp]
+    L.esmdiff_plddt_mean.argtypes = [vp, i32, i32, vp, i32, vp]
+    L.esmdiff_pair_features.argtypes = [vp, i32, vp, i32, i32, vp]
+    L.esmdiff_pae_tm.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, vp]
+    L.esmdiff_decoder_set_pair_chunk_bytes.argtypes = [vp, ctypes.c_int64]
+    L.esmdiff_encoder_knn.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    L.esmdiff_encoder_neighbourhood.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.esmdiff_encoder_nearest_code.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     for n in EXPORTS:
         if n not in ("esmdiff_engine_destroy", "esmdiff_last_error", "esmdiff_encoder_destroy", "esmdiff_encoder_last_error"):
             getattr(L, n).restype = ctypes.c_int

@@ -413,4 +413,54 @@ int esmdiff_encoder_encode(esmdiff_encoder* e, const float* ca, const float* rot
   return 0;
 }
 
+// ---- test entries (include/esmdiff_hip_test.h): the glue kernels above, one at a time, launched as esmdiff_encoder_encode
+// launches them.  Synchronous; errors go to esmdiff_encoder_last_error(NULL). ----
+static int glue_done(hipStream_t st, const char* name) {
+  hipError_t s = hipGetLastError();
+  const hipError_t s2 = hipStreamSynchronize(st);
+  if (s == hipSuccess) s = s2;
+  return s == hipSuccess ? 0 : efail(nullptr, ESMDIFF_E_HIP, std::string(name) + ": " + hipGetErrorString(s));
+}
+
+int esmdiff_encoder_knn(const float* ca, const uint8_t* has, int32_t B, int32_t L, int32_t knn, int32_t* edges, void* stream) {
+  if (!ca || !has || !edges || B <= 0 || L <= 0 || knn <= 0) return efail(nullptr, ESMDIFF_E_INVALID, "encoder_knn: invalid argument");
+  if (L > 8192) return efail(nullptr, ESMDIFF_E_INVALID, "encoder_knn: L > 8192");
+  const int K = knn < L ? knn : L;
+  if ((int64_t)B * L * K > (int64_t)1 << 30) return efail(nullptr, ESMDIFF_E_INVALID, "encoder_knn: B*L*knn too large");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(knn_kernel, dim3(L, B), dim3(256), (size_t)L * sizeof(float), st, ca, has, L, K, edges);
+  return glue_done(st, "knn_kernel");
+}
+
+int esmdiff_encoder_neighbourhood(const int32_t* edges, const float* table, const float* rot, const float* trans, const uint8_t* has,
+                                  int32_t B, int32_t L, int32_t K, int32_t D, int32_t bins, float* x, float* nrot, float* ntrans,
+                                  uint8_t* nmask, void* stream) {
+  if (!edges || !table || !rot || !trans || !has || !x || !nrot || !ntrans || !nmask)
+    return efail(nullptr, ESMDIFF_E_INVALID, "encoder_neighbourhood: null pointer");
+  if (B <= 0 || L <= 0 || K <= 0 || K > L || D <= 0 || D % 4 || bins <= 0)
+    return efail(nullptr, ESMDIFF_E_INVALID, "encoder_neighbourhood: B, L, K <= L, D % 4 == 0 and bins must be positive");
+  const int64_t M = (int64_t)B * L * K;
+  if (M > (int64_t)1 << 30) return efail(nullptr, ESMDIFF_E_INVALID, "encoder_neighbourhood: B*L*K too large");
+  hipStream_t st = (hipStream_t)stream;
+  // the kernel gathers rows by edge: every index is checked on the host before the launch
+  std::vector<int32_t> he((size_t)M);
+  if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(he.data(), edges, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    return efail(nullptr, ESMDIFF_E_HIP, "encoder_neighbourhood: reading the edges failed");
+  for (int32_t v : he)
+    if (v < 0 || v >= L) return efail(nullptr, ESMDIFF_E_INVALID, "encoder_neighbourhood: edge outside 0 .. L-1");
+  hipLaunchKernelGGL(neighbourhood_kernel, dim3((unsigned)M), dim3(256), 0, st, edges, table, rot, trans, has, L, K, D, bins, x, nrot,
+                     ntrans, nmask);
+  return glue_done(st, "neighbourhood_kernel");
+}
+
+int esmdiff_encoder_nearest_code(const float* z, const float* code, const uint8_t* has, int32_t R, int32_t n_codes, int32_t d_out,
+                                 int64_t* tok, void* stream) {
+  if (!z || !code || !has || !tok) return efail(nullptr, ESMDIFF_E_INVALID, "encoder_nearest_code: null pointer");
+  if (R <= 0 || n_codes <= 0 || d_out <= 0 || d_out > 8192)
+    return efail(nullptr, ESMDIFF_E_INVALID, "encoder_nearest_code: R, n_codes and d_out (<= 8192) must be positive");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(codebook_kernel, dim3((unsigned)R), dim3(256), (size_t)d_out * sizeof(float), st, z, code, has, n_codes, d_out, tok);
+  return glue_done(st, "codebook_kernel");
+}
+
 }  // extern "C"

@@ -31,6 +31,9 @@ namespace eng {
 
 enum Section { S_EMBED = 0, S_LN, S_QKV, S_QKROPE, S_ATTN, S_OUT, S_FFN_UP, S_FFN_DOWN, S_HEAD, S_SAMPLER, S_COUNT };
 
+// engine_decode.hip (pairwise_confidence): bytes of pair rows one chunk of whole samples may occupy
+constexpr int64_t kDefaultPairChunkBytes = 1536ll << 20;
+
 // One linear's weight, held in the one form its engine runs it in.  create_engine chooses the form per group of weights
 // (body_form / head_form / plain_form), load_linear fills the slot, and the forwards dispatch on `form`.  An accessor of
 // another form than the slot's gives null.
@@ -84,6 +87,7 @@ struct esmdiff_engine {
   bf16_t *pair_x = nullptr, *pair_h = nullptr;   // pair rows of a chunk of samples (allocated on first use)
   float* pair_logits = nullptr;
   int64_t pair_rows_cap = 0;
+  int64_t pair_chunk_bytes = eng::kDefaultPairChunkBytes;   // esmdiff_decoder_set_pair_chunk_bytes (tests of the chunk loop)
   float *pl_b0 = nullptr, *pl_ln_w = nullptr, *pl_ln_b = nullptr, *pl_b3 = nullptr, *pl_logits = nullptr;
   // block 0 geometric attention (optional weights; live only while frames are set)
   bool has_geom = false;

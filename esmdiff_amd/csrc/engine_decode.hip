@@ -10,7 +10,7 @@ static int pairwise_confidence(esmdiff_engine* e, const int64_t* tokens, float* 
   const int64_t LL = (int64_t)L * L;
   // chunk of whole samples: ~1.5 GB of pair rows at most (768 B per row: features, hidden, 64 f32 logits; 1280 B in float32)
   const size_t esz = e->strict ? 4 : 2;
-  int cb = (int)std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(1536ll << 20) / (LL * (int64_t)(256 * esz + 256))));
+  int cb = (int)std::max<int64_t>(1, std::min<int64_t>(B, e->pair_chunk_bytes / (LL * (int64_t)(256 * esz + 256))));
   if (e->pair_rows_cap < (int64_t)cb * LL) {
     HIP_TRY(e, hipStreamSynchronize(st));
     for (void* p : {(void*)e->pair_x, (void*)e->pair_h, (void*)e->pair_logits})

@@ -239,4 +239,55 @@ int esmdiff_geom_attention(const void* P, int32_t dtype, const float* rot, const
   return launched(nullptr, s, "geom_attention");
 }
 
+// ---- the structure decoder's heads, one kernel at a time (synchronous) ----
+// a launch on the caller's stream followed by its completion
+static int launched_sync(hipError_t s, hipStream_t st, const char* name) {
+  const hipError_t s2 = hipStreamSynchronize(st);
+  return launched(nullptr, s == hipSuccess ? s2 : s, name);
+}
+
+int esmdiff_dim6_to_backbone(const float* v, int32_t ld, float* out, int32_t M, float trans_scale, void* stream) {
+  if (!v || !out) return fail(nullptr, ESMDIFF_E_INVALID, "dim6_to_backbone: null pointer");
+  if (M <= 0 || ld < 9) return fail(nullptr, ESMDIFF_E_INVALID, "dim6_to_backbone: M=%d must be positive, ld=%d at least 9", M, ld);
+  const hipStream_t st = (hipStream_t)stream;
+  return launched_sync(launch_dim6_to_backbone(v, ld, out, M, trans_scale, st), st, "dim6_to_backbone");
+}
+
+int esmdiff_plddt_mean(const float* v, int32_t ld, int32_t n_bins, float* out, int32_t M, void* stream) {
+  if (!v || !out) return fail(nullptr, ESMDIFF_E_INVALID, "plddt_mean: null pointer");
+  if (M <= 0 || n_bins <= 0 || ld < n_bins)
+    return fail(nullptr, ESMDIFF_E_INVALID, "plddt_mean: M=%d n_bins=%d must be positive, ld=%d at least n_bins", M, n_bins, ld);
+  const hipStream_t st = (hipStream_t)stream;
+  return launched_sync(launch_plddt_mean(v, ld, n_bins, out, M, st), st, "plddt_mean");
+}
+
+int esmdiff_pair_features(const void* qk, int32_t dtype, void* X, int32_t nb, int32_t L, void* stream) {
+  if (!qk || !X) return fail(nullptr, ESMDIFF_E_INVALID, "pair_features: null pointer");
+  if (dtype != 0 && dtype != 2)
+    return fail(nullptr, ESMDIFF_E_INVALID, "pair_features: dtype %d (0 bf16, 2 f32; the pairwise head has no f16 build)", dtype);
+  if (nb <= 0 || L <= 0 || (int64_t)nb * L * L > 0x7fffffffll)
+    return fail(nullptr, ESMDIFF_E_INVALID, "pair_features: nb=%d L=%d must be positive with nb * L^2 < 2^31", nb, L);
+  const hipStream_t st = (hipStream_t)stream;
+  const hipError_t s = dtype == 2 ? launch_pair_features_f32((const float*)qk, (float*)X, nb, L, st)
+                                  : launch_pair_features((const bf16_t*)qk, (bf16_t*)X, nb, L, st);
+  return launched_sync(s, st, "pair_features");
+}
+
+int esmdiff_pae_tm(const float* logits, const int64_t* tokens, float* tm_rows, float* pae, float* ptm, int32_t nb, int32_t L,
+                   float max_bin, void* stream) {
+  if (!logits || !tokens || !tm_rows || !ptm) return fail(nullptr, ESMDIFF_E_INVALID, "pae_tm: null pointer");
+  if (nb <= 0 || L <= 0 || (int64_t)nb * L * L > 0x7fffffffll || !(max_bin > 0.f))
+    return fail(nullptr, ESMDIFF_E_INVALID, "pae_tm: nb=%d L=%d max_bin=%g must be positive with nb * L^2 < 2^31", nb, L, (double)max_bin);
+  const hipStream_t st = (hipStream_t)stream;
+  return launched_sync(launch_pae_tm(logits, tokens, tm_rows, pae, ptm, nb, L, max_bin, st), st, "pae_tm");
+}
+
+int esmdiff_decoder_set_pair_chunk_bytes(esmdiff_engine* e, int64_t bytes) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (e->kind != 1) return fail(e, ESMDIFF_E_INVALID, "not a decoder engine");
+  if (bytes < 0) return fail(e, ESMDIFF_E_INVALID, "pair chunk bytes %lld: positive, or 0 for the default", (long long)bytes);
+  e->pair_chunk_bytes = bytes ? bytes : kDefaultPairChunkBytes;
+  return 0;
+}
+
 }  // extern "C"

@@ -762,6 +762,11 @@ class StructureDecoder:
         except Exception:
             pass
 
+    def set_pair_chunk_bytes(self, nbytes: int) -> None:
+        """esmdiff_decoder_set_pair_chunk_bytes: the pairwise head's pair-row budget per chunk of whole samples (768 B per
+        pair row in bf16, 1280 B in f32); 0 restores the default.  For the tests of the chunk loop."""
+        N.check(self._lib.esmdiff_decoder_set_pair_chunk_bytes(self._h, int(nbytes)), self._h)
+
     def decode(self, structure_tokens: torch.Tensor, return_plddt: bool = False, return_ptm: bool = False,
                return_pae: bool = False):
         """structure_tokens (B, L) int64 including BOS / EOS -> backbone coordinates (B, L - 2, 3, 3) float32 (N, CA, C);
@@ -1017,3 +1022,101 @@ def geom_attention(P: torch.Tensor, rot: torch.Tensor, trans: torch.Tensor, has_
                                            ctypes.cast(ws[0].data_ptr(), f32p), ctypes.cast(ws[1].data_ptr(), f32p),
                                            _ptr(out), B, L, VH, _stream()))
     return out
+
+
+# ---- the ends of the structure decoder and the encoder's glue kernels, one at a time (include/esmdiff_hip_test.h) ----
+def _f32_rows(v: torch.Tensor) -> torch.Tensor:
+    assert v.dtype == torch.float32 and v.dim() == 2 and v.stride(1) == 1 and v.is_cuda
+    return v
+
+
+def dim6_to_backbone(v: torch.Tensor, trans_scale: float) -> torch.Tensor:
+    """esmdiff_dim6_to_backbone: v f32 [M, ld] (a view with a row stride is fine) -> N, CA, C f32 [M, 3, 3]."""
+    _require_gpu()
+    M = _f32_rows(v).shape[0]
+    out = torch.empty(M, 3, 3, dtype=torch.float32, device=v.device)
+    N.check(N.lib().esmdiff_dim6_to_backbone(_ptr(v), v.stride(0), _ptr(out), M, float(trans_scale), _stream()))
+    return out
+
+
+def plddt_mean(v: torch.Tensor, n_bins: int) -> torch.Tensor:
+    """esmdiff_plddt_mean: logits f32 [M, ld], the first n_bins columns of each row -> f32 [M]."""
+    _require_gpu()
+    M = _f32_rows(v).shape[0]
+    out = torch.empty(M, dtype=torch.float32, device=v.device)
+    N.check(N.lib().esmdiff_plddt_mean(_ptr(v), v.stride(0), int(n_bins), _ptr(out), M, _stream()))
+    return out
+
+
+def pair_features(qk: torch.Tensor) -> torch.Tensor:
+    """esmdiff_pair_features: qk [nb, L, 128] bfloat16 or float32 -> [nb, L, L, 128], (b, i, j) = [q_j * k_i | q_j - k_i]."""
+    _require_gpu()
+    nb, L, C = qk.shape
+    assert C == 128 and qk.dtype in (torch.bfloat16, torch.float32) and qk.is_contiguous()
+    X = torch.empty(nb, L, L, 128, dtype=qk.dtype, device=qk.device)
+    N.check(N.lib().esmdiff_pair_features(_ptr(qk), GEOM_DTYPES[qk.dtype], _ptr(X), nb, L, _stream()))
+    return X
+
+
+def pae_tm(logits: torch.Tensor, tokens: torch.Tensor, max_bin: float = 31.0, want_pae: bool = True):
+    """esmdiff_pae_tm: logits f32 [nb, L, L, 64], tokens i64 [nb, L] -> (tm_rows [nb, L], pae [nb, L, L] or None, ptm [nb])."""
+    _require_gpu()
+    nb, L = tokens.shape
+    assert logits.shape == (nb, L, L, 64) and logits.dtype == torch.float32 and logits.is_contiguous()
+    assert tokens.dtype == torch.int64 and tokens.is_contiguous()
+    tm = torch.empty(nb, L, dtype=torch.float32, device=logits.device)
+    pae = torch.empty(nb, L, L, dtype=torch.float32, device=logits.device) if want_pae else None
+    ptm = torch.empty(nb, dtype=torch.float32, device=logits.device)
+    N.check(N.lib().esmdiff_pae_tm(_ptr(logits), _ptr(tokens), _ptr(tm), _ptr(pae), _ptr(ptm), nb, L, float(max_bin), _stream()))
+    return tm, pae, ptm
+
+
+def _enc_check(code: int) -> None:
+    if code != 0:
+        raise RuntimeError(f"libesmdiff_hip error {code}: {N.lib().esmdiff_encoder_last_error(None).decode()}")
+
+
+def encoder_knn(ca: torch.Tensor, has: torch.Tensor, knn: int) -> torch.Tensor:
+    """esmdiff_encoder_knn: ca f32 [B, L, 3], has [B, L] -> edges i32 [B, L, min(knn, L)]."""
+    _require_gpu()
+    B, L, _ = ca.shape
+    assert ca.dtype == torch.float32 and ca.is_contiguous() and has.shape == (B, L)
+    hm = has.to(device=ca.device, dtype=torch.uint8).contiguous()
+    edges = torch.empty(B, L, min(knn, L), dtype=torch.int32, device=ca.device)
+    _enc_check(N.lib().esmdiff_encoder_knn(_ptr(ca), _ptr(hm), B, L, int(knn), _ptr(edges), _stream()))
+    return edges
+
+
+def encoder_neighbourhood(edges: torch.Tensor, table: torch.Tensor, rot: torch.Tensor, trans: torch.Tensor,
+                          has: torch.Tensor, bins: int):
+    """esmdiff_encoder_neighbourhood: edges i32 [B, L, K], table f32 [2 bins + 2, D], rot [B, L, 3, 3], trans [B, L, 3],
+    has [B, L] -> (x [B, L, K, D], nrot [B, L, K, 3, 3], ntrans [B, L, K, 3], nmask u8 [B, L, K])."""
+    _require_gpu()
+    B, L, K = edges.shape
+    D = table.shape[1]
+    dev = edges.device
+    assert edges.dtype == torch.int32 and edges.is_contiguous() and table.shape[0] == 2 * bins + 2
+    t = table.to(device=dev, dtype=torch.float32).contiguous()
+    r = rot.to(device=dev, dtype=torch.float32).contiguous()
+    tr = trans.to(device=dev, dtype=torch.float32).contiguous()
+    hm = has.to(device=dev, dtype=torch.uint8).contiguous()
+    assert r.shape == (B, L, 3, 3) and tr.shape == (B, L, 3) and hm.shape == (B, L)
+    x = torch.empty(B, L, K, D, dtype=torch.float32, device=dev)
+    nrot = torch.empty(B, L, K, 3, 3, dtype=torch.float32, device=dev)
+    ntrans = torch.empty(B, L, K, 3, dtype=torch.float32, device=dev)
+    nmask = torch.empty(B, L, K, dtype=torch.uint8, device=dev)
+    _enc_check(N.lib().esmdiff_encoder_neighbourhood(_ptr(edges), _ptr(t), _ptr(r), _ptr(tr), _ptr(hm), B, L, K, D, int(bins),
+                                                     _ptr(x), _ptr(nrot), _ptr(ntrans), _ptr(nmask), _stream()))
+    return x, nrot, ntrans, nmask
+
+
+def encoder_nearest_code(z: torch.Tensor, code: torch.Tensor, has: torch.Tensor) -> torch.Tensor:
+    """esmdiff_encoder_nearest_code: z f32 [R, d_out], code f32 [n_codes, d_out], has [R] -> tok i64 [R]."""
+    _require_gpu()
+    R, d_out = z.shape
+    assert z.dtype == code.dtype == torch.float32 and z.is_contiguous() and code.is_contiguous() and code.shape[1] == d_out
+    hm = has.to(device=z.device, dtype=torch.uint8).contiguous()
+    assert hm.shape == (R,)
+    tok = torch.empty(R, dtype=torch.int64, device=z.device)
+    _enc_check(N.lib().esmdiff_encoder_nearest_code(_ptr(z), _ptr(code), _ptr(hm), R, code.shape[0], d_out, _ptr(tok), _stream()))
+    return tok

@@ -124,6 +124,43 @@ int esmdiff_geom_attention(const void* P, int32_t dtype, const float* rot, const
                            const float* rotation_scale, const float* distance_scale, void* out, int32_t B, int32_t L,
                            int32_t VH, void* stream);
 
+/* ---- The ends of the structure decoder, one kernel at a time (tests/test_gpu_decoder_ends.py).  All synchronous; every argument
+ * is checked before anything is launched (ESMDIFF_E_INVALID). ----
+ *   esmdiff_dim6_to_backbone  v f32 [M, ld] (columns 0..8 read: trans 3 | x 3 | y 3; ld >= 9) -> out f32 [M, 3, 3] = N, CA, C:
+ *                             csrc/embed.hip, the tail of esm's Dim6RotStructureHead
+ *   esmdiff_plddt_mean        v f32 [M, ld] (n_bins logits per row, ld >= n_bins) -> out f32 [M] = sum softmax(v) (i + 0.5) / n_bins
+ *   esmdiff_pair_features     qk [nb*L, 128] = [q 64 | k 64] -> X [nb*L*L, 128], row (b, i, j) = [q_j * k_i | q_j - k_i].
+ *                             dtype 0: bf16, 2: f32 (the pairwise head has no f16 build: 1 is refused)
+ *   esmdiff_pae_tm            logits f32 [nb*L*L, 64] PAE-bin logits, tokens i64 [nb, L] (ids >= 4096 are special: masked out)
+ *                             -> tm_rows f32 [nb, L], pae f32 [nb, L, L] (or NULL), ptm f32 [nb] = max over rows (csrc/pairwise.hip)
+ *   esmdiff_decoder_set_pair_chunk_bytes   bytes of pair rows that one chunk of whole samples of esmdiff_decoder_decode's pairwise
+ *                             head may occupy (768 B per pair row in bf16, 1280 B in f32); 0 restores the default (1.5 GB).
+ *                             Decoder engines only; not synchronous (it launches nothing). */
+int esmdiff_dim6_to_backbone(const float* v, int32_t ld, float* out, int32_t M, float trans_scale, void* stream);
+int esmdiff_plddt_mean(const float* v, int32_t ld, int32_t n_bins, float* out, int32_t M, void* stream);
+int esmdiff_pair_features(const void* qk, int32_t dtype, void* X, int32_t nb, int32_t L, void* stream);
+int esmdiff_pae_tm(const float* logits, const int64_t* tokens, float* tm_rows, float* pae, float* ptm, int32_t nb, int32_t L,
+                   float max_bin, void* stream);
+int esmdiff_decoder_set_pair_chunk_bytes(esmdiff_engine* eng, int64_t bytes);
+
+/* ---- The structure encoder's glue kernels (csrc/encoder.hip), launched as esmdiff_encoder_encode launches them.  Synchronous;
+ * errors are read with esmdiff_encoder_last_error(NULL). ----
+ *   esmdiff_encoder_knn           ca f32 [B, L, 3], has u8 [B, L] -> edges i32 [B, L, K], K = min(knn, L), L <= 8192: the K nearest
+ *                                 residues by CA distance (sequence distance * 100 + 1e6 where either residue is unknown),
+ *                                 nearest first, lowest index first among equal keys
+ *   esmdiff_encoder_neighbourhood edges i32 [B, L, K] (each in 0 .. L-1: checked on the host), table f32 [2 bins + 2, D], frames
+ *                                 rot f32 [B*L, 9], trans f32 [B*L, 3], has u8 [B*L] -> x f32 [B*L*K, D] = table[clamp(edge -
+ *                                 edge_0, +-bins) + bins + 1], nrot [B*L*K, 9], ntrans [B*L*K, 3], nmask u8 [B*L*K]: the
+ *                                 neighbours' frames.  D % 4 == 0
+ *   esmdiff_encoder_nearest_code  z f32 [R, d_out], code f32 [n_codes, d_out], has u8 [R] -> tok i64 [R] = the code nearest in
+ *                                 squared distance, lowest index among equals; 4096 where has == 0.  d_out <= 8192 */
+int esmdiff_encoder_knn(const float* ca, const uint8_t* has, int32_t B, int32_t L, int32_t knn, int32_t* edges, void* stream);
+int esmdiff_encoder_neighbourhood(const int32_t* edges, const float* table, const float* rot, const float* trans, const uint8_t* has,
+                                  int32_t B, int32_t L, int32_t K, int32_t D, int32_t bins, float* x, float* nrot, float* ntrans,
+                                  uint8_t* nmask, void* stream);
+int esmdiff_encoder_nearest_code(const float* z, const float* code, const uint8_t* has, int32_t R, int32_t n_codes, int32_t d_out,
+                                 int64_t* tok, void* stream);
+
 /* Accumulated per-section device time of the esmdiff_forward_logits/ddpm_sample calls since profiling was
  * enabled: esmdiff_set_profiling(eng, 1) brackets every launch with HIP events on the launch stream (no sync);
  * mode 2 brackets only the dominant kernel (FFN-up GEMM, section 6), cheap enough for a timed region; 0 = off. sections: 0 embed, 1 layernorm, 2 gemm_qkv,
