@@ -64,12 +64,14 @@ EXPORTS = [
     "esmdiff_cluster_threshold", "esmdiff_cluster_gromos",
     "esmdiff_lddt_pairs",
     "esmdiff_flex_pair_msf", "esmdiff_flex_fit", "esmdiff_flex_moments",
+    "esmdiff_dssp",
     "esmdiff_describe_gemm_choice", "esmdiff_gemm_workspace_floats",
     "esmdiff_dim6_to_backbone", "esmdiff_plddt_mean", "esmdiff_pair_features", "esmdiff_pae_tm",
     "esmdiff_decoder_set_pair_chunk_bytes",
     "esmdiff_encoder_knn", "esmdiff_encoder_neighbourhood", "esmdiff_encoder_nearest_code",
 ]
 LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
+DSSP_MAX_L = 4096                            # ESMDIFF_DSSP_MAX_L
 TM_MAX_L = 1280                              # ESMDIFF_TM_MAX_L
 
 CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
@@ -163,6 +165,7 @@ def lib():
     L.esmdiff_flex_pair_msf.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_flex_fit.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.esmdiff_flex_moments.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+    L.esmdiff_dssp.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.esmdiff_encoder_create.argtypes = [i32] * 9 + [ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.esmdiff_encoder_destroy.argtypes = [vp]
     L.esmdiff_encoder_destroy.restype = None

@@ -1,7 +1,7 @@
 """Evaluate one sampled ensemble against its target structures on the device.
 
     python -m esmdiff_amd.analyze_ensemble --samples <multi-MODEL pdb> --targets a.pdb [b.pdb ...] --output <dir> [--max_models 100]
-                                           [--lddt] [--plddt_scale 1.0] [--flex] [--pca_components 3]
+                                           [--lddt] [--plddt_scale 1.0] [--flex] [--pca_components 3] [--dssp]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
@@ -17,7 +17,13 @@ rmsd_to_mean), the RMSF about it (rmsf), the reference's pairwise RMSF (pair_rms
 on the mean (pca: explained_variance, explained_variance_ratio, projections of the samples, target_projections; --pca_components
 modes).  With exactly two targets also resflex (Pearson / Spearman / Kendall between the report's apo-holo deviation `rmsd` and its
 `rmsf`, the reference's per-target numbers), resflex_mean_structure (the same against the mean-structure RMSF) and
-displacement_overlap (the share of the displacement between the two targets that the leading modes span, cumulative)."""
+displacement_overlap (the share of the displacement between the two targets that the leading modes span, cumulative).
+--dssp adds a "dssp" block (esmdiff_amd/secondary.py, csrc/dssp.hip; [DSSP-RECALL], parity with mkdssp unpinned): the legend, the
+samples' eight-state strings, counts (L, 8), the three-state propensity (helix, strand, coil per residue) and content, per target its
+string and the agreement of the samples with it (q3 per sample, q3_mean, q3_best, best_model, per_residue) and, with exactly two
+targets, switch_residues: the residues whose three-state class differs between the two, with the ensemble's share in each target's
+class — the secondary-structure counterpart of ResFlex.  Samples and targets are read again as N / CA / C with the carbonyl O inferred
+on both alike; the samples' prolines donate no hydrogen bond."""
 from __future__ import annotations
 
 import argparse
@@ -26,8 +32,8 @@ from pathlib import Path
 
 import numpy as np
 
-from . import ensemble, flexibility
-from .pdbio import load_coords, read_pdb_bfactors
+from . import ensemble, flexibility, secondary
+from .pdbio import load_coords, read_pdb_backbone, read_pdb_bfactors
 
 
 def _jsonable(v):
@@ -69,8 +75,23 @@ def flex_report(samples, targets, report: dict, pca_components: int = 3) -> dict
     return out
 
 
+def dssp_report(samples_path, target_paths, keep=None) -> dict:
+    """The --dssp block: the files read again as N / CA / C backbones (`keep`: the analysed subset of the samples' models), O inferred;
+    the proline flags come from the residue names of the samples' first model."""
+    backbones = load_coords(Path(samples_path), max_n_model=None, ca_only=False, verbose=False)
+    if keep is not None:
+        backbones = backbones[keep]
+    sequence = None
+    if Path(samples_path).name.endswith(".pdb") and Path(samples_path).is_file():
+        sequence = read_pdb_backbone(samples_path)[0]
+        if len(sequence) != backbones.shape[1]:
+            sequence = None
+    targets = [load_coords(Path(p), max_n_model=None, ca_only=False, verbose=False)[0] for p in target_paths]
+    return secondary.report(secondary.dssp(backbones, sequence), [secondary.dssp(t, sequence) for t in targets])
+
+
 def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0,
-            flex: bool = False, pca_components: int = 3) -> dict:
+            flex: bool = False, pca_components: int = 3, dssp: bool = False) -> dict:
     samples = load_coords(Path(samples_path), max_n_model=None, verbose=False)
     n_all, keep = len(samples), np.arange(len(samples))
     if len(samples) > max_models:
@@ -97,6 +118,8 @@ def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, ld
         report.update(lddt_report(samples, np.stack(targets), plddt, plddt_scale))
     if flex:
         report["flex"] = flex_report(samples, np.stack(targets), report, pca_components)
+    if dssp:
+        report["dssp"] = dssp_report(samples_path, target_paths, keep)
     return report
 
 
@@ -111,12 +134,14 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--plddt_scale", type=float, default=1.0, help="the samples' B-factors divided by this are pLDDT in [0, 1]")
     ap.add_argument("--flex", action="store_true", help="add the mean structure, RMSF, pairwise RMSF, PCA and the ResFlex correlations")
     ap.add_argument("--pca_components", type=int, default=3, help="modes of the --flex PCA")
+    ap.add_argument("--dssp", action="store_true", help="add the DSSP states, the three-state propensities and the agreement with the targets")
     return ap
 
 
 def main(argv=None) -> Path:
     args = parser().parse_args(argv)
-    report = analyze(args.samples, args.targets, args.max_models, args.seed, args.lddt, args.plddt_scale, args.flex, args.pca_components)
+    report = analyze(args.samples, args.targets, args.max_models, args.seed, args.lddt, args.plddt_scale, args.flex, args.pca_components,
+                     args.dssp)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

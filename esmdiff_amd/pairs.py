@@ -1,5 +1,5 @@
 """The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
-csrc/cluster.hip and csrc/flex.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+csrc/cluster.hip, csrc/flex.hip and csrc/dssp.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
 on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
 host-facing layers above it.
 Row blocks are contiguous slices (A[r0:r1]): a slice carries its own pointer, dtype and shape.  There is no CPU fallback."""
@@ -129,6 +129,20 @@ def lddt(A, B, ma, mb, r0: float = LDDT_R0, thresholds=LDDT_THRESHOLDS, seq_sep:
     """lDDT (n, m) float64: kept / (n_thresholds total), NaN where the native has no pair."""
     kept, total, _, _ = lddt_counts(A, B, ma, mb, False, r0, thresholds, seq_sep)
     return kept.to(torch.float64) / (len(thresholds) * total).to(torch.float64)[None]
+
+
+def dssp(X, mask, no_donor, counts: bool = True):
+    """One esmdiff_dssp call: X f64 (n, L, 4, 3) N / CA / C / O, mask u8 (n, L) or None, no_donor u8 (L,) or None -> ss u8 (n, L),
+    counts i32 (L, 8) (None without `counts`), acceptor i32 (n, L, 2), energy f64 (n, L, 2)."""
+    assert X.dim() == 4 and tuple(X.shape[2:]) == (4, 3) and X.dtype == torch.float64, f"f64 (n, L, 4, 3) backbones, got {X.dtype} {tuple(X.shape)}"
+    n, L = X.shape[:2]
+    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    assert no_donor is None or (no_donor.dtype == torch.uint8 and tuple(no_donor.shape) == (L,)), "no_donor is u8 (L,)"
+    ss, table = _new((n, L), torch.uint8), _new((L, 8), torch.int32) if counts else None
+    acceptor, energy = _new((n, L, 2), torch.int32), _new((n, L, 2))
+    code = N.lib().esmdiff_dssp(_p(X), n, L, _p(mask), _p(no_donor), _p(ss), _p(table), _p(acceptor), _p(energy), _stream())
+    _check("esmdiff_dssp", code, invalid=lambda: f"esmdiff_dssp: invalid argument: L = {L} (1 to {N.DSSP_MAX_L} residues)")
+    return ss, table, acceptor, energy
 
 
 def adjacency(n: int) -> torch.Tensor:

@@ -590,6 +590,26 @@ int esmdiff_flex_fit(const double* A, int32_t n, int32_t L, const uint8_t* maskA
 int esmdiff_flex_moments(const double* X, int32_t n, int32_t L, const uint8_t* mask, double* mean, double* msf, int32_t* count,
                          void* stream);
 
+/* Secondary structure of backbones after Kabsch & Sander 1983 ("DSSP"): float64 geometry in, backbone hydrogen bonds, INTEGER state
+ * codes and their per-residue counts out, held exactly to the numpy restatement tests/dssp_ref.py.  (An addition; the ABI number
+ * stays.)  DESIGN.md §3.22 states the definition — presence, chain breaks, donors and acceptors, the energy, the two-best rule, turns,
+ * bridges, ladders and the passes — and the deliberate differences from the `mkdssp` program [DSSP-RECALL: parity unpinned].
+ * X f64 [n, L, 4, 3]: N, CA, C, O per residue; mask u8 [n, L] or NULL (all given); no_donor u8 [L] or NULL: residues whose N carries
+ * no H (proline), shared by all structures.  All pointers are device pointers; the library allocates nothing.
+ *   ss       u8  [n, L]     0 '-', 1 S, 2 T, 3 I, 4 G, 5 B, 6 E, 7 H; a residue that is masked or lacks N, CA or C gets 0
+ *   counts   i32 [L, 8]     or NULL: the number of structures in which residue l is present and has code c
+ *   acceptor i32 [n, L, 2]  required: the two acceptors of donor j's N-H of lowest energy among those below -0.5 kcal/mol, ordered
+ *                           by (energy, index); -1 in an empty slot
+ *   energy   f64 [n, L, 2]  required: their energies, 0.0 in an empty slot
+ * Distances are sqrt((dx dx + dy dy) + dz dz) in float64, correctly rounded square root and division, no FMA contraction.  On
+ * success every element of every output is written; masked or absent residues' coordinates never influence anything (they may be NaN
+ * or garbage).  Integer atomics only: two runs are bit-identical, and a structure's rows do not depend on the batch.  The call
+ * synchronises `stream`.  n == 0 succeeds and zeroes counts.  n < 0, L < 1, L > ESMDIFF_DSSP_MAX_L or a required pointer that is
+ * NULL return ESMDIFF_E_INVALID and touch no output. */
+#define ESMDIFF_DSSP_MAX_L 4096
+int esmdiff_dssp(const double* X, int32_t n, int32_t L, const uint8_t* mask, const uint8_t* no_donor, uint8_t* ss, int32_t* counts,
+                 int32_t* acceptor, double* energy, void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
