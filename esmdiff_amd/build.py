@@ -120,7 +120,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     objs = [str(OBJDIR / f"{n}.o") for n in UNITS] + [str(OBJDIR / f"{n}_f16.o") for n in F16_UNITS]
     emap = OBJDIR / "exports.map"
     _write_export_map(emap)
-    r = subprocess.run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", f"-Wl,--version-script={emap}", *objs, "-o", str(LIB)],
+    r = subprocess.run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", f"-Wl,--version-script={emap}", *objs, "-o", str(LIB)],
                        capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stderr}")

@@ -9,6 +9,8 @@
 // f16 has 5 exponent bits: weights (|w| <= 65504, precision floor 6e-8 absolute) and LayerNorm / attention / SwiGLU outputs
 // of this network sit comfortably inside; conversions saturate to +-65504 instead of producing inf (ed_sat).
 // esmdiff_config.precision = ESMDIFF_PRECISION_F16 selects the ed16 kernels at engine create.
+// The launchers of these units, and only they, are declared in kernels_typed.inc, which the engine's header includes once per
+// namespace; a host call names its build through ED_KN(e->f16, launch_x(..)) (engine.h).  Every other launcher exists once, in ed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

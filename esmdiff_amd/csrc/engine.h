@@ -1,7 +1,7 @@
 // engine.h — private to the engine units of libesmdiff_hip.so (never installed): the engine's data model, the section timer and
 // the few helpers that cross units.
 //   engine.hip          lifetime and state: weight loader, create / destroy, the setters and getters
-//   engine_forward.hip  one forward: batch planner, the float32-grade and the 16-bit (engine_forward.inc) launch sequences
+//   engine_forward.hip  one forward: batch planner, sub-batch view, the float32-grade and the 16-bit launch sequences
 //   engine_sample.hip   what runs forwards in a loop or consumes logits: ddpm / gibbs steps and samplers, q_xt, the NELBO
 //   engine_decode.hip   the structure decoder's backbone and confidence heads
 //   engine_test.hip     kernel-level entries of include/esmdiff_hip_test.h
@@ -19,8 +19,8 @@
 #include <vector>
 
 #include "kernels.h"
-#define ed ed16            // the f16 build of the same kernel sources (ed_half.h, esmdiff_amd/build.py)
-#include "kernels_ns.inc"
+#define ed ed16            // the f16 build of the operand-typed units (ed_half.h, esmdiff_amd/build.py: F16_UNITS): only what
+#include "kernels_typed.inc"   // they define is declared in ed16, so a once-only launcher spelled ed16:: does not compile
 #undef ed
 
 // The operand-type build of a launcher, chosen by the engine's 16-bit type: ED_KN(e->f16, launch_x(args)) calls ed16::launch_x
@@ -126,9 +126,9 @@ struct esmdiff_engine {
   int n_streams = 2;         // esmdiff_set_option(ESMDIFF_OPT_STREAMS): sub-batch launch queues of the 16-bit forward
   ed::GemmWorkspace gemm_ws[4] = {};  // split-K partials of the small-M GEMM path, one per launch queue
   ed::GemmWorkspace gemm_ws2[4] = {}; // ... a second set: the out-projection's K slices stay live next to the FFN-down's
-  // precision = ESMDIFF_PRECISION_F32: float32 weights / activations (forward_strict); the 16-bit workspace above stays null
+  // precision = ESMDIFF_PRECISION_F32: float32 weights / activations (engine_forward.hip: strict_part); the 16-bit workspace above stays null
   bool strict = false;
-  // precision = ESMDIFF_PRECISION_F32_SPLIT: forward_strict with every large linear as three f16 MFMA passes over split
+  // precision = ESMDIFF_PRECISION_F32_SPLIT: strict_part with every large linear as three f16 MFMA passes over split
   // operands (gemm_split.hip); a2 / rs: the split activation rows feeding the next linear and their row scales
   bool split = false;
   bool f16 = false;          // precision = ESMDIFF_PRECISION_F16: the bf16 engine's launch sequence on the ed16 kernels
@@ -213,7 +213,7 @@ struct Prof {
     p.mark(section);         \
   } while (0)
 
-// the planner's constants (engine_forward.hip: parts_for / strict_parts; esmdiff_set_small_batch_splitk sizes its planes by the last)
+// the planner's constants (engine_forward.hip: plan_batch; esmdiff_set_small_batch_splitk sizes its planes by the last)
 constexpr int kDefaultStreams = 2;
 constexpr int64_t kDefaultDualMinTokens = 2200;
 constexpr int64_t kDualSmallMaxTokens = 1024;      // the all-small two-queue window reaches up to this many tokens, see forward()

@@ -410,7 +410,7 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     TRY(load_f32(e, t, b + "ffn.0.weight", {D}, &ly.ln2_w));
     TRY(load_f32(e, t, b + "ffn.0.bias", {D}, &ly.ln2_b));
     // FFN-up with the SwiGLU in the GEMM's epilogue: rows interleaved gate / up (W16, and SPLIT: mid leaves it as f32 and is split
-    // with its row's own scale, forward_strict); F32 keeps the checkpoint's order
+    // with its row's own scale, strict_part); F32 keeps the checkpoint's order
     TRY(load_linear(e, t, b + "ffn.1.weight", {2 * FH, D}, bf, &ly.w_up, 0, FH));
     TRY(load_linear(e, t, b + "ffn.3.weight", {D, FH}, bf, &ly.w_down));
   }

@@ -18,35 +18,41 @@ using namespace eng;
 
 namespace {
 
-// Workspace of one sub-batch: the engine's buffers are all sample-major, so a sub-batch is a pointer offset.
+// Workspace of one sub-batch: the engine's buffers are all sample-major, so a sub-batch is a pointer offset.  An engine holds the
+// 16-bit workspace or the float32 one (fh2, a2, rs: also a 16-bit engine with the float32-grade head); the rest stays null here.
 struct Part {
   const int64_t *seq, *xtok;
   float *x, *logits, *pl_logits;
-  bf16_t *h, *h2, *qkv, *q, *k, *ctx, *mid, *dlt, *dlt2;
-  bf16_t *gp, *gctx;
-  uint16_t* a2;   // head_split: split rows feeding the two head linears, their row scales, the f32 Linear-0 output
-  float *rs, *fh2;
+  bf16_t *h, *h2, *qkv, *q, *k, *ctx, *mid, *dlt, *dlt2, *gp, *gctx, *pair_qk;
+  float *fh, *fh2, *fqkv, *fq, *fk, *fctx, *fgu, *fmid, *fgp, *fgctx, *fpair_qk;   // fgu: F32 engines only
+  uint16_t* a2;   // split rows feeding the next float32-grade linear, and their row scales
+  float* rs;
   const float *f_rot, *f_trans;
   const uint8_t* f_mask;
   const int32_t* lens;   // ragged batch: this sub-batch's lengths (device), else null
   int b0, B;             // first sample of the sub-batch in the batch, and how many
-  hipStream_t st;
-  const ed::GemmWorkspace* gws;
-  const ed::GemmWorkspace* gws2;
+  hipStream_t st;        // queue pi: the caller's stream (pi = 0) or side[pi - 1]
+  const GemmWorkspace *gws, *gws2;   // queue pi's split-K workspaces, null where the engine has none
 };
 
-Part make_part(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, float* logits, int ld, int b0, int nb, int L,
-               hipStream_t st, int queue) {
-  const esmdiff_config& c = e->cfg;
-  const int64_t t0 = (int64_t)b0 * L, D = c.d_model;
-  return Part{seq + t0, xtok + t0, e->x + t0 * D, logits + t0 * ld, e->pl_logits ? e->pl_logits + t0 * e->ld_plddt : nullptr, e->h + t0 * D, e->h2 + t0 * D, e->qkv + t0 * 3 * D,
-              e->q + t0 * D, e->k + t0 * D, e->ctx + t0 * D, e->mid + t0 * c.ffn_hidden, e->dlt + t0 * D, e->dlt2 + t0 * D,
-              e->gp ? e->gp + t0 * 15 * e->v_heads : nullptr, e->gctx ? e->gctx + t0 * 3 * e->v_heads : nullptr,
-              e->a2 ? e->a2 + t0 * 3 * D : nullptr, e->rs ? e->rs + t0 : nullptr, e->fh2 ? e->fh2 + t0 * D : nullptr,
-              e->f_rot ? e->f_rot + t0 * 9 : nullptr, e->f_trans ? e->f_trans + t0 * 3 : nullptr,
-              e->f_mask ? e->f_mask + t0 : nullptr, e->cur_lens ? e->cur_lens + b0 : nullptr, b0, nb, st,
-              e->gemm_ws[queue].partial ? &e->gemm_ws[queue] : nullptr,
-              e->gemm_ws2[queue].partial ? &e->gemm_ws2[queue] : nullptr};
+// Cuts B samples into np sub-batches, part pi = samples [B pi / np, B (pi + 1) / np), and offsets every buffer the engine holds.
+void cut_batch(esmdiff_engine* e, Part* parts, int np, const int64_t* seq, const int64_t* xtok, float* logits, int ld, int B, int L,
+               hipStream_t st) {
+  const int64_t D = e->cfg.d_model, FH = e->cfg.ffn_hidden, VH = e->v_heads;
+  const int64_t a2_row = 3 * (e->strict ? std::max(D, FH) : D);   // float32-grade engine: also the FFN-down's split rows
+  for (int pi = 0; pi < np; ++pi) {
+    const int b0 = (int)((int64_t)B * pi / np), b1 = (int)((int64_t)B * (pi + 1) / np);
+    const int64_t t0 = (int64_t)b0 * L;
+    auto off = [t0](auto* p, int64_t stride) { return p ? p + t0 * stride : nullptr; };
+    parts[pi] = Part{off(seq, 1), off(xtok, 1), off(e->x, D), off(logits, ld), off(e->pl_logits, e->ld_plddt),
+                     off(e->h, D), off(e->h2, D), off(e->qkv, 3 * D), off(e->q, D), off(e->k, D), off(e->ctx, D), off(e->mid, FH),
+                     off(e->dlt, D), off(e->dlt2, D), off(e->gp, 15 * VH), off(e->gctx, 3 * VH), off(e->pair_qk, 128),
+                     off(e->fh, D), off(e->fh2, D), off(e->fqkv, 3 * D), off(e->fq, D), off(e->fk, D), off(e->fctx, D),
+                     off(e->fgu, 2 * FH), off(e->fmid, FH), off(e->fgp, 15 * VH), off(e->fgctx, 3 * VH), off(e->fpair_qk, 128),
+                     off(e->a2, a2_row), off(e->rs, 1), off(e->f_rot, 9), off(e->f_trans, 3), off(e->f_mask, 1),
+                     e->cur_lens ? e->cur_lens + b0 : nullptr, b0, b1 - b0, pi == 0 ? st : e->side[pi - 1],
+                     e->gemm_ws[pi].partial ? &e->gemm_ws[pi] : nullptr, e->gemm_ws2[pi].partial ? &e->gemm_ws2[pi] : nullptr};
+  }
 }
 
 // How forward() will cut a batch: number of sub-batch streams, and whether the sub-batches take the small-batch path.
@@ -72,6 +78,10 @@ struct BatchPlan {
   bool small;   // the sub-batches take the small-batch path
 };
 BatchPlan plan_batch(const esmdiff_engine* e, int B, int L) {
+  // float32-grade engines: one path, and two queues only for F32_SPLIT at large batches.  (r06: with frames set the two-queue forward
+  // was not deterministic while geom_attention_kernel held packed float ops beside the other queue's GEMM: geom.hip.)
+  if (e->strict)
+    return BatchPlan{(e->split && !e->side.empty() && e->profiling != 1 && B >= 2 && (int64_t)B * L >= kStrictDualMinTokens) ? 2 : 1, false};
   const int np_def = parts_for(e, B, L, kDefaultStreams, kDefaultDualMinTokens);
   const bool small = parts_small(e, B, L, np_def);
   int np = parts_for(e, B, L, e->n_streams, e->dual_min_tokens);
@@ -100,25 +110,10 @@ int join_streams(esmdiff_engine* e, hipStream_t st, int np) {
 // precision = F32: the same network in float32 end to end (csrc/strict.hip).  One stream, one launch per op, residual
 // adds in the branch GEMMs' epilogues as x + r / scaling_factor (esm's own expression).  Sections are timed like the
 // bf16 path's.  Block 0's geometric branch runs between the attention and the FFN branch while frames are set.
-struct SPart {   // one sub-batch of a strict forward: the engine's float32 workspace at a row offset, on its own stream
-  const int64_t *seq, *xtok;
-  float *x, *fh, *fh2, *fqkv, *fq, *fk, *fctx, *fgu, *fmid, *fgp, *fgctx, *fpair_qk, *logits, *pl_logits;   // fgu: F32 engines only
-  uint16_t* a2;   // split rows feeding the next linear
-  float* rs;
-  const float *f_rot, *f_trans;
-  const uint8_t* f_mask;
-  const int32_t* lens;   // ragged batch: this sub-batch's lengths (device), else null
-  int b0, B;             // first sample of the sub-batch in the batch, and how many
-  hipStream_t st;
-};
-
-// sub-batch streams of a float32-grade forward (one function for forward_strict and esmdiff_describe_plan).  (r06: with frames set
-// the two-queue forward was not deterministic while geom_attention_kernel held packed float ops beside the other queue's GEMM: geom.hip.)
-static int strict_parts(const esmdiff_engine* e, int B, int L) {
-  return (e->split && !e->side.empty() && e->profiling != 1 && B >= 2 && (int64_t)B * L >= kStrictDualMinTokens) ? 2 : 1;
-}
-
-static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int ld, int L) {
+// F32_SPLIT at large batches: two sub-batches on two streams, as the 16-bit engine does (every kernel's row results are
+// independent of the batch, so the cut changes no bit): the persistent split GEMMs leave CUs idle in their last round and the
+// other sub-batch's kernels fill them.  This is one sub-batch, enqueued whole; cond: its first conditioning row.
+int strict_part(esmdiff_engine* e, const Part& w, const float* cond, int ld, int L) {
   const esmdiff_config& c = e->cfg;
   const int D = c.d_model, H = c.n_heads, FH = c.ffn_hidden;
   const bool geom = e->has_geom && e->frames_B > 0;
@@ -226,52 +221,116 @@ static int strict_part(esmdiff_engine* e, const SPart& w, const float* cond, int
   return 0;
 }
 
-int forward_strict(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, const float* t_freq_dev, float* logits,
-                   int ld, int B, int L, hipStream_t st) {
+// The launch sequence of the 16-bit-operand engines (bf16, or f16: the ed16 build of the same kernel sources, ed_half.h), enqueued
+// launch by launch across the sub-batches.  T(launch_x(..)) is a launcher that exists per operand type, chosen by e->f16; a
+// launcher spelled plainly exists once (embed, and the float32-grade head's kernels).
+int forward_16bit(esmdiff_engine* e, const Part* parts, BatchPlan plan, const float* cond, int ld, int L) {
   const esmdiff_config& c = e->cfg;
-  const int D = c.d_model, FH = c.ffn_hidden;
-  Prof p{e, st};
-  const float* cond = nullptr;
-  if (t_freq_dev && e->sig_w1) {
-    RUN(S_EMBED, launch_sigma_mlp(t_freq_dev, e->sig_w1, e->sig_b1, e->sig_w2, e->sig_b2, e->sig_hidden, e->cond, c.freq_dim, D, st,
-                                  e->sigma_rows));
-    cond = e->cond;
-  }
-  const bool geom = e->has_geom && e->frames_B > 0;
-  if (geom && (e->frames_B != B || e->frames_L != L))
-    return fail(e, ESMDIFF_E_INVALID, "frames were set for B=%d L=%d, forward called with B=%d L=%d", e->frames_B, e->frames_L, B, L);
-  // F32_SPLIT at large batches: two sub-batches on two streams, as the bf16 engine does (every kernel's row results are
-  // independent of the batch, so the cut changes no bit): the persistent split GEMMs leave CUs idle in their last round and the
-  // other sub-batch's kernels fill them.
-  const int np = strict_parts(e, B, L);
-  const int64_t WS = 3 * (int64_t)std::max(D, FH);
-  SPart parts[2];
-  for (int pi = 0; pi < np; ++pi) {
-    const int b0 = (int)((int64_t)B * pi / np), b1 = (int)((int64_t)B * (pi + 1) / np);
-    const int64_t t0 = (int64_t)b0 * L;
-    auto off = [&](float* p_, int64_t stride) { return p_ ? p_ + t0 * stride : nullptr; };
-    parts[pi] = SPart{seq + t0, xtok + t0, off(e->x, D), off(e->fh, D), off(e->fh2, D), off(e->fqkv, 3 * D), off(e->fq, D), off(e->fk, D),
-                      off(e->fctx, D), off(e->fgu, 2 * FH), off(e->fmid, FH), off(e->fgp, 15 * e->v_heads), off(e->fgctx, 3 * e->v_heads),
-                      off(e->fpair_qk, 128), logits + t0 * ld, off(e->pl_logits, e->ld_plddt), e->a2 ? e->a2 + t0 * WS : nullptr,
-                      e->rs ? e->rs + t0 : nullptr, e->f_rot ? e->f_rot + t0 * 9 : nullptr, e->f_trans ? e->f_trans + t0 * 3 : nullptr,
-                      e->f_mask ? e->f_mask + t0 : nullptr, e->cur_lens ? e->cur_lens + b0 : nullptr, b0, b1 - b0, pi == 0 ? st : e->side[pi - 1]};
-  }
-  if (int r = fork_streams(e, st, np)) return r;
-  for (int pi = 0; pi < np; ++pi)   // (per-sample sigmas: the part's first conditioning row)
-    if (int r = strict_part(e, parts[pi], cond && e->sigma_rows > 1 ? cond + (int64_t)parts[pi].b0 * D : cond, ld, L)) return r;
-  return join_streams(e, st, np);
-}
+  const int D = c.d_model, H = c.n_heads, FH = c.ffn_hidden;
+  const float inv_scale = 1.0f / c.residue_scale;
+  const int np = plan.np;
+  Prof p{e, parts[0].st};
+  const int cond_stride = e->sigma_rows > 1 ? D : 0;   // esmdiff_forward_logits_sigmas: one conditioning vector per sample
+#define T(call) ED_KN(e->f16, call)
+#define EACH(section, expr)                  \
+  do {                                       \
+    for (int pi = 0; pi < np; ++pi) {        \
+      const Part& w = parts[pi];             \
+      const int M = w.B * L;                 \
+      (void)M;                               \
+      p.s = w.st;                            \
+      RUN(section, expr);                    \
+    }                                        \
+  } while (0)
 
-#define KN ed
-#define ED_FWD_NAME forward_bf16
-#include "engine_forward.inc"
-#undef KN
-#undef ED_FWD_NAME
-#define KN ed16
-#define ED_FWD_NAME forward_f16
-#include "engine_forward.inc"
-#undef KN
-#undef ED_FWD_NAME
+  if (e->kind == 1) {
+    EACH(S_EMBED, launch_gather_rows(w.xtok, e->e_struct, w.x, M, D, ESMDIFF_VOCAB, w.st));
+  } else {
+    EACH(S_EMBED, launch_embed(w.seq, w.xtok, e->e_seq, e->e_struct, e->cvec,
+                               cond ? cond + (int64_t)w.b0 * cond_stride : nullptr, w.x, w.B, L, D, w.st, cond_stride));
+  }
+  // The residual stream x stays f32.  Each branch GEMM (out-proj -> dlt2, FFN-down -> dlt) writes its output, already
+  // divided by the residue scale, as a bf16 delta; the LayerNorm kernels add the deltas while they read x anyway, so no
+  // GEMM epilogue does a read-modify-write.  x is written back once per block: the attention-side LayerNorm only
+  // forms x + dF(previous block) in registers, the FFN-side one forms (x + dF) + dA — the same two f32 additions in the
+  // same order as adding them one LayerNorm apart — and stores it.
+  const bool geom = e->has_geom && e->frames_B > 0;
+  const int VH = e->v_heads;
+  bool pending = false;
+  // Small batches (a sub-batch of < 1 152 rows, ed::small_max_rows()): the two branch linears leave their products as raw f32 K-slice planes
+  // (gemm.hip: launch_gemm_partials) and the LayerNorm that follows sums the planes into x — x += dF before the
+  // attention-side LayerNorm, x += dA before the FFN-side one: the same two additions in the same order — so neither a
+  // split-K reduce pass nor a bf16 delta round trip runs.  Sub-batches of one forward are all on the same side of the
+  // switch or results would depend on how the batch was cut; parts differ by at most one sample, so test part 0's rows.
+  const bool small = plan.small;
+  GemmPartials PF[4] = {}, PA[4] = {};
+  for (int i = 0; i < c.n_layers; ++i) {
+    const Layer& ly = e->layers[i];
+    if (small) {
+      if (pending) EACH(S_LN, T(launch_add_partials_layernorm_bf16(w.x, PF[pi], D, inv_scale, ly.ln1_w, ly.ln1_b, w.h, M, D, w.st)));
+      else EACH(S_LN, T(launch_add_layernorm_bf16(w.x, nullptr, nullptr, 0, ly.ln1_w, ly.ln1_b, w.h, M, D, w.st)));
+    } else {
+      EACH(S_LN, T(launch_add_layernorm_bf16(w.x, pending ? w.dlt : nullptr, nullptr, 0, ly.ln1_w, ly.ln1_b, w.h, M, D, w.st)));
+    }
+    EACH(S_QKV, T(launch_gemm_bf16(w.h, ly.w_qkv.w16(), w.qkv, nullptr, M, 3 * D, D, 3 * D, 3 * D, 1.f, ESMDIFF_EPI_BF16, w.st, w.gws)));
+    EACH(S_QKROPE, T(launch_qk_norm_rope(w.qkv, ly.q_ln_w, ly.k_ln_w, e->rope_cos, e->rope_sin, w.q, w.k, w.B, L, H, w.st)));
+    EACH(S_ATTN, T(launch_attention(w.q, w.k, w.qkv, w.ctx, w.B, L, H, w.st, w.lens)));
+    if (small) EACH(S_OUT, T(launch_gemm_partials(w.ctx, ly.w_out.w16(), w.gws2, M, D, D, w.st, &PA[pi])));
+    else EACH(S_OUT, T(launch_gemm_bf16(w.ctx, ly.w_out.w16(), w.dlt2, nullptr, M, D, D, D, D, inv_scale, ESMDIFF_EPI_BF16, w.st, w.gws)));
+    const bool geom_here = i == 0 && geom;
+    if (geom_here) {
+      // x += dA; s = s_norm(x); p = proj(s); geometric attention; dG = out_proj(.) / scale  (block 0 only; the FFN-side
+      // LayerNorm below then adds dG instead of dA)
+      if (small) EACH(S_LN, T(launch_add_partials_layernorm_bf16(w.x, PA[pi], D, inv_scale, e->g_snorm_w, nullptr, w.h, M, D, w.st)));
+      else EACH(S_LN, T(launch_add_layernorm_bf16(w.x, nullptr, w.dlt2, 1, e->g_snorm_w, nullptr, w.h, M, D, w.st)));
+      EACH(S_ATTN, T(launch_gemm_bf16(w.h, e->g_proj.w16(), w.gp, nullptr, M, 15 * VH, D, 15 * VH, 15 * VH, 1.f, ESMDIFF_EPI_BF16, w.st, w.gws)));
+      EACH(S_ATTN, T(launch_geom_attention(w.gp, w.f_rot, w.f_trans, w.f_mask, e->g_wrot, e->g_wdist, w.gctx, w.B, L, VH, w.st)));
+      EACH(S_ATTN, T(launch_gemm_bf16(w.gctx, e->g_out.w16(), w.dlt2, nullptr, M, D, 3 * VH, D, D, inv_scale, ESMDIFF_EPI_BF16, w.st, w.gws)));
+    }
+    if (small && !geom_here) {
+      EACH(S_LN, T(launch_add_partials_layernorm_bf16(w.x, PA[pi], D, inv_scale, ly.ln2_w, ly.ln2_b, w.h, M, D, w.st)));
+    } else if (small) {  // x already holds x + dF + dA; the geometric branch came back as a bf16 delta
+      EACH(S_LN, T(launch_add_layernorm_bf16(w.x, nullptr, w.dlt2, 1, ly.ln2_w, ly.ln2_b, w.h, M, D, w.st)));
+    } else {
+      EACH(S_LN, T(launch_add_layernorm_bf16(w.x, pending ? w.dlt : nullptr, w.dlt2, 1, ly.ln2_w, ly.ln2_b, w.h, M, D, w.st)));
+    }
+    EACH(S_FFN_UP, T(launch_gemm_bf16(w.h, ly.w_up.w16(), w.mid, nullptr, M, 2 * FH, D, FH, FH, 1.f, ESMDIFF_EPI_SWIGLU_BF16, w.st, w.gws)));
+    if (small) EACH(S_FFN_DOWN, T(launch_gemm_partials(w.mid, ly.w_down.w16(), w.gws, M, D, FH, w.st, &PF[pi])));
+    // (no split-K workspace here: on the regular path a row's K order must not depend on how many rows its sub-batch has —
+    //  with the workspace a part below 1 152 rows next to a larger one, e.g. B = 9 at L_tok = 258 cut 4 + 5, summed its FFN-down
+    //  in 8 slices and the other part in one pass, and step-0 sharing / batch composition changed the last bit: ADVICE r03)
+    else EACH(S_FFN_DOWN, T(launch_gemm_bf16(w.mid, ly.w_down.w16(), w.dlt, nullptr, M, D, FH, D, D, inv_scale, ESMDIFF_EPI_BF16, w.st, nullptr)));
+    pending = true;
+  }
+  e->last_pending_delta = !small && pending;
+  if (e->head_split) {
+    // f32-grade head on the bf16 body (esmdiff_config.head_precision = 1): final LayerNorm of the f32 residual stream (plus
+    // the last FFN-down delta, which the regular path keeps outside x) -> Linear + bias -> GELU -> LayerNorm -> Linear + bias,
+    // LayerNorms in the strict path's arithmetic, linears as three f16 MFMA passes over split rows (gemm_split.hip)
+    if (small && pending) EACH(S_LN, T(launch_add_partials_layernorm_bf16(w.x, PF[pi], D, inv_scale, e->final_ln_w, nullptr, w.h, M, D, w.st)));  // x += dF
+    EACH(S_LN, launch_layernorm_split(w.x, e->final_ln_w, nullptr, w.a2, w.rs, nullptr, M, D, 0, w.st,
+                                      (!small && pending) ? w.dlt : nullptr, e->f16 ? 1 : 0));
+    EACH(S_HEAD, launch_gemm256w4_split(w.a2, w.rs, e->head_w0.split(), e->head_w0.inv, w.fh2, e->head_b0, M, D, D, D, 1.f, ESMDIFF_F32EPI_STORE, w.st));
+    EACH(S_LN, launch_layernorm_split(w.fh2, e->head_ln_w, e->head_ln_b, w.a2, w.rs, nullptr, M, D, 1, w.st));
+    EACH(S_HEAD, launch_gemm256w4_split(w.a2, w.rs, e->head_w3.split(), e->head_w3.inv, w.logits, e->head_b3, M, e->vocab_pad, D, ld, 1.f, ESMDIFF_F32EPI_STORE, w.st));
+    return 0;
+  }
+  if (small && pending) EACH(S_LN, T(launch_add_partials_layernorm_bf16(w.x, PF[pi], D, inv_scale, e->final_ln_w, nullptr, w.h, M, D, w.st)));
+  else EACH(S_LN, T(launch_add_layernorm_bf16(w.x, pending ? w.dlt : nullptr, nullptr, 0, e->final_ln_w, nullptr, w.h, M, D, w.st)));
+  EACH(S_HEAD, T(launch_gemm_bf16(w.h, e->head_w0.w16(), w.h2, e->head_b0, M, D, D, D, D, 1.f, ESMDIFF_EPI_BIAS_GELU_BF16, w.st, w.gws)));
+  // decoder: the pLDDT head reads the same normalised hidden state (w.h) before the structure head's LayerNorm reuses it;
+  // its intermediates live in ctx / q, which are free after the last block
+  if (e->has_plddt) EACH(S_HEAD, T(launch_gemm_bf16(w.h, e->pl_w0.w16(), w.ctx, e->pl_b0, M, D, D, D, D, 1.f, ESMDIFF_EPI_BIAS_GELU_BF16, w.st, w.gws)));
+  // ... and so does the pairwise head's down-projection (q | k, 64 + 64 columns per token)
+  if (e->has_pair) EACH(S_HEAD, T(launch_gemm_bf16(w.h, e->pw_down.w16(), w.pair_qk, nullptr, M, 128, D, 128, 128, 1.f, ESMDIFF_EPI_BF16, w.st, w.gws)));
+  EACH(S_LN, T(launch_layernorm_bf16_in(w.h2, e->head_ln_w, e->head_ln_b, w.h, M, D, w.st)));
+  if (e->has_plddt) EACH(S_LN, T(launch_layernorm_bf16_in(w.ctx, e->pl_ln_w, e->pl_ln_b, w.q, M, D, w.st)));
+  EACH(S_HEAD, T(launch_gemm_bf16(w.h, e->head_w3.w16(), w.logits, e->head_b3, M, e->vocab_pad, D, ld, c.vocab_out, 1.f, ESMDIFF_EPI_BIAS_F32, w.st, w.gws)));
+  if (e->has_plddt) EACH(S_HEAD, T(launch_gemm_bf16(w.q, e->pl_w3.w16(), w.pl_logits, e->pl_b3, M, 128, D, e->ld_plddt, e->plddt_bins, 1.f, ESMDIFF_EPI_BIAS_F32, w.st, w.gws)));
+#undef EACH
+#undef T
+  return 0;
+}
 
 }  // namespace
 
@@ -310,12 +369,33 @@ int eng::forward(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, con
   e->last_B = B;
   e->last_L = L;
   e->last_pending_delta = false;
-  if (e->strict) {
-    e->stat_forwards += 1;
-    e->stat_rows += (int64_t)B * L;
-    return forward_strict(e, seq, xtok, t_freq_dev, logits, ld, B, L, st);
+  e->stat_forwards += 1;
+  e->stat_rows += (int64_t)B * L;
+  if (e->has_geom && e->frames_B > 0 && (e->frames_B != B || e->frames_L != L))
+    return fail(e, ESMDIFF_E_INVALID, "frames were set for B=%d L=%d, forward called with B=%d L=%d", e->frames_B, e->frames_L, B, L);
+  const int D = e->cfg.d_model;
+  Prof p{e, st};
+  const float* cond = nullptr;
+  // sigma_embedder runs whenever its weights were loaded and the caller hands a sinusoid: with time conditioning off the
+  // reference still adds sigma_embedder(0) (model.py:466-471 with _process_sigma zeroing sigma, :535-541), and the
+  // host passes the sinusoid of 0 for that case
+  if (t_freq_dev && e->sig_w1) {
+    RUN(S_EMBED, launch_sigma_mlp(t_freq_dev, e->sig_w1, e->sig_b1, e->sig_w2, e->sig_b2, e->sig_hidden, e->cond, e->cfg.freq_dim, D, st,
+                                  e->sigma_rows));
+    cond = e->cond;
   }
-  return e->f16 ? forward_f16(e, seq, xtok, t_freq_dev, logits, ld, B, L, st) : forward_bf16(e, seq, xtok, t_freq_dev, logits, ld, B, L, st);
+  // profiling == 1 (per-section breakdown) keeps one stream so that the sections do not overlap
+  const BatchPlan plan = plan_batch(e, B, L);
+  Part parts[4];
+  cut_batch(e, parts, plan.np, seq, xtok, logits, ld, B, L, st);
+  if (int r = fork_streams(e, st, plan.np)) return r;
+  if (e->strict) {   // part after part (per-sample sigmas: the part's first conditioning row)
+    for (int pi = 0; pi < plan.np; ++pi)
+      if (int r = strict_part(e, parts[pi], cond && e->sigma_rows > 1 ? cond + (int64_t)parts[pi].b0 * D : cond, ld, L)) return r;
+  } else if (int r = forward_16bit(e, parts, plan, cond, ld, L)) {
+    return r;
+  }
+  return join_streams(e, st, plan.np);
 }
 
 extern "C" {
@@ -331,13 +411,12 @@ int esmdiff_describe_plan(const esmdiff_engine* e, int32_t B, int32_t L, char* b
   auto at = [&]() { return tmp + (n < (int)sizeof tmp ? n : (int)sizeof tmp - 1); };
   const char* prec = e->strict ? (e->split ? "f32_split" : "f32") : (e->f16 ? "f16" : "bf16");
   n += snprintf(at(), room(), "precision=%s head=%s B=%d L=%d", prec, (e->strict || e->head_split) ? "f32-grade" : prec, B, L);
+  const int np = plan_parts(e, B, L);
   if (e->strict) {
     const int64_t tokens = (int64_t)B * L;
-    const int np = strict_parts(e, B, L);
     n += snprintf(at(), room(), " streams=%d path=%s k_sliced_small_batches=%d", np,
                   e->split ? "split(3 f16 MFMA passes, 256x256w4)" : "strict(f32 MFMA)", e->sk_parts && tokens <= kSplitkMaxRows ? 1 : 0);
   } else {
-    const int np = plan_parts(e, B, L);
     const bool small = plan_small(e, B, L);
     const int m0 = (int)((int64_t)B / np) * L;
     char g1[32], g2[32], g3[32], g4[32];

@@ -1174,6 +1174,90 @@ def test_two_queue_forward_with_frames_equals_the_one_queue_forward_in_every_eng
     assert not any(rec.values()), rec
 
 
+_CUT_ENGINES = {"bf16": ("bf16", None), "f16": ("f16", None), "bf16_f32head": ("bf16", "f32"), "f16_f32head": ("f16", "f32"),
+                "f32_split": ("f32_split", None)}
+
+
+@pytest.mark.parametrize("kind", [*_CUT_ENGINES, "decoder"])
+def test_every_sub_batch_offset_gives_the_one_queue_forward(kind):
+    """A forward cut into two sub-batches reads and writes every engine buffer at the second part's row offset; a wrong offset or
+    stride of any of them (workspace rows, the float32-grade head's split rows and row scales, per-sample conditioning rows, frames,
+    the split-K workspaces' queue, the decoder's pair and pLDDT rows) shows as a difference from the one-queue forward (profiling
+    mode 1), which offsets nothing.  Bit for bit throughout; the smallest shapes that still cut:
+      16-bit engines, with and without the float32-grade head   (10, 258)  two regular parts of 1 290 rows
+                                                                 (8, 100)   800 tokens: the all-small two-queue window, small-batch
+                                                                            path on either queue count
+      F32_SPLIT                                                  (4, 2100)  8 400 tokens >= the 8 192 of its two-queue threshold
+      bf16 decoder with both confidence heads                    (10, 258)  coordinates, pLDDT, pTM, PAE
+    TINY with block 0's geometric branch, different tokens and one sigma per sample, frames on all but a window of residues and a
+    different backbone per sample (sample 0's centred at the origin); logits and ESMOutput.embeddings are compared."""
+    import ctypes
+    from esmdiff_amd import _native as N
+    if kind == "decoder":
+        from esmdiff_amd.config import TINY_DECODER
+        from esmdiff_amd.engine import StructureDecoder
+        from esmdiff_amd.weights import random_init_decoder_state_dict
+        B, L = 10, 258
+        sd = random_init_decoder_state_dict(TINY_DECODER, seed=2)
+        assert "pairwise_classification_head.linear2.weight" in sd and "plddt_head.3.weight" in sd
+        dec = StructureDecoder(TINY_DECODER, sd, max_batch=B, max_len=L, precision="bf16")
+        tok = torch.randint(0, 4096, (B, L), generator=torch.Generator().manual_seed(7))
+        tok[:, 0], tok[:, -1] = 4098, 4097
+        buf = ctypes.create_string_buffer(2048)
+        try:
+            outs = {}
+            for queues in (2, 1):
+                N.check(N.lib().esmdiff_set_profiling(dec._h, 1 if queues == 1 else 0), dec._h)
+                assert N.lib().esmdiff_describe_plan(dec._h, B, L, buf, 2048) > 0
+                assert f"streams={queues} " in buf.value.decode(), buf.value.decode()
+                outs[queues] = [t.cpu() for t in dec.decode(tok, return_plddt=True, return_ptm=True, return_pae=True)]
+            for name, two, one in zip(("coordinates", "plddt", "ptm", "pae"), outs[2], outs[1]):
+                assert torch.isfinite(two).all() and torch.equal(two, one), (name, (two != one).nonzero()[:3].tolist())
+            assert len({float(v) for v in outs[2][2]}) == B                   # ten different samples
+        finally:
+            dec.close()
+        return
+    from esmdiff_amd.config import TINY
+    from esmdiff_amd.engine import Engine
+    from esmdiff_amd.geometry import build_affine3d_from_coordinates
+    from esmdiff_amd.schedule import timestep_embedding
+    from esmdiff_amd.weights import random_init_state_dict
+    precision, head = _CUT_ENGINES[kind]
+    shapes = ((4, 2100),) if kind == "f32_split" else ((10, 258), (8, 100))
+    sd = random_init_state_dict(TINY, seed=11, with_geom=True)
+    eng = Engine(TINY, sd, max_batch=max(b for b, _ in shapes), max_len=max(l for _, l in shapes), precision=precision, head_precision=head)
+    try:
+        for B, L in shapes:
+            g = torch.Generator().manual_seed(B * L)
+            seq = torch.stack([_seq(1, L, g)[0] for _ in range(B)]).cuda()
+            x = torch.randint(0, 4096, (B, L), generator=g)
+            x[:, 0], x[:, -1] = 4098, 4097
+            lo, hi = L // 3, L // 3 + L // 4                                   # the window without frames
+            x[:, lo:hi] = MASK
+            x = x.cuda()
+            tf = timestep_embedding(torch.linspace(0.05, 6.9, B), TINY.freq_dim)
+            ca = torch.cumsum(torch.nn.functional.normalize(torch.randn(B, L, 3, generator=g), dim=-1) * 3.8, 1)
+            ca[0] -= ca[0].mean(0)
+            xyz = torch.stack([ca + torch.tensor([-1.2, 0.7, 0.0]), ca, ca + torch.tensor([1.3, 0.6, 0.1])], 2)
+            xyz[:, lo:hi] = float("inf")
+            xyz[:, 0] = xyz[:, -1] = float("nan")
+            eng.set_frames(*build_affine3d_from_coordinates(xyz))
+            outs = {}
+            for queues in (2, 1):
+                eng.set_profiling(1 if queues == 1 else 0)
+                assert f"streams={queues} " in eng.describe_plan(B, L), eng.describe_plan(B, L)
+                logits = eng.forward_logits(x, seq, tf).clone()
+                outs[queues] = (logits, eng.embeddings(B, L))
+            eng.set_profiling(0)
+            eng.set_frames(None)
+            for name, two, one in zip(("logits", "embeddings"), outs[2], outs[1]):
+                bad = (two != one).flatten(1).any(1).nonzero().flatten().tolist()
+                assert torch.isfinite(two).all() and not bad, (kind, B, L, name, "differing samples", bad)
+            assert not torch.equal(outs[2][0][0], outs[2][0][B - 1])          # the samples differ
+    finally:
+        eng.close()
+
+
 @pytest.mark.parametrize("streamed", [False, True])
 def test_certified_gibbs_tiny_with_coordinates_ragged_and_streaming(streamed):
     """CertifiedSampler.gibbs_sample on the real engines (TINY model, the reference's default mode, sample_esmdiff.py:66-130):

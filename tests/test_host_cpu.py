@@ -132,8 +132,9 @@ def test_hand_placed_gemm_has_no_sgpr_reload_hazard():
     import sys
     sys.path.insert(0, str(ROOT / "tools"))
     import check_asm_hazards as chk
+    from esmdiff_amd.build import F16_FLAGS
     csrc = ROOT / "esmdiff_amd" / "csrc"
-    for src, extra in ((csrc / "gemm256w4.hip", []), (csrc / "gemm256w4.hip", ["-DED_F16", "-Ded=ed16"]), (csrc / "gemm256w4_split.hip", [])):
+    for src, extra in ((csrc / "gemm256w4.hip", []), (csrc / "gemm256w4.hip", F16_FLAGS), (csrc / "gemm256w4_split.hip", [])):
         r = subprocess.run(["/opt/rocm/bin/hipcc", *chk.FLAGS, *extra, str(src), "-o", "/dev/stdout"], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
         seen = 0
