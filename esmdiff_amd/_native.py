@@ -69,6 +69,7 @@ EXPORTS = [
     "esmdiff_dim6_to_backbone", "esmdiff_plddt_mean", "esmdiff_pair_features", "esmdiff_pae_tm",
     "esmdiff_decoder_set_pair_chunk_bytes",
     "esmdiff_encoder_knn", "esmdiff_encoder_neighbourhood", "esmdiff_encoder_nearest_code",
+    "esmdiff_forward_logits_needed", "esmdiff_get_tail_rows",
 ]
 LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
 DSSP_MAX_L = 4096                            # ESMDIFF_DSSP_MAX_L
@@ -76,7 +77,7 @@ TM_MAX_L = 1280                              # ESMDIFF_TM_MAX_L
 
 CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
-OPT_STREAMS, OPT_DUAL_MIN_TOKENS = 1, 2      # esmdiff_option
+OPT_STREAMS, OPT_DUAL_MIN_TOKENS, OPT_NEEDED_ROWS = 1, 2, 3      # esmdiff_option
 
 
 def flex_pair_slots(n: int) -> int:
@@ -116,6 +117,8 @@ def lib():
     L.esmdiff_forward_logits.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
     L.esmdiff_forward_logits_sigmas.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
     L.esmdiff_forward_logits_sigmas.restype = ctypes.c_int
+    L.esmdiff_forward_logits_needed.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    L.esmdiff_get_tail_rows.argtypes = [vp, c_i64p, i32]
     L.esmdiff_ddpm_step.argtypes = [vp, vp, vp, i32, f32, f32, i32, vp, ctypes.POINTER(Rng), i32, i32, i32, vp]
     L.esmdiff_ddpm_step_margin.argtypes = [vp, vp, vp, i32, f32, f32, i32, ctypes.POINTER(Rng), i32, i32, i32, f32, vp, vp]
     L.esmdiff_ddpm_step_margin.restype = ctypes.c_int

@@ -153,6 +153,15 @@ struct esmdiff_engine {
   int g_strategy = 0;
   uint32_t* g_inv_mask = nullptr;
   bool g_inv_on = false;
+  // needed rows (esmdiff_set_option(ESMDIFF_OPT_NEEDED_ROWS); engine_forward.hip: needed_tail): a forward of esmdiff_ddpm_sample runs
+  // the last block's branches and the head on the rows that hold MASK.  rows_list / rows_map: launch_mask_row_list's outputs,
+  // rows_count: its counts per sub-batch in pinned host memory, ev_rows: recorded behind it.  rows_mapped: the last forward left
+  // compact logits (the sampler reads them through rows_map) and x / logits of the other rows stale.
+  int needed_rows = 1;
+  int32_t *rows_list = nullptr, *rows_map = nullptr, *rows_count = nullptr;
+  hipEvent_t ev_rows = nullptr;
+  bool rows_mapped = false;
+  int64_t stat_tail_rows = 0;   // rows that ran the last block's branches and the head (esmdiff_get_tail_rows)
   int64_t stat_forwards = 0, stat_rows = 0;
   int last_B = 0, last_L = 0;       // shape of the last forward, and whether its last FFN-down delta is still outside x
   bool last_pending_delta = false;  // (regular bf16 path: the final add+LayerNorm forms x + dF in registers only)
@@ -176,8 +185,9 @@ int check_bl(esmdiff_engine* e, int B, int L);
 int check_lens(esmdiff_engine* e, int B, int L);
 int check_not_decoder(esmdiff_engine* e);
 // engine_forward.hip
+// needed_rows: the caller reads logits on the rows with xtok == MASK only (through e->rows_map while e->rows_mapped)
 int forward(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, const float* t_freq_dev, float* logits, int ld, int B, int L,
-            hipStream_t st);
+            hipStream_t st, bool needed_rows = false);
 int shared_forward_batch(const esmdiff_engine* e, int B, int L);
 
 #define HIP_TRY(e, call)                                                                              \

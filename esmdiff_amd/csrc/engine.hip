@@ -249,6 +249,10 @@ int esmdiff_set_option(esmdiff_engine* e, int32_t option, int64_t value) {
       if (value < 1) return fail(e, ESMDIFF_E_INVALID, "ESMDIFF_OPT_DUAL_MIN_TOKENS must be positive");
       e->dual_min_tokens = value;
       return 0;
+    case ESMDIFF_OPT_NEEDED_ROWS:
+      if (value != 0 && value != 1) return fail(e, ESMDIFF_E_INVALID, "ESMDIFF_OPT_NEEDED_ROWS: 0 or 1, got %lld", (long long)value);
+      e->needed_rows = (int)value;
+      return 0;
     default:
       return fail(e, ESMDIFF_E_INVALID, "unknown option %d", option);
   }
@@ -299,6 +303,13 @@ int esmdiff_get_counters(esmdiff_engine* e, int64_t* forwards, int64_t* token_ro
   return 0;
 }
 
+int esmdiff_get_tail_rows(esmdiff_engine* e, int64_t* rows_out, int32_t reset) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (rows_out) *rows_out = e->stat_tail_rows;
+  if (reset) e->stat_tail_rows = 0;
+  return 0;
+}
+
 int esmdiff_abi_version(void) { return ESMDIFF_ABI_VERSION; }
 
 const char* esmdiff_last_error(const esmdiff_engine* eng) { return eng ? eng->err.c_str() : g_create_error.c_str(); }
@@ -312,6 +323,8 @@ void esmdiff_engine_destroy(esmdiff_engine* e) {
     if (p) hipFree(p);
   for (hipEvent_t ev : e->ev) hipEventDestroy(ev);
   if (e->ev_fork) hipEventDestroy(e->ev_fork);
+  if (e->ev_rows) hipEventDestroy(e->ev_rows);
+  if (e->rows_count) hipHostFree(e->rows_count);
   for (hipEvent_t ev : e->ev_join) hipEventDestroy(ev);
   for (hipStream_t sd : e->side) hipStreamDestroy(sd);
   delete e;
@@ -630,6 +643,15 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
   if (hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess)
     return bail(fail(e, ESMDIFF_E_HIP, "engine create: fork event: %s", hipGetErrorString(hipGetLastError())));
   if (int r = add_side_stream(e)) return bail(r);
+  // needed rows: the row lists of a forward's sub-batches, and their counts where the host reads them (one slot per launch queue)
+  if (!strict && kind == 0) {
+    const size_t Mx = (size_t)cfg->max_batch * cfg->max_len;
+    if (int r = dalloc(e, &e->rows_list, Mx)) return bail(r);
+    if (int r = dalloc(e, &e->rows_map, Mx)) return bail(r);
+    if (hipHostMalloc((void**)&e->rows_count, 4 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&e->ev_rows, hipEventDisableTiming) != hipSuccess)
+      return bail(fail(e, ESMDIFF_E_HIP, "engine create: needed-rows count slot: %s", hipGetErrorString(hipGetLastError())));
+  }
   // the launch-skipping switch of the retired timing experiments gave wrong results by construction; a library that finds it in
   // the environment refuses to start rather than silently ignore a request it once honoured
   if (getenv("ESMDIFF_DEBUG_SKIP"))

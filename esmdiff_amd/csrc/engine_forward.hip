@@ -10,7 +10,8 @@
 // False, net.py:433-441 with mask_and_zero_frameless=True, net.py:344) and is skipped; with frames set through
 // esmdiff_set_frames it runs between the attention branch and the FFN of block 0 (geom.hip).
 // Work is enqueued on the caller's stream, plus one engine-owned stream for the second half of a large batch
-// (forked and joined with events, see forward()); a forward never synchronises.
+// (forked and joined with events, see forward()); a forward never synchronises — except a forward of esmdiff_ddpm_sample, which
+// waits once for the count of the rows its sampler will read (needed_tail()).
 #include "engine.h"
 
 using namespace ed;
@@ -221,17 +222,85 @@ int strict_part(esmdiff_engine* e, const Part& w, const float* cond, int ld, int
   return 0;
 }
 
+#define T(call) ED_KN(e->f16, call)
+
+// Needed rows: what follows the last block's attention, on the rows the ddpm sampler will read.  Everything from the out-projection
+// on is row-wise (GEMMs, LayerNorms, SwiGLU, GELU) and feeds nothing but the logits, and the sampler reads logits only on rows
+// that hold MASK (sampler.hip: ddpm_step_kernel leaves every other row at once), so a sub-batch with M' such rows of M runs
+//   gather ctx -> out-proj -> add+LayerNorm (x and the pending FFN-down delta through the row list; compact x', h) -> FFN-up ->
+//   FFN-down -> final add+LayerNorm -> head GEMM -> head LayerNorm -> head GEMM -> compact logits
+// on M' rows.  Exact: a GEMM row does not depend on M (tests/test_gpu_gemm_dispatch.py; no launch here gets a split-K workspace,
+// so a row's K order is one pass whatever kernel M' lands on), and the row kernels are one wave per row.  Compact buffers, all free
+// once the last attention has run: ctx' in h2, the out-proj delta in q, x' (f32) in qkv, then h / mid / dlt / h2 from their
+// starts, and the logits rows at the start of the sub-batch's own logits (read through e->rows_map).
+// The host learns M' BEFORE it enqueues these launches and AFTER it has enqueued the rest of the forward: it waits for ev_rows,
+// recorded behind launch_mask_row_list at the start of the forward, so what it waits for is at least a whole transformer body
+// ahead of the device's queue tail and no queue runs dry.  A sub-batch with M' above 7/8 M (needed_rows_compact) runs plainly,
+// one with M' = 0 launches nothing; the sub-batches decide independently and their launches interleave as in forward_16bit.
+// The compact FFN-up is timed under the head section: profiling level 2 reports FFN-up launches that are all full-size.
+int needed_tail(esmdiff_engine* e, const Part* parts, int np, const Layer& ly, int ld, int L) {
+  const esmdiff_config& c = e->cfg;
+  const int D = c.d_model, FH = c.ffn_hidden;
+  const float inv_scale = 1.0f / c.residue_scale;
+  Prof p{e, parts[0].st};
+  HIP_TRY(e, hipEventSynchronize(e->ev_rows));
+  int rows[4];
+  bool cmp[4];
+  for (int pi = 0; pi < np; ++pi) {
+    const int M = parts[pi].B * L, n = e->rows_count[pi];
+    if (n < 0 || n > M) return fail(e, ESMDIFF_E_HIP, "needed rows: sub-batch %d counted %d MASK rows of %d", pi, n, M);
+    cmp[pi] = needed_rows_compact(n, M);
+    rows[pi] = cmp[pi] ? n : M;
+    e->stat_tail_rows += rows[pi];
+    e->rows_mapped = e->rows_mapped || cmp[pi];
+  }
+  // one launch per sub-batch that has rows to run and is of the kind `which`: 'c' compact, 'p' plain, 'a' either.  M: the rows of
+  // the launch; the buffers that differ between the two kinds are named here once
+#define TAIL(which, section, expr)                                                            \
+  do {                                                                                        \
+    for (int pi = 0; pi < np; ++pi) {                                                         \
+      const Part& w = parts[pi];                                                              \
+      const int M = rows[pi];                                                                 \
+      const bool k = cmp[pi];                                                                 \
+      if (M == 0 || (which == 'c' && !k) || (which == 'p' && k)) continue;                    \
+      const int32_t* list = e->rows_list + (int64_t)w.b0 * L;   /* the sub-batch's MASK rows */ \
+      float* xc = reinterpret_cast<float*>(w.qkv);              /* compact x' */              \
+      const bf16_t* ctx = k ? w.h2 : w.ctx;                                                   \
+      bf16_t* dA = k ? w.q : w.dlt2;                                                          \
+      float* xf = k ? xc : w.x;                                                               \
+      const GemmWorkspace* gws = k ? nullptr : w.gws;                                         \
+      (void)list, (void)xc, (void)ctx, (void)dA, (void)xf, (void)gws;                         \
+      p.s = w.st;                                                                             \
+      RUN(section, expr);                                                                     \
+    }                                                                                         \
+  } while (0)
+  TAIL('c', S_OUT, launch_gather_rows16(w.ctx, list, w.h2, M, D, w.st));
+  TAIL('a', S_OUT, T(launch_gemm_bf16(ctx, ly.w_out.w16(), dA, nullptr, M, D, D, D, D, inv_scale, ESMDIFF_EPI_BF16, w.st, gws)));
+  TAIL('p', S_LN, T(launch_add_layernorm_bf16(w.x, w.dlt, w.dlt2, 1, ly.ln2_w, ly.ln2_b, w.h, M, D, w.st)));
+  TAIL('c', S_LN, T(launch_add_layernorm_rows_bf16(w.x, w.dlt, list, w.q, xc, ly.ln2_w, ly.ln2_b, w.h, M, D, w.st)));
+  TAIL('a', k ? S_HEAD : S_FFN_UP,   // (the section: see above)
+       T(launch_gemm_bf16(w.h, ly.w_up.w16(), w.mid, nullptr, M, 2 * FH, D, FH, FH, 1.f, ESMDIFF_EPI_SWIGLU_BF16, w.st, gws)));
+  TAIL('a', S_FFN_DOWN, T(launch_gemm_bf16(w.mid, ly.w_down.w16(), w.dlt, nullptr, M, D, FH, D, D, inv_scale, ESMDIFF_EPI_BF16, w.st, nullptr)));
+  TAIL('a', S_LN, T(launch_add_layernorm_bf16(xf, w.dlt, nullptr, 0, e->final_ln_w, nullptr, w.h, M, D, w.st)));
+  TAIL('a', S_HEAD, T(launch_gemm_bf16(w.h, e->head_w0.w16(), w.h2, e->head_b0, M, D, D, D, D, 1.f, ESMDIFF_EPI_BIAS_GELU_BF16, w.st, gws)));
+  TAIL('a', S_LN, T(launch_layernorm_bf16_in(w.h2, e->head_ln_w, e->head_ln_b, w.h, M, D, w.st)));
+  TAIL('a', S_HEAD, T(launch_gemm_bf16(w.h, e->head_w3.w16(), w.logits, e->head_b3, M, e->vocab_pad, D, ld, c.vocab_out, 1.f, ESMDIFF_EPI_BIAS_F32, w.st, gws)));
+#undef TAIL
+  e->last_pending_delta = true;
+  return 0;
+}
+
 // The launch sequence of the 16-bit-operand engines (bf16, or f16: the ed16 build of the same kernel sources, ed_half.h), enqueued
 // launch by launch across the sub-batches.  T(launch_x(..)) is a launcher that exists per operand type, chosen by e->f16; a
-// launcher spelled plainly exists once (embed, and the float32-grade head's kernels).
-int forward_16bit(esmdiff_engine* e, const Part* parts, BatchPlan plan, const float* cond, int ld, int L) {
+// launcher spelled plainly exists once (embed, and the float32-grade head's kernels).  needed: the forward goes on with
+// needed_tail() after the last block's attention.
+int forward_16bit(esmdiff_engine* e, const Part* parts, BatchPlan plan, const float* cond, int ld, int L, bool needed) {
   const esmdiff_config& c = e->cfg;
   const int D = c.d_model, H = c.n_heads, FH = c.ffn_hidden;
   const float inv_scale = 1.0f / c.residue_scale;
   const int np = plan.np;
   Prof p{e, parts[0].st};
   const int cond_stride = e->sigma_rows > 1 ? D : 0;   // esmdiff_forward_logits_sigmas: one conditioning vector per sample
-#define T(call) ED_KN(e->f16, call)
 #define EACH(section, expr)                  \
   do {                                       \
     for (int pi = 0; pi < np; ++pi) {        \
@@ -275,6 +344,7 @@ int forward_16bit(esmdiff_engine* e, const Part* parts, BatchPlan plan, const fl
     EACH(S_QKV, T(launch_gemm_bf16(w.h, ly.w_qkv.w16(), w.qkv, nullptr, M, 3 * D, D, 3 * D, 3 * D, 1.f, ESMDIFF_EPI_BF16, w.st, w.gws)));
     EACH(S_QKROPE, T(launch_qk_norm_rope(w.qkv, ly.q_ln_w, ly.k_ln_w, e->rope_cos, e->rope_sin, w.q, w.k, w.B, L, H, w.st)));
     EACH(S_ATTN, T(launch_attention(w.q, w.k, w.qkv, w.ctx, w.B, L, H, w.st, w.lens)));
+    if (needed && i == c.n_layers - 1) return needed_tail(e, parts, np, ly, ld, L);   // (regular path, not block 0: forward())
     if (small) EACH(S_OUT, T(launch_gemm_partials(w.ctx, ly.w_out.w16(), w.gws2, M, D, D, w.st, &PA[pi])));
     else EACH(S_OUT, T(launch_gemm_bf16(w.ctx, ly.w_out.w16(), w.dlt2, nullptr, M, D, D, D, D, inv_scale, ESMDIFF_EPI_BF16, w.st, w.gws)));
     const bool geom_here = i == 0 && geom;
@@ -332,6 +402,11 @@ int forward_16bit(esmdiff_engine* e, const Part* parts, BatchPlan plan, const fl
   return 0;
 }
 
+// what esmdiff_get_embeddings / esmdiff_get_sequence_logits answer after a forward that went on with the MASK rows only
+const char kStaleRows[] =
+    "the last forward ran inside esmdiff_ddpm_sample on the rows that hold MASK only (ESMDIFF_OPT_NEEDED_ROWS): the other rows' "
+    "hidden state is stale; run a full forward (esmdiff_forward_logits) first, or set the option to 0";
+
 }  // namespace
 
 // Step-0 sharing: the number of leading samples whose forward gives, bit for bit, the logits every sample of an
@@ -365,10 +440,11 @@ int eng::shared_forward_batch(const esmdiff_engine* e, int B, int L) {
 //     B = 16 185 / 167 ms, L_tok = 128 B = 8 188 / 176; below ~700 tokens the halves' GEMMs each stream the whole weight
 //     matrix for half the rows and lose (B = 4 at L_tok = 60: 87.0 / 95.8 ms), and B = 3 at L_tok = 258 cuts into 1 + 2.
 int eng::forward(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, const float* t_freq_dev, float* logits,
-                 int ld, int B, int L, hipStream_t st) {
+                 int ld, int B, int L, hipStream_t st, bool needed_rows) {
   e->last_B = B;
   e->last_L = L;
   e->last_pending_delta = false;
+  e->rows_mapped = false;
   e->stat_forwards += 1;
   e->stat_rows += (int64_t)B * L;
   if (e->has_geom && e->frames_B > 0 && (e->frames_B != B || e->frames_L != L))
@@ -388,13 +464,27 @@ int eng::forward(esmdiff_engine* e, const int64_t* seq, const int64_t* xtok, con
   const BatchPlan plan = plan_batch(e, B, L);
   Part parts[4];
   cut_batch(e, parts, plan.np, seq, xtok, logits, ld, B, L, st);
+  // needed rows: the regular path of a 16-bit engine whose only head is the structure head; needed_tail() names the buffers it
+  // takes over (the extra heads' intermediates live in two of them).  Not under stream capture: the host wait cannot be captured.
+  bool needed = needed_rows && e->needed_rows && e->rows_count && !e->head_split && !plan.small && !e->has_plddt && !e->has_pair &&
+                e->cfg.n_layers >= 2;
+  if (needed) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(e, hipStreamIsCapturing(st, &cs));
+    needed = cs == hipStreamCaptureStatusNone;
+  }
+  if (needed) {   // the MASK rows of each sub-batch, counted for the host: first on the caller's stream, the queues fork behind it
+    HIP_TRY(e, launch_mask_row_list(xtok, B, L, plan.np, e->rows_list, e->rows_map, e->rows_count, st));
+    HIP_TRY(e, hipEventRecord(e->ev_rows, st));
+  }
   if (int r = fork_streams(e, st, plan.np)) return r;
   if (e->strict) {   // part after part (per-sample sigmas: the part's first conditioning row)
     for (int pi = 0; pi < plan.np; ++pi)
       if (int r = strict_part(e, parts[pi], cond && e->sigma_rows > 1 ? cond + (int64_t)parts[pi].b0 * D : cond, ld, L)) return r;
-  } else if (int r = forward_16bit(e, parts, plan, cond, ld, L)) {
+  } else if (int r = forward_16bit(e, parts, plan, cond, ld, L, needed)) {
     return r;
   }
+  if (!needed) e->stat_tail_rows += (int64_t)B * L;
   return join_streams(e, st, plan.np);
 }
 
@@ -432,7 +522,8 @@ int esmdiff_describe_plan(const esmdiff_engine* e, int32_t B, int32_t L, char* b
     else
       n += snprintf(at(), room(), " gemm[qkv]=%s gemm[out]=%s gemm[ffn_up]=%s gemm[ffn_down]=%s", g1, g2, g3, g4);
   }
-  n += snprintf(at(), room(), " step0_sharing=%d final_skip=%d small_max_rows=%d", e->step0_share, e->final_skip, ed::small_max_rows());
+  n += snprintf(at(), room(), " step0_sharing=%d final_skip=%d small_max_rows=%d needed_rows=%d", e->step0_share, e->final_skip,
+                ed::small_max_rows(), e->needed_rows);
   if (e->lens_B == B) {   // ragged batch (esmdiff_set_lengths): attention walks each sample's own keys
     int64_t valid = 0;
     for (int b = 0; b < B; ++b) valid += std::min<int64_t>(e->lens_host[b], L);
@@ -465,6 +556,22 @@ int esmdiff_forward_logits(esmdiff_engine* e, const int64_t* seq, const int64_t*
   return forward(e, seq, x, t_freq, logits_out, ld_logits, B, L, (hipStream_t)stream);
 }
 
+// (esmdiff_hip_test.h) the forward as esmdiff_ddpm_sample runs it, into the engine's own logits, then the MASK rows to the caller's
+int esmdiff_forward_logits_needed(esmdiff_engine* e, const int64_t* seq, const int64_t* x, const float* t_freq,
+                                  float* logits_out, int32_t ld_logits, int32_t B, int32_t L, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (int r = check_not_decoder(e)) return r;
+  if (!seq || !x || !logits_out) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (ld_logits < e->cfg.vocab_out) return fail(e, ESMDIFF_E_INVALID, "ld_logits (%d) below the vocabulary (%d)", ld_logits, e->cfg.vocab_out);
+  if (int r = check_bl(e, B, L)) return r;
+  if (int r = check_lens(e, B, L)) return r;
+  hipStream_t st = (hipStream_t)stream;
+  if (int r = forward(e, seq, x, t_freq, e->logits, e->ld_logits, B, L, st, true)) return r;
+  HIP_TRY(e, launch_copy_masked_logits(x, e->logits, e->ld_logits, e->rows_mapped ? e->rows_map : nullptr, logits_out, ld_logits,
+                                       e->cfg.vocab_out, B * L, st));
+  return 0;
+}
+
 int esmdiff_forward_logits_sigmas(esmdiff_engine* e, const int64_t* seq, const int64_t* x, const float* t_freq,
                                   float* logits_out, int32_t ld_logits, int32_t B, int32_t L, void* stream) {
   if (!e) return ESMDIFF_E_INVALID;
@@ -482,6 +589,7 @@ int esmdiff_get_embeddings(esmdiff_engine* e, float* out, int32_t B, int32_t L, 
   if (!out) return fail(e, ESMDIFF_E_INVALID, "null pointer");
   if (B != e->last_B || L != e->last_L || B <= 0)
     return fail(e, ESMDIFF_E_INVALID, "embeddings of a (%d, %d) forward requested, the last forward was (%d, %d)", B, L, e->last_B, e->last_L);
+  if (e->rows_mapped) return fail(e, ESMDIFF_E_INVALID, "%s", kStaleRows);
   hipStream_t st = (hipStream_t)stream;
   const size_t M = (size_t)B * L, D = e->cfg.d_model;
   HIP_TRY(e, hipMemcpyAsync(out, e->x, M * D * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -498,6 +606,7 @@ int esmdiff_get_sequence_logits(esmdiff_engine* e, float* out, int32_t ld_out, i
   if (!out || ld_out < e->plddt_bins) return fail(e, ESMDIFF_E_INVALID, "bad output");
   if (B != e->last_B || L != e->last_L || B <= 0)
     return fail(e, ESMDIFF_E_INVALID, "sequence logits of a (%d, %d) forward requested, the last forward was (%d, %d)", B, L, e->last_B, e->last_L);
+  if (e->rows_mapped) return fail(e, ESMDIFF_E_INVALID, "%s", kStaleRows);
   HIP_TRY(e, hipMemcpy2DAsync(out, (size_t)ld_out * 4, e->pl_logits, (size_t)e->ld_plddt * 4, (size_t)e->plddt_bins * 4, (size_t)B * L,
                               hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;

@@ -198,19 +198,23 @@ int esmdiff_ddpm_sample(esmdiff_engine* e, const int64_t* seq, int64_t* x_inout,
           HIP_TRY(e, hipMemcpyAsync(e->lens_sub_dev, sub_lens.data(), (size_t)n_run * 4, hipMemcpyHostToDevice, st));
           e->cur_lens = e->lens_sub_dev;
         }
-        const int rf = forward(e, e->cseq, e->cx, t_freq ? e->tfreq + (size_t)i * F : nullptr, e->logits, e->ld_logits, n_run, L, st);
+        const int rf = forward(e, e->cseq, e->cx, t_freq ? e->tfreq + (size_t)i * F : nullptr, e->logits, e->ld_logits, n_run, L, st, true);
         e->cur_lens = e->lens_B ? e->lens_dev : nullptr;
         if (rf) return rf;
-        RUN(S_SAMPLER, launch_ddpm_step(e->cx, e->logits, e->ld_logits, e->cfg.vocab_out, 0.f, 0.f, 1, nullptr, 1, rng->seed, rng->sample_offset, i, n_run, L, st, 0));
+        RUN(S_SAMPLER, launch_ddpm_step(e->cx, e->logits, e->ld_logits, e->cfg.vocab_out, 0.f, 0.f, 1, nullptr, 1, rng->seed, rng->sample_offset, i, n_run, L, st, 0,
+                                        0.f, nullptr, e->rows_mapped ? e->rows_map : nullptr));
         HIP_TRY(e, launch_move_token_rows(e->cx, x_inout, e->idx_dev, n_live, L, 0, st));   // only the live samples go back
         HIP_TRY(e, hipStreamSynchronize(st));                    // idx (host vector) must outlive the H2D copy
         break;
       }
     }
-    if (int r = forward(e, seq, x_inout, t_freq ? e->tfreq + (size_t)i * F : nullptr, e->logits, e->ld_logits, Bf, L, st)) return r;
+    // the update reads logits on the rows that hold MASK only: the forward may run its last block's branches and its head on those
+    // rows alone (engine_forward.hip: needed_tail) and then leaves them compact, found through rows_map
+    if (int r = forward(e, seq, x_inout, t_freq ? e->tfreq + (size_t)i * F : nullptr, e->logits, e->ld_logits, Bf, L, st, true)) return r;
     const int fin = i == T;
     RUN(S_SAMPLER, launch_ddpm_step(x_inout, e->logits, e->ld_logits, e->cfg.vocab_out, fin ? 0.f : mc_t[i], fin ? 0.f : mc_s[i],
-                                    fin, nullptr, 1, rng->seed, rng->sample_offset, i, B, L, st, Bf < B ? Bf : 0));
+                                    fin, nullptr, 1, rng->seed, rng->sample_offset, i, B, L, st, Bf < B ? Bf : 0, 0.f, nullptr,
+                                    e->rows_mapped ? e->rows_map : nullptr));
   }
   return 0;
 }

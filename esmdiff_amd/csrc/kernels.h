@@ -54,7 +54,7 @@ inline hipError_t ensure_dynamic_lds(const void* fn, int bytes) {
 hipError_t launch_ddpm_step(int64_t* x, const float* logits, int ld, int V, float mc_t, float mc_s, int final_,
                             const float* u, int use_philox, uint64_t seed, uint64_t sample_offset, int step,
                             int B, int L, hipStream_t stream, int logits_period = 0, float margin = 0.f,
-                            int32_t* sample_flags = nullptr);
+                            int32_t* sample_flags = nullptr, const int32_t* row_map = nullptr);   // row_map: see launch_mask_row_list
 // the same update with one parameter set per sample (esmdiff_ddpm_step_rows); flags / gap may be null
 hipError_t launch_ddpm_step_rows(int64_t* x, const float* logits, int ld, int V, const esmdiff_sample_step* sp, uint64_t seed,
                                  int B, int L, float margin_ratio, float margin_diff, int32_t* sample_flags, float* sample_gap,
@@ -69,6 +69,19 @@ hipError_t launch_samples_with_mask(const int64_t* x, int B, int L, int32_t* has
 hipError_t launch_move_token_rows(const int64_t* src, int64_t* dst, const int32_t* idx, int n, int L, int gather, hipStream_t stream);
 // flag[0] (device int32) = -1 if every row of seq and x [B, L] equals row 0, else 0
 hipError_t launch_rows_identical(const int64_t* seq, const int64_t* x, int B, int L, int32_t* flag, hipStream_t stream);
+// A sub-batch of `rows` rows of which `count` hold MASK runs the last block's branches and the head on those rows only: up to 7/8 of
+// the rows.  Above that (step 0: every row) the gathers cost more than the rows they drop.  Asked by the host and by
+// mask_row_list_kernel of the same count.
+__host__ __device__ inline bool needed_rows_compact(int count, int rows) { return (int64_t)count * 8 <= (int64_t)rows * 7; }
+// Per sub-batch of x [B, L] (np of them, cut as the forward cuts them): the ascending list of its rows with x == MASK (relative to
+// the sub-batch), their count into pinned host memory, and for every such row the logits row the sampler reads (row_map)
+hipError_t launch_mask_row_list(const int64_t* x, int B, int L, int np, int32_t* list, int32_t* map, int32_t* count_host,
+                                hipStream_t stream);
+// dst[i, :] = src[list[i], :]: n rows of D 16-bit values
+hipError_t launch_gather_rows16(const uint16_t* src, const int32_t* list, uint16_t* dst, int n, int D, hipStream_t stream);
+// out[row, :V] = logits[map ? map[row] : row, :V] on the rows of x that hold MASK; the others are not written
+hipError_t launch_copy_masked_logits(const int64_t* x, const float* logits, int ld, const int32_t* map, float* out, int ld_out,
+                                     int V, int rows, hipStream_t stream);
 
 // ---- score.hip -----------------------------------------------------------------------------
 // xt = (u < move_chance[b] and not non_moving and l < lens[b]) ? MASK : x0, and seq_out likewise with the sequence MASK when not

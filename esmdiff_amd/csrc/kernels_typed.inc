@@ -42,6 +42,10 @@ hipError_t launch_layernorm_bf16(const float* x, const float* w, const float* b,
 // v = (x + delta) + delta2 (bf16 or null each); x = v if write_x; y = LayerNorm(v) * w (+ b)
 hipError_t launch_add_layernorm_bf16(float* x, const bf16_t* delta, const bf16_t* delta2, int write_x, const float* w,
                                      const float* b, bf16_t* y, int M, int D, hipStream_t stream);
+// the same on M compact rows: v[i] = (x[rows[i]] + delta[rows[i]]) + delta2[i] (delta / delta2 16-bit or null; x, delta full-size,
+// delta2 compact); x_out[i] = v[i]; y[i] = LayerNorm(v[i]) * w (+ b)
+hipError_t launch_add_layernorm_rows_bf16(const float* x, const bf16_t* delta, const int32_t* rows, const bf16_t* delta2, float* x_out,
+                                          const float* w, const float* b, bf16_t* y, int M, int D, hipStream_t stream);
 // x += alpha * (P[0] + P[1] + ... + P[S-1]) (f32 K-slice planes of a branch linear); x written back;
 // y = LayerNorm(x) * w (+ b)
 hipError_t launch_add_partials_layernorm_bf16(float* x, const GemmPartials& P, int N, float alpha, const float* w,

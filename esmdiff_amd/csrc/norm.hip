@@ -186,6 +186,74 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(float* __restrict__ 
   }
 }
 
+// add_layernorm_kernel on M compact rows (the last block of a forward that goes on with the rows the sampler reads only,
+// engine_forward.hip: needed_tail): compact row i takes x and delta from row rows[i] of the full-size buffers and delta2 from
+// compact row i, writes the sum to x_out[i] and the normalised row to y[i]; x itself is only read.  The same operations per row
+// in the same order.  A kernel of its own, not a mode of the one above, whose instructions then stay what they were: an extra
+// kernel argument or a shared row function moved its instruction stream (profiles/r14_needed_rows_ab.txt).
+template <int NV>
+__global__ __launch_bounds__(256) void add_layernorm_rows_kernel(const float* __restrict__ x, const bf16_t* __restrict__ delta,
+                                                                 const int32_t* __restrict__ rows,
+                                                                 const bf16_t* __restrict__ delta2, float* __restrict__ x_out,
+                                                                 const float* __restrict__ w, const float* __restrict__ b,
+                                                                 bf16_t* __restrict__ y, int M) {
+  constexpr int D = NV * 256;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int src = rows[row];
+  const float* xr = x + (int64_t)src * D + lane * 4;
+  f32x4 v[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) v[j] = *reinterpret_cast<const f32x4*>(xr + j * 256);
+  auto add_bf16 = [&](const bf16_t* dptr, int r) {
+    const bf16_t* dr = dptr + (int64_t)r * D + lane * 4;
+    uint2 p[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) p[j] = *reinterpret_cast<const uint2*>(dr + j * 256);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      v[j][0] += bf2f(p[j].x & 0xffffu); v[j][1] += bf2f(p[j].x >> 16);
+      v[j][2] += bf2f(p[j].y & 0xffffu); v[j][3] += bf2f(p[j].y >> 16);
+    }
+  };
+  if (delta) add_bf16(delta, src);
+  if (delta2) add_bf16(delta2, row);
+  float* xo = x_out + (int64_t)row * D + lane * 4;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) *reinterpret_cast<f32x4*>(xo + j * 256) = v[j];
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
+  const float mean = wsum(s) * (1.0f / D);
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = v[j][e] - mean;
+      q += d * d;
+    }
+  const float rstd = rsqrtf(wsum(q) * (1.0f / D) + 1e-5f);
+  bf16_t* yr = y + (int64_t)row * D + lane * 4;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const f32x4 ww = *reinterpret_cast<const f32x4*>(w + j * 256 + lane * 4);
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (v[j][e] - mean) * rstd * ww[e];
+    if (b) {
+      const f32x4 bb = *reinterpret_cast<const f32x4*>(b + j * 256 + lane * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] += bb[e];
+    }
+    uint2 pk;
+    pk.x = pack2(o[0], o[1]);
+    pk.y = pack2(o[2], o[3]);
+    *reinterpret_cast<uint2*>(yr + j * 256) = pk;
+  }
+}
+
 // Small-batch path: the branch linear left its product as S raw f32 K-slice planes (gemm.hip: launch_gemm_partials);
 // x += alpha * (P[0] + ... + P[S-1]), summed in that order; x written back; y = LayerNorm(x) * w (+ b).
 // A few hundred rows at most, so latency is everything: ONE WORKGROUP PER ROW (256 threads, thread t owns float4 t and
@@ -299,6 +367,27 @@ hipError_t launch_add_layernorm_bf16(float* x, const bf16_t* delta, const bf16_t
   dim3 grid((M + 3) / 4), block(256);
 #define ED_ALN(N) \
   hipLaunchKernelGGL(add_layernorm_kernel<N>, grid, block, 0, stream, x, delta, delta2, w, b, y, M, write_x)
+  switch (D / 256) {
+    case 1: ED_ALN(1); break;
+    case 2: ED_ALN(2); break;
+    case 3: ED_ALN(3); break;
+    case 4: ED_ALN(4); break;
+    case 5: ED_ALN(5); break;
+    case 6: ED_ALN(6); break;
+    case 7: ED_ALN(7); break;
+    default: ED_ALN(8); break;
+  }
+#undef ED_ALN
+  return hipGetLastError();
+}
+
+hipError_t launch_add_layernorm_rows_bf16(const float* x, const bf16_t* delta, const int32_t* rows, const bf16_t* delta2, float* x_out,
+                                          const float* w, const float* b, bf16_t* y, int M, int D, hipStream_t stream) {
+  if (M <= 0) return hipSuccess;
+  if (D <= 0 || D % 256 != 0 || D > 2048 || !rows || !x_out) return hipErrorInvalidValue;
+  dim3 grid((M + 3) / 4), block(256);
+#define ED_ALN(N) \
+  hipLaunchKernelGGL(add_layernorm_rows_kernel<N>, grid, block, 0, stream, x, delta, rows, delta2, x_out, w, b, y, M)
   switch (D / 256) {
     case 1: ED_ALN(1); break;
     case 2: ED_ALN(2); break;

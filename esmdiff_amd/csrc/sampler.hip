@@ -37,7 +37,10 @@ constexpr int MAX_PER_THREAD = 20;  // supports V <= 5120
 // sample_flags may be NULL; sample_gap[b] (optional, initialised to +inf by the caller) receives the smallest winner-to-
 // runner-up gap of the sample's masked rows in log units (log ratio for an update, log-probability difference for a final
 // pass) — a statistic for choosing eps, not part of the draw.
-template <int PER, bool MARGIN = false, bool ROWS = false>
+//
+// MAPPED (esmdiff_ddpm_sample after a forward that ran its head on the masked rows only, engine_forward.hip): the logits of
+// row r are row row_map[r] of `logits`.  A separate instantiation: the plain kernel carries no map.
+template <int PER, bool MARGIN = false, bool ROWS = false, bool MAPPED = false>
 __global__ __launch_bounds__(NT) void ddpm_step_kernel(int64_t* __restrict__ x, const float* __restrict__ logits,
                                                        int ld, int V, float mc_t, float mc_s, int final_,
                                                        const float* __restrict__ u, int use_philox,
@@ -45,7 +48,8 @@ __global__ __launch_bounds__(NT) void ddpm_step_kernel(int64_t* __restrict__ x, 
                                                        int logits_period, float margin = 0.f,
                                                        int32_t* __restrict__ sample_flags = nullptr,
                                                        const esmdiff_sample_step* __restrict__ sp = nullptr,
-                                                       float margin_fin = 0.f, float* __restrict__ sample_gap = nullptr) {
+                                                       float margin_fin = 0.f, float* __restrict__ sample_gap = nullptr,
+                                                       const int32_t* __restrict__ row_map = nullptr) {
   const int row = blockIdx.x;
   if (x[row] != MASK_ID) return;  // carry-over: copy_flag * x  (model.py:606-607)
   uint64_t sample_index = 0;
@@ -67,7 +71,7 @@ __global__ __launch_bounds__(NT) void ddpm_step_kernel(int64_t* __restrict__ x, 
   // logits_period > 0: sample b reads the logits of sample b % logits_period (step-0 sharing: every sample of the batch
   // had identical inputs, engine_sample.hip::esmdiff_ddpm_sample); the noise stays keyed by the sample's own index
   const int lrow = logits_period > 0 ? ((row / L) % logits_period) * L + (row % L) : row;
-  const float* z = logits + (int64_t)lrow * ld;
+  const float* z = logits + (int64_t)(MAPPED ? row_map[lrow] : lrow) * ld;
 
   float zz[PER];
   float m = -3.402823466e38f;
@@ -184,17 +188,22 @@ __global__ __launch_bounds__(NT) void ddpm_step_kernel(int64_t* __restrict__ x, 
 
 hipError_t launch_ddpm_step(int64_t* x, const float* logits, int ld, int V, float mc_t, float mc_s, int final_,
                             const float* u, int use_philox, uint64_t seed, uint64_t sample_offset, int step,
-                            int B, int L, hipStream_t stream, int logits_period, float margin, int32_t* sample_flags) {
+                            int B, int L, hipStream_t stream, int logits_period, float margin, int32_t* sample_flags,
+                            const int32_t* row_map) {
   const int rows = B * L;
   if (rows <= 0) return hipSuccess;
   const int per = (V + NT - 1) / NT;
-  if (per > MAX_PER_THREAD) return hipErrorInvalidValue;
+  if (per > MAX_PER_THREAD || (row_map && sample_flags)) return hipErrorInvalidValue;
   dim3 grid(rows), block(NT);
 #define ED_LAUNCH(P)                                                                                                       \
   do {                                                                                                                     \
     if (sample_flags)                                                                                                      \
       hipLaunchKernelGGL((ddpm_step_kernel<P, true>), grid, block, 0, stream, x, logits, ld, V, mc_t, mc_s, final_, u,     \
                          use_philox, seed, sample_offset, step, L, logits_period, margin, sample_flags);                   \
+    else if (row_map)                                                                                                      \
+      hipLaunchKernelGGL((ddpm_step_kernel<P, false, false, true>), grid, block, 0, stream, x, logits, ld, V, mc_t, mc_s,  \
+                         final_, u, use_philox, seed, sample_offset, step, L, logits_period, 0.f, nullptr, nullptr, 0.f,   \
+                         nullptr, row_map);                                                                                \
     else                                                                                                                   \
       hipLaunchKernelGGL((ddpm_step_kernel<P, false>), grid, block, 0, stream, x, logits, ld, V, mc_t, mc_s, final_, u,    \
                          use_philox, seed, sample_offset, step, L, logits_period, 0.f, nullptr);                           \
@@ -365,6 +374,99 @@ hipError_t launch_move_token_rows(const int64_t* src, int64_t* dst, const int32_
   if (n <= 0) return hipSuccess;
   const int64_t tot = (int64_t)n * L;
   hipLaunchKernelGGL(move_token_rows_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, src, dst, idx, n, L, gather);
+  return hipGetLastError();
+}
+
+// ---- the rows the ddpm sampler will read (engine_forward.hip: the last block's branches and the head run on these only) ----
+// One workgroup per sub-batch (part pi = samples [B pi / np, B (pi + 1) / np), as cut_batch cuts them), two passes over its rows:
+// the count, then a workgroup-level prefix sum in row order, so list is ascending whatever the scheduling.
+//   list[t0 + i]  = the i-th row of the part with x == MASK, relative to the part's first row t0
+//   map[t0 + r]   = the batch-level logits row that holds row r's logits: t0 + i when the part will run compacted
+//                   (needed_rows_compact(count, rows), the rule the host applies to the same count), else t0 + r; masked rows only
+//   count_host[pi] = the count (pinned host memory; valid once an event recorded behind this kernel has completed)
+constexpr int RL_NT = 1024;
+__global__ __launch_bounds__(RL_NT) void mask_row_list_kernel(const int64_t* __restrict__ x, int B, int L, int np,
+                                                              int32_t* __restrict__ list, int32_t* __restrict__ map,
+                                                              int32_t* __restrict__ count_host) {
+  __shared__ int s_wave[RL_NT / 64];
+  __shared__ int s_total;
+  const int pi = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t0 = (int)((int64_t)B * pi / np) * L, rows = (int)((int64_t)B * (pi + 1) / np) * L - t0;
+  const int64_t* xp = x + t0;
+  int n = 0;
+  for (int r = t; r < rows; r += RL_NT) n += xp[r] == MASK_ID;
+  n = wave_sum(n);
+  if (lane == 0) s_wave[wave] = n;
+  __syncthreads();
+  if (t == 0) {
+    int tot = 0;
+    for (int w = 0; w < RL_NT / 64; ++w) tot += s_wave[w];
+    s_total = tot;
+    count_host[pi] = tot;
+  }
+  __syncthreads();
+  const bool compact = needed_rows_compact(s_total, rows);
+  int base = 0;   // masked rows before this tile
+  for (int r0 = 0; r0 < rows; r0 += RL_NT) {
+    const int r = r0 + t;
+    const bool on = r < rows && xp[r] == MASK_ID;
+    const unsigned long long bal = __ballot(on);
+    __syncthreads();   // s_wave reuse
+    if (lane == 0) s_wave[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, tile = 0;
+    for (int w = 0; w < RL_NT / 64; ++w) {
+      before += w < wave ? s_wave[w] : 0;
+      tile += s_wave[w];
+    }
+    if (on) {
+      const int i = base + before + __popcll(bal & ((1ull << lane) - 1ull));
+      list[t0 + i] = r;
+      map[t0 + r] = t0 + (compact ? i : r);
+    }
+    base += tile;
+  }
+}
+
+hipError_t launch_mask_row_list(const int64_t* x, int B, int L, int np, int32_t* list, int32_t* map, int32_t* count_host,
+                                hipStream_t stream) {
+  if (B <= 0 || L <= 0 || np <= 0 || np > B) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mask_row_list_kernel, dim3(np), dim3(RL_NT), 0, stream, x, B, L, np, list, map, count_host);
+  return hipGetLastError();
+}
+
+// dst[i, :] = src[list[i], :], rows of D 16-bit values (D % 8 == 0): one wave per row, 16 bytes per lane and trip
+__global__ __launch_bounds__(256) void gather_rows16_kernel(const uint16_t* __restrict__ src, const int32_t* __restrict__ list,
+                                                            uint16_t* __restrict__ dst, int n, int D) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= n) return;
+  const uint4* s = reinterpret_cast<const uint4*>(src + (int64_t)list[i] * D);
+  uint4* d = reinterpret_cast<uint4*>(dst + (int64_t)i * D);
+  for (int c = lane; c < D / 8; c += 64) d[c] = s[c];
+}
+
+hipError_t launch_gather_rows16(const uint16_t* src, const int32_t* list, uint16_t* dst, int n, int D, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  if (D <= 0 || D % 8 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gather_rows16_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, src, list, dst, n, D);
+  return hipGetLastError();
+}
+
+// out[row, 0..V) = logits[map ? map[row] : row, 0..V) on the rows with x == MASK; other rows of out are left as they are
+__global__ __launch_bounds__(NT) void copy_masked_logits_kernel(const int64_t* __restrict__ x, const float* __restrict__ logits,
+                                                                int ld, const int32_t* __restrict__ map, float* __restrict__ out,
+                                                                int ld_out, int V) {
+  const int row = blockIdx.x;
+  if (x[row] != MASK_ID) return;
+  const float* z = logits + (int64_t)(map ? map[row] : row) * ld;
+  float* o = out + (int64_t)row * ld_out;
+  for (int v = threadIdx.x; v < V; v += NT) o[v] = z[v];
+}
+
+hipError_t launch_copy_masked_logits(const int64_t* x, const float* logits, int ld, const int32_t* map, float* out, int ld_out,
+                                     int V, int rows, hipStream_t stream) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(copy_masked_logits_kernel, dim3(rows), dim3(NT), 0, stream, x, logits, ld, map, out, ld_out, V);
   return hipGetLastError();
 }
 

@@ -656,6 +656,28 @@ class Engine:
         hold a MASK run forward T + 1 (none, almost always); ids are bit-identical to the full run.  Off by default."""
         self._chk(self._lib.esmdiff_set_final_skip(self._h, int(bool(on))))
 
+    def set_needed_rows(self, on: bool) -> None:
+        """Needed rows (esmdiff_set_option(ESMDIFF_OPT_NEEDED_ROWS)): ddpm_sample's forwards run the last block's branches and
+        the head only on the rows that hold MASK, the rows its sampler reads; ids are bit-identical to the full run.  On by default."""
+        self._chk(self._lib.esmdiff_set_option(self._h, N.OPT_NEEDED_ROWS, int(bool(on))))
+
+    def forward_logits_needed(self, x: torch.Tensor, sequence_tokens: torch.Tensor, t_freq: Optional[torch.Tensor],
+                              out: torch.Tensor) -> torch.Tensor:
+        """One forward as ddpm_sample runs it (esmdiff_forward_logits_needed): writes the rows of `out` (B, L, ld) float32 whose
+        token in x is MASK and leaves the others as they are."""
+        B, L = x.shape
+        x, seq = self._tok(x, B, L), self._tok(sequence_tokens, B, L)
+        tf = None if t_freq is None else t_freq.to(device=self.device, dtype=torch.float32).contiguous()
+        self._chk(self._lib.esmdiff_forward_logits_needed(self._h, _ptr(seq), _ptr(x), _ptr(tf), _ptr(out), out.shape[-1], B, L, _stream()))
+        return out
+
+    def tail_rows(self, reset: bool = False) -> int:
+        """Token rows that ran the last block's branches and the head since create / the last reset (esmdiff_get_tail_rows):
+        counters()["token_rows"] minus the rows a needed-rows forward skipped."""
+        r = ctypes.c_int64(0)
+        self._chk(self._lib.esmdiff_get_tail_rows(self._h, ctypes.byref(r), int(reset)))
+        return int(r.value)
+
     def counters(self, reset: bool = False) -> Dict[str, int]:
         """Network forwards issued and token rows pushed through them since create / the last reset (executed work)."""
         f, r = ctypes.c_int64(0), ctypes.c_int64(0)

@@ -150,8 +150,10 @@ int esmdiff_describe_plan(const esmdiff_engine* eng, int32_t B, int32_t L, char*
  * K order depends on (N, K) only.  tests/test_gpu_kernels.py::test_stream_counts_bit_identical (inside one path),
  * tests/test_gpu_fullwidth.py::test_stream_options_never_change_a_bit (settings that would cross the threshold).
  *   ESMDIFF_OPT_STREAMS           sub-batch launch queues of the 16-bit forward: 1 .. 4 (default 2)
- *   ESMDIFF_OPT_DUAL_MIN_TOKENS   batches of at least this many tokens are cut into sub-batches (default 2200) */
-typedef enum { ESMDIFF_OPT_STREAMS = 1, ESMDIFF_OPT_DUAL_MIN_TOKENS = 2 } esmdiff_option;
+ *   ESMDIFF_OPT_DUAL_MIN_TOKENS   batches of at least this many tokens are cut into sub-batches (default 2200)
+ *   ESMDIFF_OPT_NEEDED_ROWS       0 / 1 (default 1): esmdiff_ddpm_sample runs the last block's branches and the head only on the rows
+ *                                 that hold MASK — the rows whose logits its sampler reads; see esmdiff_ddpm_sample */
+typedef enum { ESMDIFF_OPT_STREAMS = 1, ESMDIFF_OPT_DUAL_MIN_TOKENS = 2, ESMDIFF_OPT_NEEDED_ROWS = 3 } esmdiff_option;
 int esmdiff_set_option(esmdiff_engine* eng, int32_t option, int64_t value);
 
 /* Replaces load_state_dict_from_lightning_ckpt (checkpoint_utils.py:41-74) + hydra instantiate
@@ -300,7 +302,20 @@ int esmdiff_nelbo_eval(esmdiff_engine* eng, const int64_t* seq, const int64_t* x
 /* Replaces MaskedDiffusionLanguageModeling.ddpm_sample (model.py:543-581) for one batch, entirely on
  * the device, Philox noise: T updates + the noise-removal pass.  x_inout holds the prior on entry
  * (all MASK, model.py:555, or input_prior, :561) and the sample on return.
- * mc_t, mc_s: [T] move chances per step [host]; t_freq: [(T+1), freq_dim] [host] (row T = noise removal). */
+ * mc_t, mc_s: [T] move chances per step [host]; t_freq: [(T+1), freq_dim] [host] (row T = noise removal).
+ *
+ * Needed rows (ESMDIFF_OPT_NEEDED_ROWS, on by default; exact).  The update reads logits only on rows that hold MASK: any other row
+ * keeps its token whatever the network says (model.py:530-532, 606-607).  Everything after the last block's attention is row-wise
+ * and feeds only those logits, so on the regular path of a bf16 / f16 engine (no float32-grade head, no extra output head, at
+ * least two blocks) each forward of this entry runs the last block's out-projection and FFN, the final LayerNorm and the head on
+ * the MASK rows of each sub-batch alone, gathered into compact buffers, when they are at most 7/8 of its rows.  A GEMM row does
+ * not depend on how many rows are beside it, so the ids are bit-identical to the full run.  ONE HOST WAIT PER FORWARD: the row
+ * count of each sub-batch is written to pinned host memory by a kernel at the start of the forward, and the host waits for
+ * that kernel (an event, not the stream) after it has enqueued every block up to the last attention, then enqueues the rest
+ * at the exact sizes — by then the device has the whole body of the forward queued behind the kernel waited for.  This is the
+ * only entry whose forwards wait on the device; during stream capture, and for every other entry, the forward is the full
+ * one and nothing waits.  Afterwards the hidden state and logits of the other rows are stale: esmdiff_get_embeddings and
+ * esmdiff_get_sequence_logits refuse until the next full forward. */
 int esmdiff_ddpm_sample(esmdiff_engine* eng, const int64_t* seq, int64_t* x_inout, int32_t B, int32_t L,
                         int32_t T, const float* mc_t, const float* mc_s, const float* t_freq,
                         const esmdiff_rng* rng, void* stream);

@@ -161,6 +161,19 @@ int esmdiff_encoder_neighbourhood(const int32_t* edges, const float* table, cons
 int esmdiff_encoder_nearest_code(const float* z, const float* code, const uint8_t* has, int32_t R, int32_t n_codes, int32_t d_out,
                                  int64_t* tok, void* stream);
 
+/* ---- Needed rows (ESMDIFF_OPT_NEEDED_ROWS, esmdiff_ddpm_sample in esmdiff_hip.h), one forward at a time ----
+ *   esmdiff_forward_logits_needed  esmdiff_forward_logits as a forward of esmdiff_ddpm_sample runs it: the rows to keep are
+ *                                  derived from x (those that hold MASK), and logits_out is written on those rows only — every
+ *                                  other row of logits_out is left as it was.  Bit-identical to esmdiff_forward_logits on the rows
+ *                                  written.  Engines and batches the option does not reach run the full forward and still
+ *                                  write the MASK rows only.  One host wait, like a forward of esmdiff_ddpm_sample.
+ *   esmdiff_get_tail_rows          *rows_out = the token rows that ran the last block's branches and the head, summed over the
+ *                                  forwards since create / the last reset: equal to esmdiff_get_counters' token_rows when nothing
+ *                                  was skipped. */
+int esmdiff_forward_logits_needed(esmdiff_engine* eng, const int64_t* seq, const int64_t* x, const float* t_freq,
+                                  float* logits_out, int32_t ld_logits, int32_t B, int32_t L, void* stream);
+int esmdiff_get_tail_rows(esmdiff_engine* eng, int64_t* rows_out, int32_t reset);
+
 /* Accumulated per-section device time of the esmdiff_forward_logits/ddpm_sample calls since profiling was
  * enabled: esmdiff_set_profiling(eng, 1) brackets every launch with HIP events on the launch stream (no sync);
  * mode 2 brackets only the dominant kernel (FFN-up GEMM, section 6), cheap enough for a timed region; 0 = off. sections: 0 embed, 1 layernorm, 2 gemm_qkv,
