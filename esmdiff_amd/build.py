@@ -22,6 +22,7 @@ INCLUDE = PKG.parent / "include"
 
 UNITS = {
     "engine": [],
+    "engine_weights": [],
     "engine_forward": [],
     "engine_sample": [],
     "engine_decode": [],

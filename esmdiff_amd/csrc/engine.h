@@ -1,10 +1,12 @@
 // engine.h — private to the engine units of libesmdiff_hip.so (never installed): the engine's data model, the section timer and
 // the few helpers that cross units.
-//   engine.hip          lifetime and state: weight loader, create / destroy, the setters and getters
+//   engine.hip          lifetime and state: create / destroy, the setters and getters, the error channel
+//   engine_weights.hip  the weight loader of every create: Table, need, load_f32, load_linear (encoder.hip loads through it too)
 //   engine_forward.hip  one forward: batch planner, sub-batch view, the float32-grade and the 16-bit launch sequences
 //   engine_sample.hip   what runs forwards in a loop or consumes logits: ddpm / gibbs steps and samplers, q_xt, the NELBO
 //   engine_decode.hip   the structure decoder's backbone and confidence heads
 //   engine_test.hip     kernel-level entries of include/esmdiff_hip_test.h
+//   encoder.hip         (a kernel unit) includes this header for its host side: esmdiff_encoder is an Owner with Linear slots
 // Everything here that is not a C entry lives in namespace eng; a unit's own helpers stay static / anonymous in that unit.
 #pragma once
 #include <math.h>
@@ -34,9 +36,17 @@ enum Section { S_EMBED = 0, S_LN, S_QKV, S_QKROPE, S_ATTN, S_OUT, S_FFN_UP, S_FF
 // engine_decode.hip (pairwise_confidence): bytes of pair rows one chunk of whole samples may occupy
 constexpr int64_t kDefaultPairChunkBytes = 1536ll << 20;
 
-// One linear's weight, held in the one form its engine runs it in.  create_engine chooses the form per group of weights
-// (body_form / head_form / plain_form), load_linear fills the slot, and the forwards dispatch on `form`.  An accessor of
-// another form than the slot's gives null.
+// What the error channel, dalloc and the weight loader need of their owner: esmdiff_engine and esmdiff_encoder (encoder.hip)
+// both start with it.  allocs: what destroy frees.
+struct Owner {
+  int device = 0;
+  std::string err;
+  std::vector<void*> allocs;
+};
+
+// One linear's weight, held in the one form its owner runs it in.  create_engine chooses the form per group of weights
+// (body_form / head_form / plain_form), the encoder one form for all; load_linear fills the slot, and the launch sequences
+// dispatch on `form`.  An accessor of another form than the slot's gives null.
 struct Linear {
   // W16: the engine's 16-bit type (bf16, or f16 on an f16 engine), the FFN-up's rows interleaved gate / up.  F32 (csrc/strict.hip):
   // float32 in the checkpoint's own row order, no padding, no interleave.  SPLIT (csrc/gemm_split.hip): scaled f16 plane
@@ -59,12 +69,9 @@ struct Layer {
 
 }  // namespace eng
 
-struct esmdiff_engine {
+struct esmdiff_engine : eng::Owner {
   esmdiff_config cfg{};
   int kind = 0;  // 0: ESM3 structure-token transformer (the sampler's network); 1: VQ-VAE structure-token decoder
-  int device = 0;
-  std::string err;
-  std::vector<void*> allocs;
   // weights
   std::vector<eng::Layer> layers;
   float *e_seq = nullptr, *e_struct = nullptr, *cvec = nullptr;
@@ -177,8 +184,10 @@ struct esmdiff_engine {
 namespace eng {
 
 // ---- helpers that cross units -------------------------------------------------------------------------------------------
-// engine.hip: the message goes to the engine, or with e == null to the calling thread's create error; returns `code`
-int fail(esmdiff_engine* e, int code, const char* fmt, ...);
+// engine.hip: the message goes to the owner, or with o == null to the calling thread's handle-less string (a failed create, a
+// kernel-level test entry); returns `code`.  last_error reads it back: esmdiff_last_error and esmdiff_encoder_last_error.
+int fail(Owner* o, int code, const char* fmt, ...);
+const char* last_error(const Owner* o);
 int round_up(int v, int m);
 void softplus_host(float* v, int n);
 int check_bl(esmdiff_engine* e, int B, int L);
@@ -195,6 +204,38 @@ int shared_forward_batch(const esmdiff_engine* e, int B, int L);
     hipError_t _s = (call);                                                                           \
     if (_s != hipSuccess) return eng::fail(e, ESMDIFF_E_HIP, "%s: %s", #call, hipGetErrorString(_s)); \
   } while (0)
+
+// ---- engine_weights.hip: the one weight loader (dalloc, a template, is defined here) ------------------------------------------
+template <typename T>
+int dalloc(Owner* o, T** p, size_t n_elems, bool zero = false) {
+  void* v = nullptr;
+  hipError_t s = hipMalloc(&v, n_elems * sizeof(T) + 256);
+  if (s != hipSuccess) return fail(o, ESMDIFF_E_HIP, "hipMalloc(%zu): %s", n_elems * sizeof(T), hipGetErrorString(s));
+  if (zero) hipMemset(v, 0, n_elems * sizeof(T) + 256);
+  o->allocs.push_back(v);
+  *p = reinterpret_cast<T*>(v);
+  return 0;
+}
+
+// The caller's weight table by name; of two entries with one name the last wins.  A name that is not found as it stands is
+// looked up once more behind `prefix` (the engine's "net."); without a prefix the lookup is exact.
+struct Table {
+  std::map<std::string, const esmdiff_weight*> m;
+  std::string prefix;
+  Table(const esmdiff_weight* table, int n, const char* prefix = "");
+  const esmdiff_weight* find(const std::string& name) const;
+};
+int64_t numel(const esmdiff_weight* w);
+// the named tensor, checked: present, of this shape, f32 or bf16, with data
+int need(Owner* o, const Table& t, const std::string& name, std::initializer_list<int64_t> shape, const esmdiff_weight** out);
+// vectors and embeddings: float32, the tail up to pad_to elements zero
+int load_f32(Owner* o, const Table& t, const std::string& name, std::initializer_list<int64_t> shape, float** dst, int64_t pad_to = 0);
+// A linear's weight [rows, K] into its slot in the given form.  W16 and SPLIT zero-pad the rows to pad_rows and, with
+// swiglu_h = FH, interleave the FFN-up's gate / up rows for the SwiGLU epilogue; F32 does neither (launch_gemm_f32 bounds
+// its rows and the SwiGLU is its own pass).  SPLIT: planes [rows_p, 3 K] + the inverse scale.  f16: the owner's 16-bit
+// operand type (W16 only); scratch_bits: the device word the SPLIT form's scale reduction needs.
+int load_linear(Owner* o, const Table& t, const std::string& name, std::initializer_list<int64_t> shape, Linear::Form form,
+                Linear* dst, int64_t pad_rows = 0, int swiglu_h = 0, bool f16 = false, uint32_t* scratch_bits = nullptr);
 
 // RAII-less section timer: when profiling, records an event before/after each launch.
 struct Prof {

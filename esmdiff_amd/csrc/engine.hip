@@ -1,5 +1,6 @@
-// engine.hip — lifetime and state of an engine of libesmdiff_hip.so (C ABI: include/esmdiff_hip.h): the weight loader, create
-// and destroy, the setters and getters of engine state, and the helpers every engine unit uses (engine.h says what lives where).
+// engine.hip — lifetime and state of an engine of libesmdiff_hip.so (C ABI: include/esmdiff_hip.h): create and destroy, the
+// setters and getters of engine state, and the helpers every engine unit uses, the error channel among them (engine.h says what
+// lives where; the weights come in through engine_weights.hip).
 // The engine never synchronises except in create, in the setters that say so and in the profiling readback.
 #include "engine.h"
 
@@ -8,21 +9,23 @@ using namespace eng;
 
 namespace {
 
-thread_local std::string g_create_error;
+thread_local std::string g_error;   // the handle-less error string: a failed create of any kind, a kernel-level test entry
 
 }  // namespace
 
 namespace eng {
 
-int fail(esmdiff_engine* e, int code, const char* fmt, ...) {
+int fail(Owner* o, int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(buf, sizeof buf, fmt, ap);
   va_end(ap);
-  if (e) e->err = buf; else g_create_error = buf;
+  if (o) o->err = buf; else g_error = buf;
   return code;
 }
+
+const char* last_error(const Owner* o) { return o ? o->err.c_str() : g_error.c_str(); }
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -57,93 +60,10 @@ int check_not_decoder(esmdiff_engine* e) {
 
 namespace {
 
-template <typename T>
-int dalloc(esmdiff_engine* e, T** p, size_t n_elems, bool zero = false) {
-  void* v = nullptr;
-  hipError_t s = hipMalloc(&v, n_elems * sizeof(T) + 256);
-  if (s != hipSuccess) return fail(e, ESMDIFF_E_HIP, "hipMalloc(%zu): %s", n_elems * sizeof(T), hipGetErrorString(s));
-  if (zero) hipMemset(v, 0, n_elems * sizeof(T) + 256);
-  e->allocs.push_back(v);
-  *p = reinterpret_cast<T*>(v);
-  return 0;
-}
-
-struct Table {
-  std::map<std::string, const esmdiff_weight*> m;
-  const esmdiff_weight* find(const std::string& name) const {
-    auto it = m.find(name);
-    if (it != m.end()) return it->second;
-    it = m.find("net." + name);
-    return it == m.end() ? nullptr : it->second;
-  }
-};
-
-int64_t numel(const esmdiff_weight* w) {
-  int64_t n = 1;
-  for (int i = 0; i < w->ndim; ++i) n *= w->shape[i];
-  return n;
-}
-
-int need(esmdiff_engine* e, const Table& t, const std::string& name, std::initializer_list<int64_t> shape,
-         const esmdiff_weight** out) {
-  const esmdiff_weight* w = t.find(name);
-  if (!w) return fail(e, ESMDIFF_E_MISSING, "missing weight '%s' (state dict is loaded strictly, checkpoint_utils.py:64)", name.c_str());
-  if (w->ndim != (int)shape.size()) return fail(e, ESMDIFF_E_SHAPE, "weight '%s': ndim %d, expected %zu", name.c_str(), w->ndim, shape.size());
-  int i = 0;
-  for (int64_t s : shape) {
-    if (w->shape[i] != s) return fail(e, ESMDIFF_E_SHAPE, "weight '%s': dim %d is %lld, expected %lld", name.c_str(), i, (long long)w->shape[i], (long long)s);
-    ++i;
-  }
-  if (w->dtype != ESMDIFF_F32 && w->dtype != ESMDIFF_BF16) return fail(e, ESMDIFF_E_SHAPE, "weight '%s': unsupported dtype %d", name.c_str(), w->dtype);
-  if (!w->data) return fail(e, ESMDIFF_E_INVALID, "weight '%s': null data", name.c_str());
-  *out = w;
-  return 0;
-}
-
-// vectors and embeddings: float32, the tail up to pad_to elements zero
-int load_f32(esmdiff_engine* e, const Table& t, const std::string& name, std::initializer_list<int64_t> shape, float** dst,
-             int64_t pad_to = 0) {
-  const esmdiff_weight* w;
-  if (int r = need(e, t, name, shape, &w)) return r;
-  const int64_t n = numel(w), n_p = pad_to > n ? pad_to : n;
-  if (int r = dalloc(e, dst, (size_t)n_p, n_p != n)) return r;
-  HIP_TRY(e, launch_to_f32(w->data, w->dtype, *dst, n, 0));
-  return 0;
-}
-
-// A linear's weight [rows, K] into its slot in the given form.  W16 and SPLIT zero-pad the rows to pad_rows and, with
-// swiglu_h = FH, interleave the FFN-up's gate / up rows for the SwiGLU epilogue; F32 does neither (launch_gemm_f32 bounds
-// its rows and the SwiGLU is its own pass).  SPLIT: planes [rows_p, 3 K] + the inverse scale.
-int load_linear(esmdiff_engine* e, const Table& t, const std::string& name, std::initializer_list<int64_t> shape, Linear::Form form,
-                Linear* dst, int64_t pad_rows = 0, int swiglu_h = 0) {
-  const esmdiff_weight* w;
-  if (int r = need(e, t, name, shape, &w)) return r;
-  const int64_t n = numel(w), rows = w->shape[0], K = n / rows;
-  const int64_t rows_p = form != Linear::F32 && pad_rows > rows ? pad_rows : rows;
-  if (form == Linear::SPLIT) {
-    if (K % 128 || rows_p % 256) return fail(e, ESMDIFF_E_SHAPE, "weight '%s': [%lld, %lld] does not fit the split GEMM (rows %% 256, K %% 128)", name.c_str(), (long long)rows_p, (long long)K);
-    uint16_t* p;
-    if (int r = dalloc(e, &p, (size_t)(rows_p * 3 * K), rows_p != rows)) return r;
-    dst->w = p;
-    HIP_TRY(e, split_weight(w->data, w->dtype, p, rows, (int)K, e->scratch_bits, &dst->inv, swiglu_h));
-  } else if (form == Linear::F32) {
-    float* p;
-    if (int r = dalloc(e, &p, (size_t)n)) return r;
-    dst->w = p;
-    HIP_TRY(e, launch_to_f32(w->data, w->dtype, p, n, 0));
-  } else {
-    bf16_t* p;
-    if (int r = dalloc(e, &p, (size_t)(rows_p * K), rows_p != rows)) return r;
-    dst->w = p;
-    if (swiglu_h) {
-      if (ED_KN(e->f16, launch_interleave_swiglu(w->data, w->dtype, p, swiglu_h, (int)K, 0)) != hipSuccess)
-        return fail(e, ESMDIFF_E_HIP, "interleave_swiglu launch failed");
-    } else {
-      HIP_TRY(e, ED_KN(e->f16, launch_to_bf16(w->data, w->dtype, p, n, 0)));
-    }
-  }
-  dst->form = form;
-  return 0;
+// A linear of this engine: load_linear with the engine's 16-bit operand type and the split forms' scratch word.
+int engine_linear(esmdiff_engine* e, const Table& t, const std::string& name, std::initializer_list<int64_t> shape, Linear::Form form,
+                  Linear* dst, int64_t pad_rows = 0, int swiglu_h = 0) {
+  return load_linear(e, t, name, shape, form, dst, pad_rows, swiglu_h, e->f16, e->scratch_bits);
 }
 
 // The form of a group of weights, chosen once at create.  plain_form, the engine's non-split form: the pairwise head always, and
@@ -312,7 +232,7 @@ int esmdiff_get_tail_rows(esmdiff_engine* e, int64_t* rows_out, int32_t reset) {
 
 int esmdiff_abi_version(void) { return ESMDIFF_ABI_VERSION; }
 
-const char* esmdiff_last_error(const esmdiff_engine* eng) { return eng ? eng->err.c_str() : g_create_error.c_str(); }
+const char* esmdiff_last_error(const esmdiff_engine* eng) { return last_error(eng); }
 
 void esmdiff_engine_destroy(esmdiff_engine* e) {
   if (!e) return;
@@ -367,15 +287,13 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
   if (split && (D % 128 || FH % 128))
     return (delete e, fail(nullptr, ESMDIFF_E_INVALID, "precision F32_SPLIT needs d_model and ffn_hidden to be multiples of 128"));
   auto bail = [&](int code) {
-    g_create_error = e->err;
+    g_error = e->err;
     esmdiff_engine_destroy(e);
     return code;
   };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(e, ESMDIFF_E_HIP, "hipSetDevice failed"));
 
-  Table t;
-  for (int i = 0; i < n; ++i)
-    if (table[i].name) t.m[table[i].name] = &table[i];
+  const Table t(table, n, "net.");   // a Lightning checkpoint's names carry the wrapper's prefix
 
 #define TRY(x)                  \
   do {                          \
@@ -395,7 +313,7 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     const std::string b = stack + "blocks." + std::to_string(i) + ".";
     TRY(load_f32(e, t, b + "attn.layernorm_qkv.0.weight", {D}, &ly.ln1_w));
     TRY(load_f32(e, t, b + "attn.layernorm_qkv.0.bias", {D}, &ly.ln1_b));
-    TRY(load_linear(e, t, b + "attn.layernorm_qkv.1.weight", {3 * D, D}, bf, &ly.w_qkv));
+    TRY(engine_linear(e, t, b + "attn.layernorm_qkv.1.weight", {3 * D, D}, bf, &ly.w_qkv));
     TRY(load_f32(e, t, b + "attn.q_ln.weight", {D}, &ly.q_ln_w));
     TRY(load_f32(e, t, b + "attn.k_ln.weight", {D}, &ly.k_ln_w));
     if (split) {   // |q|, |k| <= sqrt(2 (D - 1)) max|ln weight| (LayerNorm + rotation); |v| <= (sqrt(D) max|g| + |b|_2) max_row |W_v row|_2
@@ -419,21 +337,21 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
       ly.att_qk = pow2_below(30000.f / (sqrtf(2.f * D) * wmax));
       ly.att_v = pow2_below(30000.f / ((sqrtf((float)D) * gmax + sqrtf(b2)) * rn));
     }
-    TRY(load_linear(e, t, b + "attn.out_proj.weight", {D, D}, bf, &ly.w_out));
+    TRY(engine_linear(e, t, b + "attn.out_proj.weight", {D, D}, bf, &ly.w_out));
     TRY(load_f32(e, t, b + "ffn.0.weight", {D}, &ly.ln2_w));
     TRY(load_f32(e, t, b + "ffn.0.bias", {D}, &ly.ln2_b));
     // FFN-up with the SwiGLU in the GEMM's epilogue: rows interleaved gate / up (W16, and SPLIT: mid leaves it as f32 and is split
     // with its row's own scale, strict_part); F32 keeps the checkpoint's order
-    TRY(load_linear(e, t, b + "ffn.1.weight", {2 * FH, D}, bf, &ly.w_up, 0, FH));
-    TRY(load_linear(e, t, b + "ffn.3.weight", {D, FH}, bf, &ly.w_down));
+    TRY(engine_linear(e, t, b + "ffn.1.weight", {2 * FH, D}, bf, &ly.w_up, 0, FH));
+    TRY(engine_linear(e, t, b + "ffn.3.weight", {D, FH}, bf, &ly.w_down));
   }
   TRY(load_f32(e, t, stack + "norm.weight", {D}, &e->final_ln_w));
-  TRY(load_linear(e, t, head0 + "weight", {D, D}, hf, &e->head_w0));
+  TRY(engine_linear(e, t, head0 + "weight", {D, D}, hf, &e->head_w0));
   TRY(load_f32(e, t, head0 + "bias", {D}, &e->head_b0));
   TRY(load_f32(e, t, head2 + "weight", {D}, &e->head_ln_w));
   TRY(load_f32(e, t, head2 + "bias", {D}, &e->head_ln_b));
   e->vocab_pad = round_up(V, 256);  // 4101 -> 4352: 17 column tiles of the 256x256 kernel (the 128x128 kernel took 0.40 ms at M = 25 800)
-  TRY(load_linear(e, t, head3 + "weight", {V, D}, hf, &e->head_w3, e->vocab_pad));
+  TRY(engine_linear(e, t, head3 + "weight", {V, D}, hf, &e->head_w3, e->vocab_pad));
   TRY(load_f32(e, t, head3 + "bias", {V}, &e->head_b3, e->vocab_pad));
   if (kind == 1) TRY(load_f32(e, t, "embed.weight", {ESMDIFF_VOCAB, D}, &e->e_struct));
   {
@@ -448,11 +366,11 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
       if (head_split) return bail(fail(e, ESMDIFF_E_INVALID, "a sequence head and head_precision = 1 together are not built: use precision f32 / f32_split or head_precision 0"));
       e->plddt_bins = nb;
       e->ld_plddt = split ? 256 : round_up(nb, 4);   // the split GEMM has no column bound: its output row holds all N_pad columns
-      TRY(load_linear(e, t, sh + "0.weight", {D, D}, bf, &e->pl_w0));
+      TRY(engine_linear(e, t, sh + "0.weight", {D, D}, bf, &e->pl_w0));
       TRY(load_f32(e, t, sh + "0.bias", {D}, &e->pl_b0));
       TRY(load_f32(e, t, sh + "2.weight", {D}, &e->pl_ln_w));
       TRY(load_f32(e, t, sh + "2.bias", {D}, &e->pl_ln_b));
-      TRY(load_linear(e, t, sh + "3.weight", {nb, D}, bf, &e->pl_w3, split ? 256 : 128));   // one column tile of its GEMM
+      TRY(engine_linear(e, t, sh + "3.weight", {nb, D}, bf, &e->pl_w3, split ? 256 : 128));   // one column tile of its GEMM
       TRY(load_f32(e, t, sh + "3.bias", {nb}, &e->pl_b3, 128));
       e->has_plddt = true;
     }
@@ -460,12 +378,12 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
   if (kind == 1) {
     if (t.find("pairwise_classification_head.linear2.weight")) {
       const std::string ph = "pairwise_classification_head.";
-      TRY(load_linear(e, t, ph + "downproject.weight", {128, D}, pf, &e->pw_down));
-      TRY(load_linear(e, t, ph + "linear1.weight", {128, 128}, pf, &e->pw_l1));
+      TRY(engine_linear(e, t, ph + "downproject.weight", {128, D}, pf, &e->pw_down));
+      TRY(engine_linear(e, t, ph + "linear1.weight", {128, 128}, pf, &e->pw_l1));
       TRY(load_f32(e, t, ph + "norm.weight", {128}, &e->pw_ln_w));
       TRY(load_f32(e, t, ph + "norm.bias", {128}, &e->pw_ln_b));
       // rows [distogram 64 | direction 96 | PAE 64]; padded so that the 128-row W16 GEMM tile starting at row 160 stays inside
-      TRY(load_linear(e, t, ph + "linear2.weight", {224, 128}, pf, &e->pw_l2, 384));
+      TRY(engine_linear(e, t, ph + "linear2.weight", {224, 128}, pf, &e->pw_l2, 384));
       TRY(dalloc(e, &e->zeros128, (size_t)128, true));
       e->has_pair = true;
     }
@@ -487,8 +405,8 @@ static int create_engine(const esmdiff_config* cfg, const esmdiff_weight* table,
     e->v_heads = VH;
     TRY(load_f32(e, t, ga + "s_norm.weight", {D}, &e->g_snorm_w));
     const Linear::Form gf = split && (15 * VH) % 256 == 0 && (3 * VH) % 128 == 0 ? Linear::SPLIT : pf;
-    TRY(load_linear(e, t, ga + "proj.weight", {15 * VH, D}, gf, &e->g_proj));
-    TRY(load_linear(e, t, ga + "out_proj.weight", {D, 3 * VH}, gf, &e->g_out));
+    TRY(engine_linear(e, t, ga + "proj.weight", {15 * VH, D}, gf, &e->g_proj));
+    TRY(engine_linear(e, t, ga + "out_proj.weight", {D, 3 * VH}, gf, &e->g_out));
     TRY(load_f32(e, t, ga + "rotation_scale_per_head", {VH}, &e->g_wrot));
     TRY(load_f32(e, t, ga + "distance_scale_per_head", {VH}, &e->g_wdist));
     if (hipDeviceSynchronize() != hipSuccess) return bail(fail(e, ESMDIFF_E_HIP, "geom weight conversion failed"));

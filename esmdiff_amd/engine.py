@@ -34,8 +34,41 @@ def _require_gpu():
                            "there is no CPU fallback")
 
 
-class Engine:
+def _weight_table(state_dict: Dict[str, torch.Tensor], device: torch.device):
+    """(keep, table): the caller's tensors (any float dtype) uploaded as device containers, and the esmdiff_weight array that
+    names them.  A create entry makes its own bf16 / re-laid-out copies, after which `keep` is released.  Call it with `device`
+    current."""
+    keep, table = [], (N.Weight * len(state_dict))()
+    for i, (name, t) in enumerate(state_dict.items()):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            t = t.float()
+        d = t.detach().to(device).contiguous()
+        keep.append(d)
+        shape = (ctypes.c_int64 * 4)(*(list(d.shape) + [0] * (4 - d.dim())))
+        table[i] = N.Weight(name.encode(), d.data_ptr(), N.DT_F32 if d.dtype == torch.float32 else N.DT_BF16, d.dim(), shape)
+    torch.cuda.synchronize()
+    return keep, table
+
+
+class _Handle:
+    """Lifetime of one native handle `_h` of `_lib`: `_destroy` names the entry that frees it."""
+    _destroy = ""
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = ctypes.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Engine(_Handle):
     """One engine per (process, device).  Not thread-safe.  All work is enqueued on torch's current stream."""
+    _destroy = "esmdiff_engine_destroy"
 
     def __init__(self, cfg: ModelConfig, state_dict: Dict[str, torch.Tensor], max_batch: int, max_len: int,
                  device: int = 0, precision: str = "bf16", head_precision: Optional[str] = None):
@@ -60,19 +93,8 @@ class Engine:
         c = N.Config(cfg.d_model, cfg.n_heads, cfg.n_layers, cfg.ffn_hidden, cfg.n_structure_heads, cfg.freq_dim,
                      max_batch, max_len, cfg.residue_scale, int(cfg.time_conditioning), N.PRECISION[precision],
                      1 if (head_precision == "f32" and precision in ("bf16", "f16")) else 0)
-        # upload the caller's tensors (any float dtype) as device containers; the engine makes its own
-        # bf16 / re-laid-out copies, after which these are released.
-        keep, table = [], (N.Weight * len(state_dict))()
         with torch.cuda.device(self.device):
-            for i, (name, t) in enumerate(state_dict.items()):
-                if t.dtype not in (torch.float32, torch.bfloat16):
-                    t = t.float()
-                d = t.detach().to(self.device).contiguous()
-                keep.append(d)
-                shape = (ctypes.c_int64 * 4)(*(list(d.shape) + [0] * (4 - d.dim())))
-                table[i] = N.Weight(name.encode(), d.data_ptr(), N.DT_F32 if d.dtype == torch.float32 else N.DT_BF16,
-                                    d.dim(), shape)
-            torch.cuda.synchronize()
+            keep, table = _weight_table(state_dict, self.device)
             code = self._lib.esmdiff_engine_create(ctypes.byref(c), table, len(state_dict), device,
                                                    ctypes.byref(self._h))
         if code != 0:
@@ -101,17 +123,6 @@ class Engine:
                                                             _ptr(None if b is None else b.float().contiguous()), _ptr(y),
                                                             M, Nn, K, ctypes.byref(S), _stream()))
         return y, int(S.value)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.esmdiff_engine_destroy(self._h)
-            self._h = ctypes.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------------------------------
     def _chk(self, code):
@@ -735,9 +746,10 @@ class Engine:
         return q, k
 
 
-class StructureDecoder:
+class StructureDecoder(_Handle):
     """Structure tokens -> backbone coordinates on the device (esmdiff_decoder_create / esmdiff_decoder_decode): what the
     reference gets from `esm3.decode(ESMProteinTensor(structure=...))`, /root/reference/slm/sample_esmdiff.py:40-61."""
+    _destroy = "esmdiff_engine_destroy"
 
     def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], max_batch: int, max_len: int, device: int = 0,
                  precision: str = "f32"):
@@ -754,17 +766,8 @@ class StructureDecoder:
         self._h = ctypes.c_void_p(0)
         c = N.Config(cfg.d_model, cfg.n_heads, cfg.n_layers, cfg.ffn_hidden, 23, 1, max_batch, max_len, 1.0, 0,
                      N.PRECISION[precision], 0)
-        keep, table = [], (N.Weight * len(state_dict))()
         with torch.cuda.device(self.device):
-            for i, (name, t) in enumerate(state_dict.items()):
-                if t.dtype not in (torch.float32, torch.bfloat16):
-                    t = t.float()
-                d = t.detach().to(self.device).contiguous()
-                keep.append(d)
-                shape = (ctypes.c_int64 * 4)(*(list(d.shape) + [0] * (4 - d.dim())))
-                table[i] = N.Weight(name.encode(), d.data_ptr(), N.DT_F32 if d.dtype == torch.float32 else N.DT_BF16,
-                                    d.dim(), shape)
-            torch.cuda.synchronize()
+            keep, table = _weight_table(state_dict, self.device)
             code = self._lib.esmdiff_decoder_create(ctypes.byref(c), table, len(state_dict), device, ctypes.byref(self._h))
         if code != 0:
             raise RuntimeError(f"esmdiff_decoder_create failed ({code}): {self._lib.esmdiff_last_error(None).decode()}")
@@ -772,17 +775,6 @@ class StructureDecoder:
         self.max_batch, self.max_len = max_batch, max_len
         self.has_plddt = any(k == "plddt_head.3.weight" for k in state_dict)
         self.has_ptm = any(k == "pairwise_classification_head.linear2.weight" for k in state_dict)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.esmdiff_engine_destroy(self._h)
-            self._h = ctypes.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_pair_chunk_bytes(self, nbytes: int) -> None:
         """esmdiff_decoder_set_pair_chunk_bytes: the pairwise head's pair-row budget per chunk of whole samples (768 B per
@@ -816,9 +808,10 @@ class StructureDecoder:
         return res[0] if len(res) == 1 else tuple(res)
 
 
-class StructureEncoder:
+class StructureEncoder(_Handle):
     """Backbone coordinates -> structure tokens on the device (esmdiff_encoder_create / esmdiff_encoder_encode): what the
     reference gets from `model.encode(ESMProtein(coordinates=...))`, /root/reference/slm/models/utils.py:136-137."""
+    _destroy = "esmdiff_encoder_destroy"
 
     def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], device: int = 0, precision: str = "f32"):
         """precision defaults to "f32" (csrc/strict.hip): the encoder runs once per input structure on B*L*16 neighbourhood
@@ -831,17 +824,8 @@ class StructureEncoder:
         self.device = torch.device("cuda", device)
         self._lib = N.lib()
         self._h = ctypes.c_void_p(0)
-        keep, table = [], (N.Weight * len(state_dict))()
         with torch.cuda.device(self.device):
-            for i, (name, t) in enumerate(state_dict.items()):
-                if t.dtype not in (torch.float32, torch.bfloat16):
-                    t = t.float()
-                d = t.detach().to(self.device).contiguous()
-                keep.append(d)
-                shape = (ctypes.c_int64 * 4)(*(list(d.shape) + [0] * (4 - d.dim())))
-                table[i] = N.Weight(name.encode(), d.data_ptr(), N.DT_F32 if d.dtype == torch.float32 else N.DT_BF16,
-                                    d.dim(), shape)
-            torch.cuda.synchronize()
+            keep, table = _weight_table(state_dict, self.device)
             code = self._lib.esmdiff_encoder_create(cfg.d_model, cfg.v_heads, cfg.n_layers, cfg.ffn_hidden, cfg.d_out,
                                                     cfg.n_codes, cfg.knn, cfg.relpos_bins, N.PRECISION[precision], table,
                                                     len(state_dict), device,
@@ -849,17 +833,6 @@ class StructureEncoder:
         if code != 0:
             raise RuntimeError(f"esmdiff_encoder_create failed ({code}): {self._lib.esmdiff_encoder_last_error(None).decode()}")
         del keep
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.esmdiff_encoder_destroy(self._h)
-            self._h = ctypes.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def encode(self, coordinates: torch.Tensor) -> torch.Tensor:
         """coordinates (B, L, >=3, 3) with N, CA, C first (NaN / Inf where unknown) -> structure tokens (B, L) int64 on the
@@ -877,43 +850,35 @@ class StructureEncoder:
         return tok
 
 
-def gemm_bf16(A: torch.Tensor, W: torch.Tensor, epilogue: int, *, out: Optional[torch.Tensor] = None,
-              bias: Optional[torch.Tensor] = None, alpha: float = 1.0, n_valid: Optional[int] = None) -> torch.Tensor:
-    """out = epilogue(A[M,K] @ W[N,K]^T) through esmdiff_gemm_bf16 (N % 128 == 0, K % 64 == 0)."""
+def _gemm16(dtype: torch.dtype, A, W, epilogue, out, bias, alpha, n_valid) -> torch.Tensor:
+    """gemm_bf16 / gemm_f16: one body, the entry and the type of A, W and the 16-bit outputs chosen by `dtype`."""
     _require_gpu()
     M, K = A.shape
     Nn = W.shape[0]
-    assert A.dtype == W.dtype == torch.bfloat16 and A.is_contiguous() and W.is_contiguous() and W.shape[1] == K
+    assert A.dtype == W.dtype == dtype and A.is_contiguous() and W.is_contiguous() and W.shape[1] == K
     if out is None:
         if epilogue in (N.EPI_BF16, N.EPI_BIAS_GELU_BF16):
-            out = torch.empty(M, Nn, dtype=torch.bfloat16, device=A.device)
+            out = torch.empty(M, Nn, dtype=dtype, device=A.device)
         elif epilogue == N.EPI_SWIGLU_BF16:
-            out = torch.empty(M, Nn // 2, dtype=torch.bfloat16, device=A.device)
+            out = torch.empty(M, Nn // 2, dtype=dtype, device=A.device)
         else:
             raise ValueError("f32 epilogues need an explicit `out`")
-    ldc = out.stride(0)
-    N.check(N.lib().esmdiff_gemm_bf16(_ptr(A), _ptr(W), _ptr(out), _ptr(bias), M, Nn, K, ldc,
-                                      Nn if n_valid is None else n_valid, float(alpha), epilogue, _stream()))
+    fn = N.lib().esmdiff_gemm_bf16 if dtype == torch.bfloat16 else N.lib().esmdiff_gemm_f16
+    N.check(fn(_ptr(A), _ptr(W), _ptr(out), _ptr(bias), M, Nn, K, out.stride(0), Nn if n_valid is None else n_valid,
+               float(alpha), epilogue, _stream()))
     return out
+
+
+def gemm_bf16(A: torch.Tensor, W: torch.Tensor, epilogue: int, *, out: Optional[torch.Tensor] = None,
+              bias: Optional[torch.Tensor] = None, alpha: float = 1.0, n_valid: Optional[int] = None) -> torch.Tensor:
+    """out = epilogue(A[M,K] @ W[N,K]^T) through esmdiff_gemm_bf16 (N % 128 == 0, K % 64 == 0)."""
+    return _gemm16(torch.bfloat16, A, W, epilogue, out, bias, alpha, n_valid)
 
 
 def gemm_f16(A: torch.Tensor, W: torch.Tensor, epilogue: int, *, out: Optional[torch.Tensor] = None,
              bias: Optional[torch.Tensor] = None, alpha: float = 1.0, n_valid: Optional[int] = None) -> torch.Tensor:
     """gemm_bf16's contract on the f16 build of the kernels (esmdiff_gemm_f16): A, W and 16-bit outputs are torch.float16."""
-    _require_gpu()
-    M, K = A.shape
-    Nn = W.shape[0]
-    assert A.dtype == W.dtype == torch.float16 and A.is_contiguous() and W.is_contiguous() and W.shape[1] == K
-    if out is None:
-        if epilogue in (N.EPI_BF16, N.EPI_BIAS_GELU_BF16):
-            out = torch.empty(M, Nn, dtype=torch.float16, device=A.device)
-        elif epilogue == N.EPI_SWIGLU_BF16:
-            out = torch.empty(M, Nn // 2, dtype=torch.float16, device=A.device)
-        else:
-            raise ValueError("f32 epilogues need an explicit `out`")
-    N.check(N.lib().esmdiff_gemm_f16(_ptr(A), _ptr(W), _ptr(out), _ptr(bias), M, Nn, K, out.stride(0),
-                                     Nn if n_valid is None else n_valid, float(alpha), epilogue, _stream()))
-    return out
+    return _gemm16(torch.float16, A, W, epilogue, out, bias, alpha, n_valid)
 
 
 def gemm_f32(A: torch.Tensor, W: torch.Tensor, epilogue: int = 0, *, out: Optional[torch.Tensor] = None,

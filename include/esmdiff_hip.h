@@ -164,7 +164,9 @@ int esmdiff_engine_create(const esmdiff_config* cfg, const esmdiff_weight* table
                           int32_t device, esmdiff_engine** out);
 void esmdiff_engine_destroy(esmdiff_engine* eng);
 
-/* Text of the last error on `eng` (or of the last failed create when eng == NULL). [host] */
+/* Text of the last error on `eng`.  With eng == NULL: the calling thread's handle-less string, which every call without a
+ * handle writes on failure — a failed create of any kind (engine, decoder, encoder) and the handle-less entries.  It is ONE
+ * string: esmdiff_encoder_last_error(NULL) returns the same text. [host] */
 const char* esmdiff_last_error(const esmdiff_engine* eng);
 
 /* Replaces self.net(structure_tokens=x, sequence_tokens=seq, auxiliary_embeddings=cond).structure_logits
@@ -463,6 +465,7 @@ int esmdiff_encoder_create(int32_t d_model, int32_t v_heads, int32_t n_layers, i
                            int32_t n_codes, int32_t knn, int32_t relpos_bins, int32_t precision /* esmdiff_precision */,
                            const esmdiff_weight* table, int32_t n_weights, int32_t device, esmdiff_encoder** out);
 void esmdiff_encoder_destroy(esmdiff_encoder* enc);
+/* Text of the last error on `enc`; with enc == NULL the handle-less string that esmdiff_last_error(NULL) returns too. */
 const char* esmdiff_encoder_last_error(const esmdiff_encoder* enc);
 int esmdiff_encoder_encode(esmdiff_encoder* enc, const float* ca, const float* rot, const float* trans,
                            const uint8_t* has_frame, int64_t* tokens, int32_t B, int32_t L, void* stream);

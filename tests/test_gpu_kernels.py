@@ -1504,6 +1504,59 @@ def test_engine_error_behaviour(tiny):
     assert out.shape == (1, 5) and int((out == MASK).sum()) == 0
 
 
+@pytest.mark.parametrize("precision", ["bf16", "f32"])
+def test_encoder_error_behaviour(precision):
+    """The encoder's boundary, loaded through the engine's weight loader: a missing, transposed or wrong-rank tensor and a bad
+    precision are refused with the engine's messages (the tensor is named), names are exact (no `net.` fallback), and a failed
+    create frees what it allocated and leaves no state behind: after each failure a correct encoder still builds and encodes a
+    (1, 9) backbone to the tokens of an encoder built before the failures.  Codes: ESMDIFF_E_MISSING -2, ESMDIFF_E_SHAPE -3."""
+    import ctypes
+    from esmdiff_amd import _native as N
+    from esmdiff_amd.config import TINY_ENCODER as cfg
+    from esmdiff_amd.engine import StructureEncoder
+    from esmdiff_amd.weights import random_init_encoder_state_dict
+    sd = random_init_encoder_state_dict(cfg, seed=2)
+    g = torch.Generator().manual_seed(9)
+    ca = torch.cumsum(torch.randn(1, 9, 3, generator=g) * 2.2, 1)
+    xyz = torch.stack([ca + torch.randn(1, 9, 3, generator=g) * 0.8, ca, ca + torch.randn(1, 9, 3, generator=g) * 0.8], 2)
+
+    def tokens():
+        enc = StructureEncoder(cfg, sd, precision=precision)
+        tok = enc.encode(xyz).cpu()
+        enc.close()
+        return tok
+
+    want = tokens()
+    assert want.shape == (1, 9) and int((want == MASK).sum()) == 0
+
+    def refused(bad, *match):
+        with pytest.raises(RuntimeError) as ei:
+            StructureEncoder(cfg, bad, precision=precision)
+        for m in match:
+            assert m in str(ei.value), (m, str(ei.value))
+        assert torch.equal(tokens(), want)
+
+    bad = dict(sd)
+    del bad["transformer.blocks.1.ffn.3.weight"]
+    refused(bad, "missing weight", "'transformer.blocks.1.ffn.3.weight'", "(-2)")
+    bad = dict(sd)
+    bad["pre_vq_proj.weight"] = sd["pre_vq_proj.weight"].T.contiguous()
+    refused(bad, "'pre_vq_proj.weight'", "dim 0", "(-3)")
+    bad = dict(sd)
+    bad["codebook.embeddings"] = sd["codebook.embeddings"].reshape(-1)
+    refused(bad, "'codebook.embeddings'", "ndim 1", "(-3)")
+    refused({"net." + k: v for k, v in sd.items()}, "missing weight", "(-2)")
+    # precision 2 (F32_SPLIT) is no encoder precision: refused before the table is read, on the handle-less string both
+    # *_last_error entries return
+    lib, h = N.lib(), ctypes.c_void_p(0)
+    code = lib.esmdiff_encoder_create(cfg.d_model, cfg.v_heads, cfg.n_layers, cfg.ffn_hidden, cfg.d_out, cfg.n_codes, cfg.knn,
+                                      cfg.relpos_bins, 2, (N.Weight * 1)(), 1, 0, ctypes.byref(h))
+    assert code == -1 and not h.value     # ESMDIFF_E_INVALID
+    assert "precision" in lib.esmdiff_encoder_last_error(None).decode()
+    assert lib.esmdiff_last_error(None) == lib.esmdiff_encoder_last_error(None)
+    assert torch.equal(tokens(), want)
+
+
 def _bench_line(extra):
     import json
     import os
