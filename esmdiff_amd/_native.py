@@ -70,6 +70,8 @@ EXPORTS = [
     "esmdiff_decoder_set_pair_chunk_bytes",
     "esmdiff_encoder_knn", "esmdiff_encoder_neighbourhood", "esmdiff_encoder_nearest_code",
     "esmdiff_forward_logits_needed", "esmdiff_get_tail_rows",
+    "esmdiff_layernorm_f32rows", "esmdiff_swiglu_f32", "esmdiff_qk_norm_rope_f32", "esmdiff_v_split",
+    "esmdiff_attention_f32_parts", "esmdiff_gemm_split_k", "esmdiff_get_attention_scales",
 ]
 LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
 DSSP_MAX_L = 4096                            # ESMDIFF_DSSP_MAX_L
@@ -198,6 +200,13 @@ def lib():
     L.esmdiff_encoder_knn.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.esmdiff_encoder_neighbourhood.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.esmdiff_encoder_nearest_code.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    L.esmdiff_layernorm_f32rows.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, vp]
+    L.esmdiff_swiglu_f32.argtypes = [vp, vp, i32, i32, vp]
+    L.esmdiff_qk_norm_rope_f32.argtypes = [vp, vp, vp, vp, i32, f32, f32, vp, vp, i32, i32, i32, vp]
+    L.esmdiff_v_split.argtypes = [vp, vp, i32, i32, f32, vp]
+    L.esmdiff_attention_f32_parts.argtypes = [vp, vp, vp, i32, f32, f32, vp, ctypes.POINTER(i32), i32, i32, i32, vp]
+    L.esmdiff_gemm_split_k.argtypes = [vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, f32, vp]
+    L.esmdiff_get_attention_scales.argtypes = [vp, i32, c_f32p, c_f32p]
     for n in EXPORTS:
         if n not in ("esmdiff_engine_destroy", "esmdiff_last_error", "esmdiff_encoder_destroy", "esmdiff_encoder_last_error"):
             getattr(L, n).restype = ctypes.c_int

@@ -282,6 +282,114 @@ int esmdiff_pae_tm(const float* logits, const int64_t* tokens, float* tm_rows, f
   return launched_sync(launch_pae_tm(logits, tokens, tm_rows, pae, ptm, nb, L, max_bin, st), st, "pae_tm");
 }
 
+// ---- the float32-grade row kernels of F32 / F32_SPLIT engines, one launcher at a time (synchronous) ----
+int esmdiff_layernorm_f32rows(const float* x, const float* w, const float* b, int32_t split, int32_t gelu_in, const void* delta,
+                              int32_t delta_dtype, void* a3, float* rs, float* y32, int32_t M, int32_t D, void* stream) {
+  if (!x || !w) return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_f32rows: null pointer");
+  if (split != 0 && split != 1) return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_f32rows: split %d (0 f32 rows, 1 split rows)", split);
+  if (M <= 0 || D <= 0 || D % 4 || D > 2048)
+    return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_f32rows: M=%d must be positive, D=%d a positive multiple of 4 up to 2048", M, D);
+  const hipStream_t st = (hipStream_t)stream;
+  if (!split) {
+    if (!y32 || gelu_in || delta || a3 || rs)
+      return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_f32rows: the f32 kernel writes y32 only and takes neither gelu_in nor delta");
+    return launched_sync(launch_layernorm_f32(x, w, b, y32, M, D, st), st, "layernorm_f32");
+  }
+  if (!a3 || !rs) return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_f32rows: the split kernel needs a3 and rs");
+  if ((gelu_in != 0 && gelu_in != 1) || (delta_dtype != 0 && delta_dtype != 1))
+    return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_f32rows: gelu_in %d (0 / 1), delta_dtype %d (0 bf16, 1 f16)", gelu_in, delta_dtype);
+  return launched_sync(launch_layernorm_split(x, w, b, (uint16_t*)a3, rs, y32, M, D, gelu_in, st, (const uint16_t*)delta, delta_dtype), st,
+                       "layernorm_split");
+}
+
+int esmdiff_swiglu_f32(const float* gu, float* mid, int32_t M, int32_t FH, void* stream) {
+  if (!gu || !mid) return fail(nullptr, ESMDIFF_E_INVALID, "swiglu_f32: null pointer");
+  if (M <= 0 || FH <= 0 || FH % 4)
+    return fail(nullptr, ESMDIFF_E_INVALID, "swiglu_f32: M=%d must be positive, FH=%d a positive multiple of 4", M, FH);
+  const hipStream_t st = (hipStream_t)stream;
+  return launched_sync(launch_swiglu_f32(gu, mid, M, FH, st), st, "swiglu_f32");
+}
+
+int esmdiff_qk_norm_rope_f32(esmdiff_engine* e, const float* qkv, const float* q_ln_w, const float* k_ln_w, int32_t split,
+                             float q_scale, float k_scale, void* q, void* k, int32_t B, int32_t L, int32_t H, void* stream) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (!qkv || !q_ln_w || !k_ln_w || !q || !k) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (!e->rope_cos || !e->rope_sin) return fail(e, ESMDIFF_E_INVALID, "esmdiff_qk_norm_rope_f32 needs an engine with rotary tables");
+  if (split != 0 && split != 1) return fail(e, ESMDIFF_E_INVALID, "split %d (0 f32 rows, 1 [hi | lo] f16 rows)", split);
+  if (H <= 0 || H > 32) return fail(e, ESMDIFF_E_INVALID, "H=%d: 1 .. 32 heads of 64", H);
+  if (B <= 0 || L <= 0 || L > e->cfg.max_len || (int64_t)B * L > 0x3fffffffll)   // the rotary tables hold max_len positions
+    return fail(e, ESMDIFF_E_INVALID, "B=%d L=%d: positive, L <= max_len (%d), B * L < 2^30", B, L, e->cfg.max_len);
+  if (split && !(q_scale > 0.f && k_scale > 0.f && std::isfinite(q_scale) && std::isfinite(k_scale)))
+    return fail(e, ESMDIFF_E_INVALID, "q_scale=%g k_scale=%g must be finite and positive", (double)q_scale, (double)k_scale);
+  const hipStream_t st = (hipStream_t)stream;
+  const hipError_t s = split ? launch_qk_norm_rope_split(qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, (uint16_t*)q, (uint16_t*)k, B, L, H,
+                                                         q_scale, k_scale, st)
+                             : launch_qk_norm_rope_f32(qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, (float*)q, (float*)k, B, L, H, st);
+  const hipError_t s2 = hipStreamSynchronize(st);
+  return launched(e, s == hipSuccess ? s2 : s, split ? "qk_norm_rope_split" : "qk_norm_rope_f32");
+}
+
+int esmdiff_v_split(const float* qkv, void* v2, int32_t M, int32_t D, float scale, void* stream) {
+  if (!qkv || !v2) return fail(nullptr, ESMDIFF_E_INVALID, "v_split: null pointer");
+  if (M <= 0 || D <= 0 || D % 4 || !(scale > 0.f) || !std::isfinite(scale))
+    return fail(nullptr, ESMDIFF_E_INVALID, "v_split: M=%d must be positive, D=%d a positive multiple of 4, scale=%g finite and positive", M, D,
+                (double)scale);
+  const hipStream_t st = (hipStream_t)stream;
+  return launched_sync(launch_v_split(qkv, (uint16_t*)v2, M, D, scale, st), st, "v_split");
+}
+
+int esmdiff_attention_f32_parts(const void* q, const void* k, const void* v, int32_t split, float qk_scale_product, float v_scale,
+                                float* ctx, const int32_t* lens, int32_t B, int32_t L, int32_t H, void* stream) {
+  if (!q || !k || !v || !ctx) return fail(nullptr, ESMDIFF_E_INVALID, "attention_f32_parts: null pointer");
+  if (split != 0 && split != 1) return fail(nullptr, ESMDIFF_E_INVALID, "attention_f32_parts: split %d (0 f32, 1 [hi | lo] f16 operands)", split);
+  if (B <= 0 || L <= 0 || H <= 0 || H > 32 || B > 65535 || (int64_t)B * L > 0x3fffffffll)
+    return fail(nullptr, ESMDIFF_E_INVALID, "attention_f32_parts: B=%d L=%d must be positive (B <= 65535, B * L < 2^30), H=%d in 1 .. 32", B, L, H);
+  if (split && !(qk_scale_product > 0.f && v_scale > 0.f && std::isfinite(qk_scale_product) && std::isfinite(v_scale)))
+    return fail(nullptr, ESMDIFF_E_INVALID, "attention_f32_parts: qk_scale_product=%g v_scale=%g must be finite and positive",
+                (double)qk_scale_product, (double)v_scale);
+  if (lens)   // the kernels index with them
+    for (int b = 0; b < B; ++b)
+      if (lens[b] < 1 || lens[b] > L)
+        return fail(nullptr, ESMDIFF_E_INVALID, "attention_f32_parts: lens[%d] = %d outside 1..L (%d)", b, lens[b], L);
+  const hipStream_t st = (hipStream_t)stream;
+  int32_t* dl = nullptr;
+  if (lens && hipMalloc(&dl, (size_t)B * sizeof(int32_t)) != hipSuccess) return fail(nullptr, ESMDIFF_E_HIP, "attention_f32_parts: hipMalloc failed");
+  hipError_t s = lens ? hipMemcpyAsync(dl, lens, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st) : hipSuccess;
+  if (s == hipSuccess) {
+    if (split)
+      s = launch_attention_split((const uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v, ctx, B, L, H, qk_scale_product, v_scale, st, dl);
+    else
+      s = launch_attention_f32((const float*)q, (const float*)k, (const float*)v, ctx, B, L, H, st, dl);
+  }
+  const hipError_t s2 = hipStreamSynchronize(st);   // synchronous: the length buffer and the caller's host copy die here
+  if (s == hipSuccess) s = s2;
+  if (dl) hipFree(dl);
+  return launched(nullptr, s, split ? "attention_split" : "attention_f32");
+}
+
+int esmdiff_gemm_split_k(const void* a3, const float* rs, const void* w3, float w_inv_scale, float* parts, float* x, int32_t M,
+                         int32_t N, int32_t K, int32_t S, float div, void* stream) {
+  if (!a3 || !w3 || !parts || !x) return fail(nullptr, ESMDIFF_E_INVALID, "gemm_split_k: null pointer");
+  if (M <= 0 || N <= 0 || K <= 0 || K > 0x7fffffff / 3 || !(div != 0.f))
+    return fail(nullptr, ESMDIFF_E_INVALID, "gemm_split_k: M=%d N=%d K=%d must be positive, div=%g non-zero", M, N, K, (double)div);
+  if (S < 2 || N % 256 || (3 * K) % S || ((3 * K) / S) % 128 || (3 * K) / S < 384)   // what launch_gemm256w4_splitk accepts
+    return fail(nullptr, ESMDIFF_E_INVALID, "gemm_split_k: S=%d >= 2, N=%d %% 256 == 0, 3K / S (K=%d) a multiple of 128 and at least 384", S, N, K);
+  const hipStream_t st = (hipStream_t)stream;
+  hipError_t s = launch_gemm256w4_splitk((const uint16_t*)a3, (const uint16_t*)w3, w_inv_scale, parts, M, N, K, S, st);
+  if (s == hipSuccess) s = launch_splitk_reduce_resid(parts, rs, x, M, N, S, div, st);
+  return launched_sync(s, st, "gemm_split_k");
+}
+
+int esmdiff_get_attention_scales(esmdiff_engine* e, int32_t layer, float* qk_out, float* v_out) {
+  if (!e) return ESMDIFF_E_INVALID;
+  if (!qk_out || !v_out) return fail(e, ESMDIFF_E_INVALID, "null pointer");
+  if (!(e->strict && e->split)) return fail(e, ESMDIFF_E_INVALID, "esmdiff_get_attention_scales needs an F32_SPLIT engine");
+  if (layer < 0 || layer >= (int)e->layers.size()) return fail(e, ESMDIFF_E_INVALID, "layer %d outside 0 .. %d", layer, (int)e->layers.size() - 1);
+  *qk_out = e->layers[layer].att_qk;
+  *v_out = e->layers[layer].att_v;
+  return 0;
+}
+
 int esmdiff_decoder_set_pair_chunk_bytes(esmdiff_engine* e, int64_t bytes) {
   if (!e) return ESMDIFF_E_INVALID;
   if (e->kind != 1) return fail(e, ESMDIFF_E_INVALID, "not a decoder engine");

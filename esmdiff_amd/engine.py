@@ -745,6 +745,28 @@ class Engine(_Handle):
                                                  _ptr(k_ln_w.float().contiguous()), _ptr(q), _ptr(k), B, L, H, _stream()))
         return q, k
 
+    def qk_norm_rope_f32(self, qkv: torch.Tensor, q_ln_w: torch.Tensor, k_ln_w: torch.Tensor, B: int, L: int, H: int, *,
+                         split: bool = False, q_scale: float = 1.0, k_scale: float = 1.0):
+        """The q/k LayerNorm + rotary kernel of the float32-grade engines alone, with this engine's rotary tables
+        (esmdiff_qk_norm_rope_f32): qkv f32 [B*L, 3*H*64] -> (q, k) f32 [B*L, H*64] unscaled, or with split [hi | lo] f16
+        [B*L, 2*H*64] of the rotated rows * q_scale / k_scale."""
+        D = H * 64
+        assert qkv.dtype == torch.float32 and qkv.shape == (B * L, 3 * D) and qkv.is_contiguous()
+        assert q_ln_w.numel() == k_ln_w.numel() == D
+        q = torch.full((B * L, 2 * D if split else D), float("nan"), dtype=torch.float16 if split else torch.float32,
+                       device=self.device)
+        k = q.clone()
+        self._chk(self._lib.esmdiff_qk_norm_rope_f32(self._h, _ptr(qkv), _ptr(q_ln_w.float().contiguous()),
+                                                     _ptr(k_ln_w.float().contiguous()), int(split), float(q_scale), float(k_scale),
+                                                     _ptr(q), _ptr(k), B, L, H, _stream()))
+        return q, k
+
+    def attention_scales(self, layer: int):
+        """(att_qk, att_v): the power-of-two operand scales block `layer` of an f32_split engine chose at create."""
+        qk, v = ctypes.c_float(0), ctypes.c_float(0)
+        self._chk(self._lib.esmdiff_get_attention_scales(self._h, int(layer), ctypes.byref(qk), ctypes.byref(v)))
+        return float(qk.value), float(v.value)
+
 
 class StructureDecoder(_Handle):
     """Structure tokens -> backbone coordinates on the device (esmdiff_decoder_create / esmdiff_decoder_decode): what the
@@ -942,6 +964,80 @@ def gemm_split(a2: torch.Tensor, rs: Optional[torch.Tensor], w2: torch.Tensor, w
     N.check(N.lib().esmdiff_gemm_split(_ptr(a2), _ptr(rs), _ptr(w2), float(w_inv), _ptr(out), _ptr(bias), M, n_pad, K3 // 3,
                                        out.stride(0), float(div), epilogue, _stream()))
     return out[:, :n_out]
+
+
+def gemm_split_k(a2: torch.Tensor, rs: Optional[torch.Tensor], w2: torch.Tensor, w_inv: float, x: torch.Tensor, S: int,
+                 div: float = 1.0) -> torch.Tensor:
+    """The K-sliced split GEMM and its reduce (esmdiff_gemm_split_k): x f32 [M, N] += (sum of the S slice products of
+    a2 [M, 3K] . w2 [N, 3K]^T * w_inv) * rs / div, in place; returns the slice planes f32 [S, M rounded up to 256, N]."""
+    _require_gpu()
+    M, K3 = a2.shape
+    Nn = w2.shape[0]
+    assert a2.dtype == w2.dtype == torch.float16 and w2.shape[1] == K3 and a2.is_contiguous() and w2.is_contiguous()
+    assert x.dtype == torch.float32 and x.shape == (M, Nn) and x.is_contiguous()
+    assert rs is None or (rs.dtype == torch.float32 and rs.numel() == M)
+    parts = torch.empty(max(int(S), 1), (M + 255) // 256 * 256, Nn, dtype=torch.float32, device=a2.device)
+    N.check(N.lib().esmdiff_gemm_split_k(_ptr(a2), _ptr(rs), _ptr(w2), float(w_inv), _ptr(parts), _ptr(x), M, Nn, K3 // 3, int(S),
+                                         float(div), _stream()))
+    return parts
+
+
+def layernorm_f32rows(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], *, split: bool, gelu_in: bool = False,
+                      delta: Optional[torch.Tensor] = None, want_y32: bool = True):
+    """One LayerNorm kernel of the float32-grade engines (esmdiff_layernorm_f32rows).  split False: layernorm_f32_kernel ->
+    y32 f32 [M, D].  split True: layernorm_split_kernel of gelu(x) when gelu_in, of x + delta (bf16 / f16 [M, D]) when given
+    -> (a3 f16 [M, 3D] = [hi | lo | hi], rs f32 [M], y32 or None)."""
+    _require_gpu()
+    M, D = x.shape
+    assert x.dtype == w.dtype == torch.float32 and x.is_contiguous() and w.numel() == D
+    assert b is None or (b.dtype == torch.float32 and b.numel() == D)
+    assert delta is None or (delta.dtype in (torch.bfloat16, torch.float16) and delta.shape == (M, D) and delta.is_contiguous())
+    y32 = torch.full((M, D), float("nan"), dtype=torch.float32, device=x.device) if (want_y32 or not split) else None
+    a3 = torch.full((M, 3 * D), float("nan"), dtype=torch.float16, device=x.device) if split else None
+    rs = torch.full((M,), float("nan"), dtype=torch.float32, device=x.device) if split else None
+    N.check(N.lib().esmdiff_layernorm_f32rows(_ptr(x), _ptr(w), _ptr(b), int(split), int(gelu_in), _ptr(delta),
+                                              int(delta is not None and delta.dtype == torch.float16), _ptr(a3), _ptr(rs),
+                                              _ptr(y32), M, D, _stream()))
+    return (a3, rs, y32) if split else y32
+
+
+def swiglu_f32(gu: torch.Tensor) -> torch.Tensor:
+    """gu f32 [M, 2 FH] = [gate | up] -> silu(gate) * up f32 [M, FH] (esmdiff_swiglu_f32: the F32 engine's own pass)."""
+    _require_gpu()
+    M, FH2 = gu.shape
+    assert gu.dtype == torch.float32 and gu.is_contiguous() and FH2 % 2 == 0
+    mid = torch.full((M, FH2 // 2), float("nan"), dtype=torch.float32, device=gu.device)
+    N.check(N.lib().esmdiff_swiglu_f32(_ptr(gu), _ptr(mid), M, FH2 // 2, _stream()))
+    return mid
+
+
+def v_split(qkv: torch.Tensor, scale: float) -> torch.Tensor:
+    """qkv f32 [M, 3D] -> [hi | lo] f16 [M, 2D] of its V third * scale (esmdiff_v_split)."""
+    _require_gpu()
+    M, D3 = qkv.shape
+    assert qkv.dtype == torch.float32 and qkv.is_contiguous() and D3 % 3 == 0
+    v2 = torch.full((M, 2 * (D3 // 3)), float("nan"), dtype=torch.float16, device=qkv.device)
+    N.check(N.lib().esmdiff_v_split(_ptr(qkv), _ptr(v2), M, D3 // 3, float(scale), _stream()))
+    return v2
+
+
+def attention_f32_parts(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, L: int, H: int, *,
+                        qk_scale_product: float = 1.0, v_scale: float = 1.0,
+                        lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """One attention kernel of the float32-grade engines (esmdiff_attention_f32_parts) -> ctx f32 [B*L, H*64] (NaN where
+    the kernel wrote nothing).  float32 q, k [B*L, H*64] and v = a qkv buffer [B*L, 3*H*64]: attention_f32_kernel; float16
+    [hi | lo] rows [B*L, 2*H*64] each: attention_split_kernel with its two scale arguments."""
+    _require_gpu()
+    D = H * 64
+    split = q.dtype == torch.float16
+    want = ((B * L, 2 * D),) * 3 if split else ((B * L, D), (B * L, D), (B * L, 3 * D))
+    for t, shape in zip((q, k, v), want):
+        assert t.dtype == (torch.float16 if split else torch.float32) and t.shape == shape and t.is_contiguous()
+    ctx = torch.full((B * L, D), float("nan"), dtype=torch.float32, device=q.device)
+    arr = None if lengths is None else (ctypes.c_int32 * B)(*[int(n) for n in lengths])
+    N.check(N.lib().esmdiff_attention_f32_parts(_ptr(q), _ptr(k), _ptr(v), int(split), float(qk_scale_product), float(v_scale),
+                                                _ptr(ctx), arr, B, L, H, _stream()))
+    return ctx
 
 
 def gemm_bf16_timed(A, W, out, epilogue, iters=20, bias=None, alpha=1.0) -> float:

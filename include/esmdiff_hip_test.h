@@ -161,6 +161,42 @@ int esmdiff_encoder_neighbourhood(const int32_t* edges, const float* table, cons
 int esmdiff_encoder_nearest_code(const float* z, const float* code, const uint8_t* has, int32_t R, int32_t n_codes, int32_t d_out,
                                  int64_t* tok, void* stream);
 
+/* ---- The float32-grade row kernels between the GEMMs of F32 and F32_SPLIT engines (csrc/strict.hip, csrc/gemm_split.hip,
+ * csrc/attention_split.hip), one launcher at a time (tests/test_gpu_f32_rows.py).  All synchronous; every argument is checked
+ * before the first HIP call (ESMDIFF_E_INVALID).  f16 buffers are IEEE half bits. ----
+ *   esmdiff_layernorm_f32rows  LayerNorm of x f32 [M, D] * w (+ b), eps 1e-5; D % 4 == 0, D <= 2048.
+ *                              split 0 (launch_layernorm_f32): y32 f32 [M, D]; gelu_in 0, delta, a3 and rs NULL.
+ *                              split 1 (launch_layernorm_split): LayerNorm of gelu(x) when gelu_in, of x + delta when delta
+ *                              ([M, D], delta_dtype 0 bf16 / 1 f16) -> a3 f16 [M, 3D] = [hi | lo | hi] of the row scaled by a
+ *                              power of two, rs f32 [M] = 1 / scale, and the f32 row into y32 when non-NULL
+ *   esmdiff_swiglu_f32         gu f32 [M, 2 FH] = [gate | up] -> mid f32 [M, FH] = silu(gate) * up; FH % 4 == 0
+ *   esmdiff_qk_norm_rope_f32   qkv f32 [B*L, 3*H*64] -> full-width LayerNorm of q and k (no bias) + rotary with the engine's tables
+ *                              (H 1 .. 32 explicit, as esmdiff_qk_norm_rope; any ESM3 engine).  split 0: q, k f32 [B*L, H*64],
+ *                              unscaled (q_scale, k_scale ignored).  split 1: q, k f16 [B*L, 2*H*64] = [hi | lo] of the rotated
+ *                              row * q_scale / k_scale (finite, > 0; the caller folds log2(e)/8 into q_scale, as the engine does)
+ *   esmdiff_v_split            qkv f32 [M, 3D] -> v2 f16 [M, 2D] = [hi | lo] of the V third * scale; D % 4 == 0
+ *   esmdiff_attention_f32_parts  softmax(q k^T / 8) v per 64-wide head -> ctx f32 [B*L, H*64], operands as the kernel takes them.
+ *                              split 0 (attention_f32_kernel): q, k f32 [B*L, H*64], v = the qkv buffer f32 [B*L, 3*H*64] (its V third
+ *                              is read).  split 1 (attention_split_kernel): q, k, v f16 [B*L, 2*H*64] = [hi | lo] of q * log2(e)/8 *
+ *                              q_scale, k * k_scale, v * v_scale; qk_scale_product = q_scale * k_scale.  lens: HOST int32 [B],
+ *                              each in 1..L, or NULL (as esmdiff_attention_ragged)
+ *   esmdiff_gemm_split_k       launch_gemm256w4_splitk + launch_splitk_reduce_resid: parts f32 [S, M rounded up to 256, N]
+ *                              (caller-owned) = the S K-slice products of a3 [M, 3K] . w3 [N, 3K]^T * w_inv_scale, then
+ *                              x f32 [M, N] = x + ((parts[0] + parts[1]) + ...) * rs[m] / div.  S >= 2, N % 256 == 0, 3K / S a
+ *                              multiple of 128 and at least 384
+ *   esmdiff_get_attention_scales  the power-of-two operand scales layer `layer` of an F32_SPLIT engine chose at create */
+int esmdiff_layernorm_f32rows(const float* x, const float* w, const float* b, int32_t split, int32_t gelu_in, const void* delta,
+                              int32_t delta_dtype, void* a3, float* rs, float* y32, int32_t M, int32_t D, void* stream);
+int esmdiff_swiglu_f32(const float* gu, float* mid, int32_t M, int32_t FH, void* stream);
+int esmdiff_qk_norm_rope_f32(esmdiff_engine* eng, const float* qkv, const float* q_ln_w, const float* k_ln_w, int32_t split,
+                             float q_scale, float k_scale, void* q, void* k, int32_t B, int32_t L, int32_t H, void* stream);
+int esmdiff_v_split(const float* qkv, void* v2, int32_t M, int32_t D, float scale, void* stream);
+int esmdiff_attention_f32_parts(const void* q, const void* k, const void* v, int32_t split, float qk_scale_product, float v_scale,
+                                float* ctx, const int32_t* lens, int32_t B, int32_t L, int32_t H, void* stream);
+int esmdiff_gemm_split_k(const void* a3, const float* rs, const void* w3, float w_inv_scale, float* parts, float* x, int32_t M,
+                         int32_t N, int32_t K, int32_t S, float div, void* stream);
+int esmdiff_get_attention_scales(esmdiff_engine* eng, int32_t layer, float* qk_out, float* v_out);
+
 /* ---- Needed rows (ESMDIFF_OPT_NEEDED_ROWS, esmdiff_ddpm_sample in esmdiff_hip.h), one forward at a time ----
  *   esmdiff_forward_logits_needed  esmdiff_forward_logits as a forward of esmdiff_ddpm_sample runs it: the rows to keep are
  *                                  derived from x (those that hold MASK), and logits_out is written on those rows only — every

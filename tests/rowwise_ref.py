@@ -2,6 +2,8 @@
 attention (csrc/geom.hip), q/k LayerNorm + rotary and the fused residual add + LayerNorm (csrc/norm.hip), attention
 (csrc/attention.hip).  tests/test_gpu_rowwise.py compares the kernels through them; tests/test_rowwise_bars_cpu.py shows
 that the same comparators pass the float64 reference rounded to each build's type and reject planted errors.
+The second half holds the same for the row kernels of the float32-grade engines (csrc/strict.hip, csrc/gemm_split.hip,
+csrc/attention_split.hip): tests/test_gpu_f32_rows.py and tests/test_f32_rows_bars_cpu.py.
 
 Every bar has the form  |got - ref| <= OUT_EPS[type] * |ref| + coef * unit : the first term is the output rounding of the
 build (round to nearest: half an ulp, at most 2^-8 |x| for bfloat16, 2^-11 |x| for IEEE half, nothing for float32), the
@@ -219,3 +221,284 @@ def add_ln_ref64(v32: torch.Tensor, w, b, *, eps: float = LN_EPS):
     y, rstd, vmax = ln64(v32, w, b, eps=eps)
     nw, _, _ = ln64(v32, w, None, eps=eps)
     return y, F32_EPS * (y.abs() + nw.abs() + rstd * w.double().abs() * vmax)
+
+
+# ===============================================================================================================
+# The float32-grade row kernels of F32 / F32_SPLIT engines (csrc/strict.hip, csrc/gemm_split.hip, csrc/attention_split.hip):
+# tests/test_gpu_f32_rows.py compares them through what follows, tests/test_f32_rows_bars_cpu.py shows that the same
+# comparators pass the float64 reference rounded to float32 and a torch float32 evaluation, and reject planted defects.
+# OUT_EPS[float32] = 0: every bar below is coef x an arithmetic unit alone.
+
+def gelu64(x: torch.Tensor, tanh: bool = False) -> torch.Tensor:
+    """Exact (erf) GELU in float64; tanh: the approximation the kernels must NOT compute (plants only)."""
+    x = x.double()
+    if tanh:
+        return 0.5 * x * (1 + torch.tanh(math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3)))
+    return 0.5 * x * (1 + torch.erf(x / math.sqrt(2)))
+
+
+def ln_rows_ref64(x32: torch.Tensor, w, b, *, gelu_in: bool = False, delta=None, eps: float = LN_EPS, tanh_gelu: bool = False,
+                  delta_times: int = 1):
+    """layernorm_f32_kernel / layernorm_split_kernel: LayerNorm of x (+ delta: the float32 sum x + float(delta) is exact
+    arithmetic, the reference starts from it), or of the exact-erf GELU of x -> (ref, unit) float64 under LN_COEF.  With
+    gelu_in the unit gains 4 x 2^-24 rstd |w| max|gelu(x)| for the f32 erff.  tanh_gelu / delta_times: plants."""
+    v = x32
+    for _ in range(delta_times if delta is not None else 0):
+        v = v + delta.float()
+    if not gelu_in:
+        return add_ln_ref64(v, w, b, eps=eps)
+    g = gelu64(v, tanh_gelu)
+    ref, unit = add_ln_ref64(g, w, b, eps=eps)
+    _, rstd, _ = ln64(gelu64(v), w, None, eps=eps)
+    return ref, unit + 4 * F32_EPS * rstd * w.double().abs() * gelu64(v).abs().amax(-1, keepdim=True)
+
+
+LN_ROW_KINDS = ("unit", "low_variance", "scale_1e4", "spike", "zero")
+LN_LOW_VARIANCE, LN_ZERO = 1, 4                                             # indices into LN_ROW_KINDS
+
+
+def ln_case(M: int, D: int, seed: int, gain: float, first_kind: int = 0):
+    """(x f32 [M, D], w, b, delta f32 [M, D], kinds [M]): row r is of kind LN_ROW_KINDS[(first_kind + r) % 5] — unit normal;
+    low variance (5 + 2e-3 randn: eps = 1e-5 matters, the mean's rounding is multiplied by a large rstd); scale 1e4; a single
+    1e3 spike over 1e-2 noise; all zero (row_scale's clamp: finite rs, a zero split when there is no bias).  w = gain (1 + 0.3
+    randn), b = 0.2 gain randn; delta (a 16-bit branch output, to be rounded by the caller) is 1e-3 of the row's own spread on
+    the low-variance row so that the row stays one."""
+    g = torch.Generator().manual_seed(seed)
+    kinds = (first_kind + torch.arange(M)) % 5
+    x = torch.randn(M, D, generator=g)
+    delta = torch.randn(M, D, generator=g)
+    for r in range(M):
+        kd = int(kinds[r])
+        if kd == 1:
+            x[r] = 5 + 2e-3 * x[r]
+            delta[r] *= 2e-6
+        elif kd == 2:
+            x[r] *= 1e4
+        elif kd == 3:
+            x[r] *= 1e-2
+            x[r, (7 * r + 3) % D] = 1e3
+        elif kd == 4:
+            x[r] = 0
+    w = gain * (1 + 0.3 * torch.randn(D, generator=g))
+    b = 0.2 * gain * torch.randn(D, generator=g)
+    return x, w, b, delta, kinds
+
+
+# ---- split rows (gemm_split.hip: row_scale / split4; attention_split.hip: split_pair).  a = y s with s a power of two; hi =
+# f16(a) to nearest, lo = f16(a - hi): |a - hi| <= 2^-11 |a| (half an ulp of 11 bits), lo rounds that to 11 bits again or,
+# below f16's normal range, to the subnormal spacing 2^-24: |hi + lo - a| <= max(2^-22 |a|, 2^-25).  Derived, not measured.
+SPLIT_REL, SPLIT_ABS = 2.0 ** -22, 2.0 ** -25
+
+
+def split_bar(a: torch.Tensor) -> torch.Tensor:
+    return torch.clamp(SPLIT_REL * a.double().abs(), min=SPLIT_ABS)
+
+
+def split_emulate(y32: torch.Tensor, s: torch.Tensor, *, toward_zero: bool = False):
+    """What split4 computes from the f32 values y32 and the power-of-two scale s (broadcast): (hi, lo) float16.
+    toward_zero: hi truncated instead of rounded to nearest (a plant)."""
+    a = y32.float() * s.float()
+    hi = a.half()
+    if toward_zero:
+        up = hi.float().abs() > a.abs()                                     # rounded away from zero: step one f16 back
+        bits = hi.view(torch.int16) - up.to(torch.int16)                   # sign-magnitude: the magnitude's predecessor
+        hi = bits.view(torch.float16)
+    lo = (a - hi.float()).half()
+    return hi, lo
+
+
+def row_scale_ref(y32: torch.Tensor) -> torch.Tensor:
+    """row_scale's rs = 1 / s per row of y32 (f32 [M, D]): 2^(e - 14), e the exponent of the row maximum clamped as the kernel
+    clamps it (biased 20 .. 250), so that the maximum lands in [2^14, 2^15).  float32 [M]."""
+    amax = y32.float().abs().amax(-1)
+    eb = ((amax.view(torch.int32) >> 23) & 0xff).clamp(20, 250)
+    return ((eb - 14) << 23).to(torch.int32).view(torch.float32)
+
+
+def split_planes(a3: torch.Tensor, D: int, planes: int = 3):
+    """a3 f16 [M, planes D] -> (hi, lo) float64 and, for the GEMM's [hi | lo | hi] rows, the third plane (else None)."""
+    hi, lo = a3[:, :D], a3[:, D:2 * D]
+    return hi.double(), lo.double(), (a3[:, 2 * D:3 * D] if planes == 3 else None)
+
+
+def half_ulp_f16(hi: torch.Tensor) -> torch.Tensor:
+    """Half the spacing of float16 at hi (float64 values of f16 numbers): 2^(e - 11) for |hi| in [2^e, 2^(e+1)), 2^-25 below 2^-14."""
+    _, e = torch.frexp(hi)                                                   # |hi| = m 2^e, m in [0.5, 1)
+    # 2^(e - 12) from its exponent bits: exact on every device (a device pow / ldexp may miss a power of two by an ulp)
+    half = ((e.to(torch.int64) - 12 + 1023).clamp(min=1) << 52).view(torch.float64)
+    return torch.where(hi == 0, torch.full_like(hi, 2.0 ** -25), torch.clamp(half, min=2.0 ** -25))
+
+
+def split_rows_report(a3: torch.Tensor, rs: torch.Tensor, y32: torch.Tensor) -> dict:
+    """Every property of a split row [hi | lo | hi] + rs against the f32 row y32 it was made from, located per row:
+      value   [M, D] |hi + lo - y / rs| over split_bar (<= 1 passes)
+      rs_ok   [M]    rs is exactly row_scale's power of two for this row (finite, also on an all-zero row)
+      planes  [M]    plane 2 equals plane 0 bit for bit
+      range   [M]    max |hi| in [2^14, 2^15] (closed: a maximum that rounds up to 32768 passes); all-zero rows: a zero split
+      nearest [M]    |lo| <= half an ulp of hi: hi was rounded to nearest, not toward zero (then |lo| reaches a whole ulp)
+      finite  [M]    """
+    D = y32.shape[-1]
+    hi, lo, hi2 = split_planes(a3, D)
+    a = y32.double() / rs.double()[:, None]
+    err = (hi + lo - a).abs()
+    value = torch.where(err == 0, torch.zeros_like(err), err / split_bar(a))
+    want = row_scale_ref(y32).to(rs.device)
+    hmax = hi.abs().amax(-1)
+    zero_row = y32.abs().amax(-1) == 0
+    rng = torch.where(zero_row, (a3.float().abs().amax(-1) == 0), (hmax >= 2.0 ** 14) & (hmax <= 2.0 ** 15))
+    return {"value": value, "rs_ok": (rs == want) & torch.isfinite(rs) & (rs > 0),
+            "planes": (a3[:, :D].view(torch.int16) == hi2.view(torch.int16)).all(-1), "range": rng,
+            "nearest": (lo.abs() <= half_ulp_f16(hi)).all(-1),
+            "finite": torch.isfinite(a3.float()).all(-1) & torch.isfinite(value).all(-1)}
+
+
+def split_rows_ok(rep: dict) -> bool:
+    return bool((rep["value"] <= 1).all() and rep["rs_ok"].all() and rep["planes"].all() and rep["range"].all()
+                and rep["nearest"].all() and rep["finite"].all())
+
+
+def split_rows_explain(rep: dict, a3: torch.Tensor, rs: torch.Tensor, y32: torch.Tensor) -> str:
+    """What failed in a split_rows_report and the numbers of the first offending element, for an assert's message."""
+    D = y32.shape[-1]
+    hi, lo, _ = split_planes(a3, D)
+    out = []
+    for key, v in rep.items():
+        bad = (v > 1) if key == "value" else ~v
+        if not bool(bad.any()):
+            continue
+        r = int(bad.reshape(bad.shape[0], -1).any(-1).nonzero()[0])
+        el = (lo[r].abs() > half_ulp_f16(hi[r])) if key == "nearest" else (rep["value"][r] > 1)
+        c = int(el.nonzero()[0]) if bool(el.any()) else int(y32[r].abs().argmax())
+        out.append(f"{key}: row {r} col {c} y {float(y32[r, c])!r} rs {float(rs[r])!r} hi {float(hi[r, c])!r} lo {float(lo[r, c])!r} "
+                   f"value ratio {float(rep['value'][r, c]):.3f} max|hi| {float(hi[r].abs().max())!r}")
+    return "; ".join(out)
+
+
+def is_pow2(v: float) -> bool:
+    return v > 0 and math.isfinite(v) and math.frexp(v)[0] == 0.5
+
+
+# ---- q/k LayerNorm + rotary of the float32-grade engines: qk_rope_ref64 with its q scale replaced by the kernel's own
+# The q/k LayerNorm gain the tests pair with each split scale: |row| <= sqrt(D - 1) max|w| scale must stay inside f16 (the rule
+# the engine picks its scale by): gains of 6 up to 2^6 (45 x 12 x 64 = 35 000 at D = 2048), 0.05 at 2^13 (45 x 0.1 x 8192 = 37 000).
+QK_SPLIT_GAIN = {1.0: 6.0, 2.0 ** 6: 6.0, 2.0 ** 13: 0.05}
+
+
+def qk_rope_f32_ref64(qkv, q_w, k_w, B, L, H, *, q_scale: float = 1.0, k_scale: float = 1.0, **plant):
+    """((q_ref, q_unit), (k_ref, k_unit)) for qk_norm_rope_f32_kernel (no scale) / qk_norm_rope_split_kernel (the rotated rows
+    times q_scale / k_scale: reference and unit carry the same factor).  Bar: QK_COEF x unit, plus split_bar(ref) for the
+    split form's hi + lo."""
+    (q, qu), (k, ku) = qk_rope_ref64(qkv, q_w, k_w, B, L, H, **plant)
+    return (q * (q_scale / QSCALE), qu * (q_scale / QSCALE)), (k * k_scale, ku * k_scale)
+
+
+# ---- attention in float32 grade (attention_f32_kernel: fmaf chains; attention_split_kernel: split operands, exact products,
+# f32 accumulation).  A logit s = q.k / 8 carries ~2^-24 |q| |k| / 8 of accumulation error, which moves p_k by that
+# relative amount; exp, the running sums and the final division add ~2^-24 each:
+# unit(b, h, query, channel) = 2^-24 (1 + |q| kmax / 8) sum_k p_k |v_k|.
+# ATT32_COEF = 4 x the largest needed_coef of a plain torch float32 evaluation of the same formula on the test's own inputs
+# (attention_cases below), rounded up to a power of two.  Measured on the CPU (tests/test_f32_rows_bars_cpu.py, EXPERIMENTS.md):
+# float32 torch needs 1.29 (unit), 2.47 / 2.18 (gains 4 / 8), 1.74 (one_key), 1.16 (falling staircase) and 5.92 on the rising
+# staircase at L = 258 (q and k
+# nearly parallel with |q| |k| / 8 = 20: every partial sum of the 64-term dot product rounds in the same direction)
+# -> 4 x 5.92 = 23.7 -> 32.
+ATT32_COEF = 32.0
+
+
+def attention32_ref64(q, k, v, B: int, L: int, H: int, *, drop_last_key: bool = False):
+    """softmax(q k^T / 8) v per head in float64 from q, k, v [B*L, H*64] as the kernel was handed them -> (ref, unit)."""
+    D = H * 64
+    q, k, v = (t.double().view(B, L, H, 64).transpose(1, 2) for t in (q, k, v))
+    s = q @ k.transpose(-1, -2) / 8
+    if drop_last_key:
+        s[..., -1] = -float("inf")
+    p = torch.softmax(s, -1)
+    ref = (p @ v).transpose(1, 2).reshape(B * L, D)
+    qn = q.norm(dim=-1, keepdim=True)
+    kmax = k.norm(dim=-1).amax(-1)[..., None, None]
+    unit = F32_EPS * (1 + qn * kmax / 8) * (p @ v.abs())
+    return ref, unit.transpose(1, 2).reshape(B * L, D)
+
+
+def attention32_torch(q, k, v, B: int, L: int, H: int) -> torch.Tensor:
+    """The same formula evaluated by torch in float32 (what ATT32_COEF is calibrated on)."""
+    q, k, v = (t.float().view(B, L, H, 64).transpose(1, 2) for t in (q, k, v))
+    p = torch.softmax(q @ k.transpose(-1, -2) / 8, -1)
+    return (p @ v).transpose(1, 2).reshape(B * L, H * 64)
+
+
+LN2_8 = 8 * math.log(2.0)                                                   # 1 / (log2(e) / 8)
+
+
+def split_operand(x32: torch.Tensor, scale: float) -> torch.Tensor:
+    """[hi | lo] float16 rows of x32 * scale (float32 product), as qk_norm_rope_split / v_split hand them to the attention."""
+    hi, lo = split_emulate(x32, torch.tensor(scale, dtype=torch.float32, device=x32.device))
+    return torch.cat([hi, lo], -1).contiguous()
+
+
+def split_operand_value(x2: torch.Tensor, scale: float) -> torch.Tensor:
+    """(hi + lo) / scale in float64: the operand the split attention really multiplies (its rounding is not charged twice)."""
+    D = x2.shape[-1] // 2
+    return (x2[:, :D].double() + x2[:, D:].double()) / scale
+
+
+ATT_KINDS = ("unit", "gain4", "gain8", "stairs_up", "stairs_down", "one_key")
+# L: one stage (<= 64), the HALF tail (tail <= 32), the masked tail, exact tiles, 1 to 4 waves of 32 queries, several query blocks
+ATT_LS = (1, 31, 32, 33, 64, 65, 96, 97, 128, 129, 258)
+ATT_BH = ((1, 1), (3, 3), (2, 8))                                           # B H = 1, 9 (XCD slots left empty), 16
+
+
+def attention_case(kind: str, B: int, L: int, H: int, seed: int):
+    """q, k, v float32 [B*L, H*64] (CPU).  unit / gain4 / gain8: N(0, 1) rows times 1 / 4 / 8 on q and k (trained q/k LayerNorm
+    gains).  stairs_up / stairs_down: the best logit rises / falls by 5 nats (7.2 log2 units, above the split kernel's lazy-rescale
+    threshold of 4) from one 64-key tile to the next: a rescale at every tile, or never after the first.  one_key: key 2L/3
+    carries all the mass, every other p is below 2^-13 (the lo part of P is subnormal)."""
+    g = torch.Generator().manual_seed(seed)
+    shape = (B, L, H, 64)
+    q, k, v = (torch.randn(shape, generator=g) for _ in range(3))
+    if kind.startswith("gain"):
+        q, k = q * float(kind[4:]), k * float(kind[4:])
+    elif kind != "unit":
+        u = torch.randn(B, 1, H, 64, generator=g)
+        u = u / u.norm(dim=-1, keepdim=True)
+        q = 8 * u + 0.3 * q                                                  # q . k / 8 = (u . k) + noise
+        if kind == "one_key":
+            k = 0.3 * k
+            k[:, (2 * L) // 3] = 12 * u[:, 0] + 0.3 * k[:, (2 * L) // 3]
+        else:
+            tile = (torch.arange(L) // 64).float()[None, :, None, None]
+            k = 0.3 * k + (5.0 if kind == "stairs_up" else -5.0) * tile * u
+    return tuple(t.reshape(B * L, H * 64).contiguous() for t in (q, k, v))
+
+
+# ---- SwiGLU of the F32 engine (swiglu_f32_kernel): mid = silu(g) u = g / (1 + exp(-g)) u.  exp, the add, the division and the
+# product round once each: a few 2^-24 of |mid|; where exp(-g) overflows float32 (g < -88.7) the kernel gives 0 for a true
+# |silu(g)| < 2^-122: covered by 2^-24 |u|.  bar = SWIGLU_COEF 2^-24 |mid| + 2^-24 |u|.
+# SWIGLU_COEF = 4 x the largest needed coefficient of torch's float32 silu(g) * u on swiglu_case's rows, rounded up to a power
+# of two.  Measured on the CPU: 2.39 -> 4 x 2.39 = 9.6 -> 16.
+SWIGLU_COEF = 16.0
+SWIGLU_G = (-100.0, -20.0, 0.0, 20.0, 100.0)
+
+
+def swiglu_case(M: int, FH: int, seed: int) -> torch.Tensor:
+    """gu float32 [M, 2 FH] = [gate | up]: gates N(0, 3), the first columns of every row at -100, -20, 0, 20, 100 (as far as
+    FH reaches); ups N(0, 1) over three decades."""
+    g = torch.Generator().manual_seed(seed)
+    gate = 3 * torch.randn(M, FH, generator=g)
+    n = min(FH, len(SWIGLU_G))
+    gate[:, :n] = torch.tensor(SWIGLU_G[:n])
+    up = torch.randn(M, FH, generator=g) * 10 ** torch.randint(-1, 2, (M, FH), generator=g).float()
+    return torch.cat([gate, up], 1).contiguous()
+
+
+def swiglu_ref64(gu: torch.Tensor):
+    """-> (ref, unit = 2^-24 |ref|, floor = 2^-24 |u|) float64; bar = SWIGLU_COEF unit + floor."""
+    FH = gu.shape[1] // 2
+    g, u = gu[:, :FH].double(), gu[:, FH:].double()
+    ref = g * torch.sigmoid(g) * u
+    return ref, F32_EPS * ref.abs(), F32_EPS * u.abs()
+
+
+def swiglu_needed_coef(got, ref, unit, floor) -> float:
+    over = ((got.double() - ref).abs() - floor).clamp(min=0)
+    return float(torch.where(over == 0, torch.zeros_like(over), over / unit).max())
