@@ -65,6 +65,7 @@ EXPORTS = [
     "esmdiff_lddt_pairs",
     "esmdiff_flex_pair_msf", "esmdiff_flex_fit", "esmdiff_flex_moments",
     "esmdiff_dssp",
+    "esmdiff_contact_map", "esmdiff_native_contacts",
     "esmdiff_describe_gemm_choice", "esmdiff_gemm_workspace_floats",
     "esmdiff_dim6_to_backbone", "esmdiff_plddt_mean", "esmdiff_pair_features", "esmdiff_pae_tm",
     "esmdiff_decoder_set_pair_chunk_bytes",
@@ -76,6 +77,7 @@ EXPORTS = [
 LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
 DSSP_MAX_L = 4096                            # ESMDIFF_DSSP_MAX_L
 TM_MAX_L = 1280                              # ESMDIFF_TM_MAX_L
+CONTACT_MAX_L, CONTACT_TILE, CONTACT_MAX_CHUNKS = 4096, 64, 256    # ESMDIFF_CONTACT_MAX_L, ESMDIFF_CONTACT_TILE, ESMDIFF_CONTACT_MAX_CHUNKS
 
 CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
@@ -86,6 +88,30 @@ def flex_pair_slots(n: int) -> int:
     """ESMDIFF_FLEX_PAIR_SLOTS: the partial sums esmdiff_flex_pair_msf keeps per residue (12 bytes each, in the caller's scratch)."""
     rows = (n + 1) // 2
     return 4 * rows * min(16, max(1, 2048 // rows))
+
+
+def contact_pair_tiles(L: int) -> int:
+    """ESMDIFF_CONTACT_PAIR_TILES: the 64 x 64 tiles on and above the diagonal of the L x L maps."""
+    tiles = (L + CONTACT_TILE - 1) // CONTACT_TILE
+    return tiles * (tiles + 1) // 2
+
+
+def contact_chunk_frames(n: int, L: int) -> int:
+    """ESMDIFF_CONTACT_CHUNK_FRAMES: the consecutive frames esmdiff_contact_map adds in one chunk."""
+    cap = min(CONTACT_MAX_CHUNKS, max(1, 1024 // contact_pair_tiles(L)))
+    return max(16, (n + cap - 1) // cap)
+
+
+def contact_chunks(n: int, L: int) -> int:
+    """ESMDIFF_CONTACT_CHUNKS: the chunks esmdiff_contact_map cuts n frames into; its sums add them in increasing index."""
+    frames = contact_chunk_frames(n, L)
+    return (n + frames - 1) // frames
+
+
+def contact_scratch_bytes(n: int, L: int) -> int:
+    """ESMDIFF_CONTACT_SCRATCH_BYTES: the scratch esmdiff_contact_map needs (none with one chunk)."""
+    chunks = contact_chunks(n, L)
+    return 0 if chunks == 1 else chunks * contact_pair_tiles(L) * CONTACT_TILE * CONTACT_TILE * 24
 
 
 def lib_path() -> Path:
@@ -171,6 +197,8 @@ def lib():
     L.esmdiff_flex_fit.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.esmdiff_flex_moments.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.esmdiff_dssp.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.esmdiff_contact_map.argtypes = [vp, i32, i32, vp, f64, i32, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
+    L.esmdiff_native_contacts.argtypes = [vp, i32, vp, i32, i32, vp, vp, f64, i32, f64, f64, vp, vp, vp, vp, vp, vp]
     L.esmdiff_encoder_create.argtypes = [i32] * 9 + [ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.esmdiff_encoder_destroy.argtypes = [vp]
     L.esmdiff_encoder_destroy.restype = None

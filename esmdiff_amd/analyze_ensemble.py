@@ -2,6 +2,7 @@
 
     python -m esmdiff_amd.analyze_ensemble --samples <multi-MODEL pdb> --targets a.pdb [b.pdb ...] --output <dir> [--max_models 100]
                                            [--lddt] [--plddt_scale 1.0] [--flex] [--pca_components 3] [--dssp]
+                                           [--contacts] [--contact_cutoff 8.0] [--contact_min_sep 3]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
@@ -23,7 +24,13 @@ samples' eight-state strings, counts (L, 8), the three-state propensity (helix, 
 string and the agreement of the samples with it (q3 per sample, q3_mean, q3_best, best_model, per_residue) and, with exactly two
 targets, switch_residues: the residues whose three-state class differs between the two, with the ensemble's share in each target's
 class — the secondary-structure counterpart of ResFlex.  Samples and targets are read again as N / CA / C with the carbonyl O inferred
-on both alike; the samples' prolines donate no hydrogen bond."""
+on both alike; the samples' prolines donate no hydrogen bond.
+--contacts adds a "contacts" block (esmdiff_amd/contacts.py, csrc/contacts.hip): the parameters (cutoff, min_separation, and the
+convention lam = 1.2, beta = 5 of Q), the ensemble's contacts as a sparse list [a, b, frequency, mean_distance] of the pairs a < b in
+contact in at least one sample (--contact_cutoff Angstrom between CA atoms, |a - b| >= --contact_min_sep), the internal scaling
+profile (separation, rms_distance) and its Flory exponent, per target the number of its contacts and every sample's hard and soft
+fraction of native contacts (q, q_soft, q_mean, q_soft_mean, q_best, best_model), q_ens (the mean of q_best) and, with exactly two
+targets, contact_switches: the contacts formed in one target only, with the samples' frequency of each."""
 from __future__ import annotations
 
 import argparse
@@ -32,7 +39,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import ensemble, flexibility, secondary
+from . import contacts, ensemble, flexibility, secondary
 from .pdbio import load_coords, read_pdb_backbone, read_pdb_bfactors
 
 
@@ -90,8 +97,8 @@ def dssp_report(samples_path, target_paths, keep=None) -> dict:
     return secondary.report(secondary.dssp(backbones, sequence), [secondary.dssp(t, sequence) for t in targets])
 
 
-def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0,
-            flex: bool = False, pca_components: int = 3, dssp: bool = False) -> dict:
+def load_ca(samples_path, target_paths, max_models: int = 100, seed: int = 0):
+    """-> the analysed samples (n, L, 3), the targets [(L, 3)], the number of models in the file and the positions of the analysed ones."""
     samples = load_coords(Path(samples_path), max_n_model=None, verbose=False)
     n_all, keep = len(samples), np.arange(len(samples))
     if len(samples) > max_models:
@@ -101,6 +108,18 @@ def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, ld
     for p, t in zip(target_paths, targets):
         if t.shape[0] != samples.shape[1]:
             raise ValueError(f"{p} has {t.shape[0]} residues, the samples {samples.shape[1]}: the correspondence is residue to residue")
+    return samples, targets, n_all, keep
+
+
+def contacts_report(samples_path, target_paths, max_models: int = 100, seed: int = 0, cutoff: float = 8.0, min_sep: int = 3) -> dict:
+    """The --contacts block, on the samples analyze() takes for the same max_models and seed."""
+    samples, targets, _, _ = load_ca(samples_path, target_paths, max_models, seed)
+    return contacts.report(samples, np.stack(targets), cutoff, min_sep)
+
+
+def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0,
+            flex: bool = False, pca_components: int = 3, dssp: bool = False) -> dict:
+    samples, targets, n_all, keep = load_ca(samples_path, target_paths, max_models, seed)
     if len(targets) == 2:
         report = ensemble.apo_report(samples, targets[0], targets[1])
     else:
@@ -135,6 +154,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--flex", action="store_true", help="add the mean structure, RMSF, pairwise RMSF, PCA and the ResFlex correlations")
     ap.add_argument("--pca_components", type=int, default=3, help="modes of the --flex PCA")
     ap.add_argument("--dssp", action="store_true", help="add the DSSP states, the three-state propensities and the agreement with the targets")
+    ap.add_argument("--contacts", action="store_true", help="add the contact map, the fractions of native contacts Q and the scaling profile")
+    ap.add_argument("--contact_cutoff", type=float, default=8.0, help="CA-CA distance below which a pair is a contact (Angstrom)")
+    ap.add_argument("--contact_min_sep", type=int, default=3, help="the smallest sequence separation |a - b| of a contact")
     return ap
 
 
@@ -142,6 +164,8 @@ def main(argv=None) -> Path:
     args = parser().parse_args(argv)
     report = analyze(args.samples, args.targets, args.max_models, args.seed, args.lddt, args.plddt_scale, args.flex, args.pca_components,
                      args.dssp)
+    if args.contacts:
+        report["contacts"] = contacts_report(args.samples, args.targets, args.max_models, args.seed, args.contact_cutoff, args.contact_min_sep)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

@@ -1,5 +1,5 @@
 """The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
-csrc/cluster.hip, csrc/flex.hip and csrc/dssp.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip and csrc/contacts.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
 on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
 host-facing layers above it.
 Row blocks are contiguous slices (A[r0:r1]): a slice carries its own pointer, dtype and shape.  There is no CPU fallback."""
@@ -143,6 +143,43 @@ def dssp(X, mask, no_donor, counts: bool = True):
     code = N.lib().esmdiff_dssp(_p(X), n, L, _p(mask), _p(no_donor), _p(ss), _p(table), _p(acceptor), _p(energy), _stream())
     _check("esmdiff_dssp", code, invalid=lambda: f"esmdiff_dssp: invalid argument: L = {L} (1 to {N.DSSP_MAX_L} residues)")
     return ss, table, acceptor, energy
+
+
+def contact_map(X, mask, cutoff: float, min_sep: int, sums: bool = True):
+    """One esmdiff_contact_map call: X f64 (n, L, 3), mask u8 (n, L) or None -> valid i32 (L, L), count i32 (L, L), and with `sums`
+    sum_d, sum_d2 f64 (L, L) (else None, and never allocated).  The (n, L, L) distances are never stored: the scratch holds
+    N.contact_chunks(n, L) partial tiles per tile of the triangle, and nothing when that is one chunk."""
+    assert X.dim() == 3 and X.shape[-1] == 3 and X.dtype == torch.float64, f"f64 (n, L, 3) coordinates, got {X.dtype} {tuple(X.shape)}"
+    n, L = X.shape[:2]
+    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    valid, count = _new((L, L), torch.int32), _new((L, L), torch.int32)
+    sum_d, sum_d2 = (_new((L, L)), _new((L, L))) if sums else (None, None)
+    size = N.contact_scratch_bytes(n, L) if 2 <= L <= N.CONTACT_MAX_L and n >= 1 else 0
+    scratch = _new((size // 8,)) if size else None
+    code = N.lib().esmdiff_contact_map(_p(X), n, L, _p(mask), float(cutoff), int(min_sep), _p(valid), _p(count), _p(sum_d), _p(sum_d2),
+                                       _p(scratch), size, _stream())
+    _check("esmdiff_contact_map", code,
+           capacity=lambda: f"esmdiff_contact_map: L = {L} is beyond the kernel's limit ({N.CONTACT_MAX_L} residues); there is no slow path",
+           invalid=lambda: f"esmdiff_contact_map: invalid argument: n = {n} (at least 1), L = {L} (at least 2), min_sep = {min_sep} "
+                           f"(at least 1), cutoff = {cutoff} (not NaN)")
+    return valid, count, sum_d, sum_d2
+
+
+def native_contacts(A, B, ma, mb, cutoff: float, min_sep: int, lam: float, beta: float, per_residue: bool = False, soft: bool = True):
+    """One esmdiff_native_contacts launch -> kept i32 (n, m), total i32 (m,), kept_res i32 (n, m, L) and total_res i32 (m, L) with
+    per_residue, q_soft f64 (n, m) with soft (else None, and never allocated)."""
+    n, m, L = _sizes(A, B)
+    kept, total = _new((n, m), torch.int32), _new((m,), torch.int32)
+    kept_res, total_res = (_new((n, m, L), torch.int32), _new((m, L), torch.int32)) if per_residue else (None, None)
+    q_soft = _new((n, m)) if soft else None
+    code = N.lib().esmdiff_native_contacts(_p(A), n, _p(B), m, L, _p(ma), _p(mb), float(cutoff), int(min_sep), float(lam), float(beta),
+                                           _p(kept), _p(total), _p(kept_res), _p(total_res), _p(q_soft), _stream())
+    _check("esmdiff_native_contacts", code,
+           capacity=lambda: f"esmdiff_native_contacts: L = {L} is beyond the kernel's limit ({N.CONTACT_MAX_L} residues: a model is "
+                            f"staged in LDS); there is no slow path",
+           invalid=lambda: f"esmdiff_native_contacts: invalid argument: L = {L} (at least 2), min_sep = {min_sep} (at least 1), "
+                           f"cutoff = {cutoff}, lam = {lam}, beta = {beta} (not NaN)")
+    return kept, total, kept_res, total_res, q_soft
 
 
 def adjacency(n: int) -> torch.Tensor:

@@ -628,6 +628,68 @@ int esmdiff_flex_moments(const double* X, int32_t n, int32_t L, const uint8_t* m
 int esmdiff_dssp(const double* X, int32_t n, int32_t L, const uint8_t* mask, const uint8_t* no_donor, uint8_t* ss, int32_t* counts,
                  int32_t* acceptor, double* energy, void* stream);
 
+/* Contacts of CA traces (float64 coordinates, device pointers in and out; each call synchronises `stream`): DESIGN.md §3.23, held to
+ * the numpy restatement tests/contacts_ref.py.  (An addition; the ABI number stays.)  A distance is sqrt((dx dx + dy dy) + dz dz) in
+ * float64, correctly rounded square root, no FMA contraction, so every comparison falls as numpy's does.  No float atomics.  Every
+ * element of every output that is not NULL is written; the caller zeroes nothing.  L > ESMDIFF_CONTACT_MAX_L returns
+ * ESMDIFF_E_CAPACITY, any other bad argument ESMDIFF_E_INVALID, before anything is launched.
+ *
+ * esmdiff_contact_map: an ensemble X f64 [n, L, 3] reduced over its frames into L x L maps.  mask u8 [n, L] or NULL (all given): a
+ * masked coordinate is never read; a residue whose coordinate is NaN counts as masked in that frame.  For every pair with
+ * |a - b| >= min_sep (min_sep >= 1), with V the frames in which both residues are valid:
+ *   valid  i32 [L, L]            |V|
+ *   count  i32 [L, L]            the number of frames of V with d(a, b) < cutoff (strict)
+ *   sum_d  f64 [L, L] (or NULL)  the sum over V of d(a, b)
+ *   sum_d2 f64 [L, L] (or NULL)  the sum over V of (dx dx + dy dy) + dz dz, the square root's own argument
+ * (sum_d and sum_d2 are given or NULL together.)  All maps are symmetric and 0 where |a - b| < min_sep.
+ * THE ORDER OF THE TWO SUMS is a function of (n, L) alone.  The frames are cut into C = ESMDIFF_CONTACT_CHUNKS(n, L) chunks of
+ * F = ESMDIFF_CONTACT_CHUNK_FRAMES(n, L) consecutive frames (the last one may be shorter, none is empty).  Inside a chunk the frames
+ * are added one after another in increasing index, starting from the first; a frame in which the pair is not valid adds nothing.  The
+ * chunk sums are then added in increasing chunk index, starting from chunk 0's.  So two runs are bit-identical on any device, and
+ * tests/contacts_ref.py follows the order bit for bit.  C is chosen so that (pair tiles x C) fills the machine: at most
+ * ESMDIFF_CONTACT_MAX_CHUNKS for short chains with many frames, 1 from L = 1985 on, where the 64 x 64 tiles of the triangle alone do.
+ * scratch: ESMDIFF_CONTACT_SCRATCH_BYTES(n, L) bytes on the device, 8-byte aligned, need not be zeroed (the chunks' partial tiles);
+ * 0 bytes — scratch may be NULL — when there is one chunk.  A smaller scratch_bytes returns ESMDIFF_E_CAPACITY.
+ *
+ * esmdiff_native_contacts: every model A f64 [n, L, 3] against every native B f64 [m, L, 3], laid out as esmdiff_lddt_pairs (B == NULL:
+ * A against itself, m ignored, maskB = maskA; maskA u8 [n, L] / maskB u8 [m, L] or NULL).  The native contact set of native j is
+ *   C_j = {(a, b) ordered : |a - b| >= min_sep, maskB[j, a] and maskB[j, b], d0 = |B[j, a] - B[j, b]| < cutoff}   (strict)
+ *   total     i32 [m]               |C_j|
+ *   kept      i32 [n, m]            the number of (a, b) in C_j with maskA[i, a], maskA[i, b] and d_i(a, b) < lambda d0 (strict;
+ *                                   lambda d0 is one float64 product): a pair whose model residue is missing keeps nothing and
+ *                                   stays in `total`
+ *   total_res i32 [m, L] (or NULL), kept_res i32 [n, m, L] (or NULL)   the same per residue a, as in esmdiff_lddt_pairs
+ *   q_soft    f64 [n, m] (or NULL)  the sum over C_j of 1 / (1 + exp(beta (d_i(a, b) - lambda d0))) (Best, Hummer & Eaton 2013); a
+ *                                   pair whose model residue is missing adds 0
+ * Q = kept / total, soft Q = q_soft / total: the caller divides.  The order of the q_soft sum is a function of L alone (csrc/contacts.hip
+ * states it: per row a its contacts in increasing b dealt to 64 lane sums, an xor butterfly, the rows a = w, w + 8 ... added per wave w,
+ * the eight wave sums as a fixed tree), so two runs are bit-identical.  L > ESMDIFF_CONTACT_MAX_L (one model of the longest chain, 96 KiB
+ * of float64 planes, has to fit in LDS) returns ESMDIFF_E_CAPACITY. */
+#define ESMDIFF_CONTACT_MAX_L 4096
+#define ESMDIFF_CONTACT_TILE 64
+#define ESMDIFF_CONTACT_MAX_CHUNKS 256
+#define ESMDIFF_CONTACT_TILES(L) (((L) + ESMDIFF_CONTACT_TILE - 1) / ESMDIFF_CONTACT_TILE)
+#define ESMDIFF_CONTACT_PAIR_TILES(L) ((int64_t)ESMDIFF_CONTACT_TILES(L) * (ESMDIFF_CONTACT_TILES(L) + 1) / 2)
+/* the most chunks a chain of L residues is ever cut into: 1024 workgroups wanted */
+#define ESMDIFF_CONTACT_CHUNK_CAP(L)                                            \
+  (1024 / ESMDIFF_CONTACT_PAIR_TILES(L) < 1 ? (int64_t)1                        \
+   : (1024 / ESMDIFF_CONTACT_PAIR_TILES(L) > ESMDIFF_CONTACT_MAX_CHUNKS ? (int64_t)ESMDIFF_CONTACT_MAX_CHUNKS \
+                                                                       : 1024 / ESMDIFF_CONTACT_PAIR_TILES(L)))
+/* frames per chunk: at least 16 */
+#define ESMDIFF_CONTACT_CHUNK_FRAMES(n, L)                                      \
+  ((((n) + ESMDIFF_CONTACT_CHUNK_CAP(L) - 1) / ESMDIFF_CONTACT_CHUNK_CAP(L)) < 16 ? (int64_t)16 \
+   : (((n) + ESMDIFF_CONTACT_CHUNK_CAP(L) - 1) / ESMDIFF_CONTACT_CHUNK_CAP(L)))
+#define ESMDIFF_CONTACT_CHUNKS(n, L) (((n) + ESMDIFF_CONTACT_CHUNK_FRAMES(n, L) - 1) / ESMDIFF_CONTACT_CHUNK_FRAMES(n, L))
+/* per chunk and pair tile 64 x 64 cells of two f64 and two i32; nothing with one chunk */
+#define ESMDIFF_CONTACT_SCRATCH_BYTES(n, L)                                     \
+  (ESMDIFF_CONTACT_CHUNKS(n, L) == 1 ? (int64_t)0                               \
+   : ESMDIFF_CONTACT_CHUNKS(n, L) * ESMDIFF_CONTACT_PAIR_TILES(L) * ESMDIFF_CONTACT_TILE * ESMDIFF_CONTACT_TILE * 24)
+int esmdiff_contact_map(const double* X, int32_t n, int32_t L, const uint8_t* mask, double cutoff, int32_t min_sep, int32_t* valid,
+                        int32_t* count, double* sum_d, double* sum_d2, void* scratch, int64_t scratch_bytes, void* stream);
+int esmdiff_native_contacts(const double* A, int32_t n, const double* B, int32_t m, int32_t L, const uint8_t* maskA,
+                            const uint8_t* maskB, double cutoff, int32_t min_sep, double lambda, double beta, int32_t* kept,
+                            int32_t* total, int32_t* kept_res, int32_t* total_res, double* q_soft, void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
