@@ -66,6 +66,7 @@ EXPORTS = [
     "esmdiff_flex_pair_msf", "esmdiff_flex_fit", "esmdiff_flex_moments",
     "esmdiff_dssp",
     "esmdiff_contact_map", "esmdiff_native_contacts",
+    "esmdiff_backbone_torsions", "esmdiff_ramachandran",
     "esmdiff_describe_gemm_choice", "esmdiff_gemm_workspace_floats",
     "esmdiff_dim6_to_backbone", "esmdiff_plddt_mean", "esmdiff_pair_features", "esmdiff_pae_tm",
     "esmdiff_decoder_set_pair_chunk_bytes",
@@ -78,6 +79,7 @@ LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_
 DSSP_MAX_L = 4096                            # ESMDIFF_DSSP_MAX_L
 TM_MAX_L = 1280                              # ESMDIFF_TM_MAX_L
 CONTACT_MAX_L, CONTACT_TILE, CONTACT_MAX_CHUNKS = 4096, 64, 256    # ESMDIFF_CONTACT_MAX_L, ESMDIFF_CONTACT_TILE, ESMDIFF_CONTACT_MAX_CHUNKS
+RAMA_MAX_BINS = 72                           # ESMDIFF_RAMA_MAX_BINS
 
 CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
@@ -112,6 +114,24 @@ def contact_scratch_bytes(n: int, L: int) -> int:
     """ESMDIFF_CONTACT_SCRATCH_BYTES: the scratch esmdiff_contact_map needs (none with one chunk)."""
     chunks = contact_chunks(n, L)
     return 0 if chunks == 1 else chunks * contact_pair_tiles(L) * CONTACT_TILE * CONTACT_TILE * 24
+
+
+def rama_chunk_frames(n: int, L: int) -> int:
+    """ESMDIFF_RAMA_CHUNK_FRAMES: the consecutive frames esmdiff_ramachandran adds in one chunk."""
+    cap = min(1024, max(1, 65536 // L))
+    return max(16, (n + cap - 1) // cap)
+
+
+def rama_chunks(n: int, L: int) -> int:
+    """ESMDIFF_RAMA_CHUNKS: the chunks esmdiff_ramachandran cuts n frames into; its sums add them in increasing index."""
+    frames = rama_chunk_frames(n, L)
+    return (n + frames - 1) // frames
+
+
+def rama_scratch_bytes(n: int, L: int) -> int:
+    """ESMDIFF_RAMA_SCRATCH_BYTES: the scratch esmdiff_ramachandran's sums need (none with one chunk)."""
+    chunks = rama_chunks(n, L)
+    return 0 if chunks <= 1 else chunks * L * 48
 
 
 def lib_path() -> Path:
@@ -199,6 +219,8 @@ def lib():
     L.esmdiff_dssp.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.esmdiff_contact_map.argtypes = [vp, i32, i32, vp, f64, i32, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_native_contacts.argtypes = [vp, i32, vp, i32, i32, vp, vp, f64, i32, f64, f64, vp, vp, vp, vp, vp, vp]
+    L.esmdiff_backbone_torsions.argtypes = [vp, i32, i32, i32, vp, f64, vp, vp, vp, vp, vp]
+    L.esmdiff_ramachandran.argtypes = [vp, i32, i32, i32, vp, f64, i32, vp, vp, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_encoder_create.argtypes = [i32] * 9 + [ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.esmdiff_encoder_destroy.argtypes = [vp]
     L.esmdiff_encoder_destroy.restype = None

@@ -3,6 +3,7 @@
     python -m esmdiff_amd.analyze_ensemble --samples <multi-MODEL pdb> --targets a.pdb [b.pdb ...] --output <dir> [--max_models 100]
                                            [--lddt] [--plddt_scale 1.0] [--flex] [--pca_components 3] [--dssp]
                                            [--contacts] [--contact_cutoff 8.0] [--contact_min_sep 3]
+                                           [--torsions] [--rama_bins 36]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
@@ -30,7 +31,16 @@ convention lam = 1.2, beta = 5 of Q), the ensemble's contacts as a sparse list [
 contact in at least one sample (--contact_cutoff Angstrom between CA atoms, |a - b| >= --contact_min_sep), the internal scaling
 profile (separation, rms_distance) and its Flory exponent, per target the number of its contacts and every sample's hard and soft
 fraction of native contacts (q, q_soft, q_mean, q_soft_mean, q_best, best_model), q_ens (the mean of q_best) and, with exactly two
-targets, contact_switches: the contacts formed in one target only, with the samples' frequency of each."""
+targets, contact_switches: the contacts formed in one target only, with the samples' frequency of each.
+--torsions adds a "torsions" block (esmdiff_amd/torsions.py, csrc/torsions.hip): the parameters (bins, break_distance, the region
+rectangles), per residue the counts (phi, psi, both, omega defined, cis), the circular means and variances of phi / psi / omega, the
+region propensities (alpha, beta, ppII, left, other: a stated convention), the cis fraction and the entropy of the --rama_bins x
+--rama_bins Ramachandran map, the geometry summary of the samples (bond lengths and angles against ideal values, outliers per sample),
+per target its phi / psi, its region string and the agreement of the samples with it (share per sample, share_mean, share_best,
+best_model, per_residue), js_ramachandran: the Jensen-Shannon distance between the samples' maps and those of the targets taken
+together as one ensemble (thin with few targets: each target fills one cell per residue) and, with exactly two targets,
+region_switches: the residues whose region differs between the two, with the samples' share in each.  Samples and targets are read
+again as N / CA / C backbones, on the analysed subset."""
 from __future__ import annotations
 
 import argparse
@@ -39,7 +49,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import contacts, ensemble, flexibility, secondary
+from . import contacts, ensemble, flexibility, secondary, torsions
 from .pdbio import load_coords, read_pdb_backbone, read_pdb_bfactors
 
 
@@ -95,6 +105,15 @@ def dssp_report(samples_path, target_paths, keep=None) -> dict:
             sequence = None
     targets = [load_coords(Path(p), max_n_model=None, ca_only=False, verbose=False)[0] for p in target_paths]
     return secondary.report(secondary.dssp(backbones, sequence), [secondary.dssp(t, sequence) for t in targets])
+
+
+def torsions_report(samples_path, target_paths, keep=None, bins: int = 36) -> dict:
+    """The --torsions block: the files read again as N / CA / C backbones (`keep`: the analysed subset of the samples' models)."""
+    backbones = load_coords(Path(samples_path), max_n_model=None, ca_only=False, verbose=False)
+    if keep is not None:
+        backbones = backbones[keep]
+    targets = [load_coords(Path(p), max_n_model=None, ca_only=False, verbose=False)[0] for p in target_paths]
+    return torsions.report(backbones, targets, bins)
 
 
 def load_ca(samples_path, target_paths, max_models: int = 100, seed: int = 0):
@@ -157,6 +176,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--contacts", action="store_true", help="add the contact map, the fractions of native contacts Q and the scaling profile")
     ap.add_argument("--contact_cutoff", type=float, default=8.0, help="CA-CA distance below which a pair is a contact (Angstrom)")
     ap.add_argument("--contact_min_sep", type=int, default=3, help="the smallest sequence separation |a - b| of a contact")
+    ap.add_argument("--torsions", action="store_true", help="add the backbone torsions: Ramachandran statistics, regions, geometry, agreement with the targets")
+    ap.add_argument("--rama_bins", type=int, default=36, help="cells per axis of the --torsions Ramachandran maps (1 to 72)")
     return ap
 
 
@@ -166,6 +187,9 @@ def main(argv=None) -> Path:
                      args.dssp)
     if args.contacts:
         report["contacts"] = contacts_report(args.samples, args.targets, args.max_models, args.seed, args.contact_cutoff, args.contact_min_sep)
+    if args.torsions:
+        keep = load_ca(args.samples, args.targets, args.max_models, args.seed)[3]
+        report["torsions"] = torsions_report(args.samples, args.targets, keep, args.rama_bins)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

@@ -1,5 +1,5 @@
 """The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
-csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip and csrc/contacts.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip and csrc/torsions.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
 on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
 host-facing layers above it.
 Row blocks are contiguous slices (A[r0:r1]): a slice carries its own pointer, dtype and shape.  There is no CPU fallback."""
@@ -180,6 +180,49 @@ def native_contacts(A, B, ma, mb, cutoff: float, min_sep: int, lam: float, beta:
            invalid=lambda: f"esmdiff_native_contacts: invalid argument: L = {L} (at least 2), min_sep = {min_sep} (at least 1), "
                            f"cutoff = {cutoff}, lam = {lam}, beta = {beta} (not NaN)")
     return kept, total, kept_res, total_res, q_soft
+
+
+def _backbone_sizes(X, mask):
+    assert X.dim() == 4 and X.shape[2] in (3, 4) and X.shape[3] == 3 and X.dtype == torch.float64, \
+        f"f64 (n, L, 3 or 4, 3) backbones, got {X.dtype} {tuple(X.shape)}"
+    n, L, atoms = X.shape[:3]
+    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    return n, L, atoms
+
+
+def backbone_torsions(X, mask, break_distance: float, geometry: bool = False):
+    """One esmdiff_backbone_torsions call: X f64 (n, L, 3 or 4, 3) N / CA / C (/ O, never read), mask u8 (n, L) or None -> phi, psi,
+    omega f64 (n, L) in radians (NaN where undefined) and, with `geometry`, geom f64 (n, L, 6) (else None, and never allocated)."""
+    n, L, atoms = _backbone_sizes(X, mask)
+    phi, psi, omega = _new((n, L)), _new((n, L)), _new((n, L))
+    geom = _new((n, L, 6)) if geometry else None
+    code = N.lib().esmdiff_backbone_torsions(_p(X), n, L, atoms, _p(mask), float(break_distance), _p(phi), _p(psi), _p(omega), _p(geom),
+                                             _stream())
+    _check("esmdiff_backbone_torsions", code,
+           invalid=lambda: f"esmdiff_backbone_torsions: invalid argument: L = {L} (at least 1), break_distance = {break_distance} "
+                           f"(positive and finite)",
+           capacity=lambda: f"esmdiff_backbone_torsions: {n} x {L} residues are more than one launch takes; pass the structures in blocks")
+    return phi, psi, omega, geom
+
+
+def ramachandran(X, mask, break_distance: float, bins: int, sums: bool = True):
+    """One esmdiff_ramachandran call: X and mask as backbone_torsions takes them -> hist i32 (L, bins, bins), counts i32 (L, 5) and, with
+    `sums`, sums f64 (L, 6) (else None, and never allocated).  No (n, L) angle array exists: the scratch holds N.rama_chunks(n, L)
+    partial sums per residue, and nothing when that is one chunk."""
+    n, L, atoms = _backbone_sizes(X, mask)
+    bins = int(bins)
+    ok = 1 <= bins <= N.RAMA_MAX_BINS
+    hist, counts = _new((L, bins, bins) if ok else (1,), torch.int32), _new((L, 5), torch.int32)     # not ok: the entry refuses, writes nothing
+    out = _new((L, 6)) if sums else None
+    size = N.rama_scratch_bytes(n, L) if sums else 0
+    scratch = _new((size // 8,)) if size else None
+    code = N.lib().esmdiff_ramachandran(_p(X), n, L, atoms, _p(mask), float(break_distance), bins, _p(hist), _p(counts), _p(out),
+                                        _p(scratch), size, _stream())
+    _check("esmdiff_ramachandran", code,
+           capacity=lambda: f"esmdiff_ramachandran: bins = {bins} is beyond the kernel's limit ({N.RAMA_MAX_BINS} per axis)",
+           invalid=lambda: f"esmdiff_ramachandran: invalid argument: L = {L} (at least 1), bins = {bins} (at least 1), "
+                           f"break_distance = {break_distance} (positive and finite)")
+    return hist, counts, out
 
 
 def adjacency(n: int) -> torch.Tensor:

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ESMDIFF_ABI_VERSION 8   /* 8: + esmdiff_q_xt, esmdiff_nelbo_rows, esmdiff_nelbo_eval (additions only, the number stays); + esmdiff_gibbs_step_rows, esmdiff_set_lengths (an addition); esmdiff_logit_error_stats writes 8 floats per row and takes all_columns; 7: + esmdiff_ddpm_step_rows, esmdiff_logit_error_stats (additions only); 6: + esmdiff_ddpm_step_margin, esmdiff_forward_logits_sigmas, esmdiff_set_small_batch_splitk */
+#define ESMDIFF_ABI_VERSION 8   /* 8: + esmdiff_backbone_torsions, esmdiff_ramachandran (additions, the number stays); + esmdiff_q_xt, esmdiff_nelbo_rows, esmdiff_nelbo_eval (additions only, the number stays); + esmdiff_gibbs_step_rows, esmdiff_set_lengths (an addition); esmdiff_logit_error_stats writes 8 floats per row and takes all_columns; 7: + esmdiff_ddpm_step_rows, esmdiff_logit_error_stats (additions only); 6: + esmdiff_ddpm_step_margin, esmdiff_forward_logits_sigmas, esmdiff_set_small_batch_splitk */
 
 /* structure-track vocabulary: esm constants mirrored at model.py:380-381 */
 #define ESMDIFF_VOCAB 4101
@@ -689,6 +689,59 @@ int esmdiff_contact_map(const double* X, int32_t n, int32_t L, const uint8_t* ma
 int esmdiff_native_contacts(const double* A, int32_t n, const double* B, int32_t m, int32_t L, const uint8_t* maskA,
                             const uint8_t* maskB, double cutoff, int32_t min_sep, double lambda, double beta, int32_t* kept,
                             int32_t* total, int32_t* kept_res, int32_t* total_res, double* q_soft, void* stream);
+
+/* Backbone torsions phi / psi / omega and the Ramachandran maps of an ensemble (float64 coordinates, device pointers in and out; each
+ * call synchronises `stream`): DESIGN.md §3.24, held to the numpy restatement tests/torsions_ref.py.  (An addition; the ABI number
+ * stays.)  X f64 [n, L, atoms, 3] with atoms = 3 (N, CA, C) or 4 (N, CA, C, O; O is never read: the array made for esmdiff_dssp goes
+ * in as it is); mask u8 [n, L] or NULL (all given).  No FMA contraction, correctly rounded square root and division.
+ *   present   residue i is not masked and its N, CA and C are all finite; the coordinates of any other residue influence nothing
+ *   link      i -> i + 1: both present and |C_i - N_{i+1}| <= break_distance, the length sqrt((dx dx + dy dy) + dz dz)
+ *   dihedral  of p0 .. p3: b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2, n1 = b1 x b2, n2 = b2 x b3, x = n1 . n2,
+ *             y = sqrt(b2 . b2) (b1 . n2), angle = atan2(y, x), with a x b = (ay bz - az by, az bx - ax bz, ax by - ay bx) and
+ *             a . b = (ax bx + ay by) + az bz; undefined when x == 0 and y == 0 or either is not finite
+ *   phi_i = dihedral(C_{i-1}, N_i, CA_i, C_i) needs the link i - 1 -> i; psi_i = dihedral(N_i, CA_i, C_i, N_{i+1}) and
+ *   omega_i = dihedral(CA_i, C_i, N_{i+1}, CA_{i+1}) need the link i -> i + 1
+ * n < 0, L < 1, atoms not 3 or 4, a break_distance that is not positive and finite or a required pointer that is NULL return
+ * ESMDIFF_E_INVALID and touch nothing.  There is no limit on L.
+ *
+ * esmdiff_backbone_torsions: phi, psi, omega f64 [n, L] in radians, NaN where undefined; geom f64 [n, L, 6] or NULL: the lengths
+ * N-CA, CA-C, C_i-N_{i+1} (sqrt of the dot product above) and the angles N-CA-C, CA_i-C_i-N_{i+1}, C_i-N_{i+1}-CA_{i+1} in radians
+ * as atan2(|u x v|, u . v) of the two bonds leaving the middle atom, NaN where a residue they touch is not present (the two that reach
+ * into i + 1 do not need the link).  Every element of every output that is not NULL is written; a structure's rows do not depend on
+ * its batch; n == 0 succeeds.
+ *
+ * esmdiff_ramachandran: the ensemble reduced over its frames, from the coordinates; memory is O(L bins^2) whatever n is.
+ *   hist   i32 [L, bins, bins]  the frames in which phi_i and psi_i are both defined, at [i][bin of phi][bin of psi]; the bin of an
+ *                               angle is b = (int)floor((angle * 57.29577951308232 + 180.0) / (360.0 / bins)), b -= bins where
+ *                               b >= bins (+180 degrees is bin 0), b += bins where b < 0 (it is not, with atan2 in [-pi, pi])
+ *   counts i32 [L, 5]           the frames with phi defined, psi defined, both, omega defined, and cis (omega defined and x > 0)
+ *   sums   f64 [L, 6] or NULL   the sums of cos phi, sin phi, cos psi, sin psi, cos omega, sin omega over the frames in which that
+ *                               angle is defined, with cos = x / r, sin = y / r, r = sqrt(x x + y y): no trigonometric function
+ * bins is 1 .. ESMDIFF_RAMA_MAX_BINS, beyond that ESMDIFF_E_CAPACITY.  Every output is written, the caller zeroes nothing; n == 0
+ * gives zeros.  Integer atomics only.  x and y are computed by the function esmdiff_backbone_torsions uses: the same bits.
+ * THE ORDER OF THE SUMS is a function of (n, L) alone.  The frames are cut into C = ESMDIFF_RAMA_CHUNKS(n, L) chunks of
+ * F = ESMDIFF_RAMA_CHUNK_FRAMES(n, L) consecutive frames (the last one may be shorter, none is empty).  Inside a chunk a residue's
+ * terms are added one after another in increasing frame index, starting from the first defined one (a chunk without one has the sum
+ * +0.0).  The chunk sums are then added in increasing chunk index, starting from chunk 0's.  So two runs are bit-identical, and
+ * tests/torsions_ref.py follows the order bit for bit.
+ * scratch: ESMDIFF_RAMA_SCRATCH_BYTES(n, L) bytes on the device, 8-byte aligned, need not be zeroed (C x L x 6 chunk sums); not
+ * read — it may be NULL — when there is one chunk or sums is NULL.  A smaller scratch_bytes returns ESMDIFF_E_CAPACITY. */
+#define ESMDIFF_RAMA_MAX_BINS 72
+/* the most chunks a chain of L residues is ever cut into: one thread per (residue, chunk), about 65536 of them wanted */
+#define ESMDIFF_RAMA_CHUNK_CAP(L) \
+  (65536 / (int64_t)(L) < 1 ? (int64_t)1 : (65536 / (int64_t)(L) > 1024 ? (int64_t)1024 : 65536 / (int64_t)(L)))
+/* frames per chunk: at least 16 */
+#define ESMDIFF_RAMA_CHUNK_FRAMES(n, L)                                   \
+  ((((n) + ESMDIFF_RAMA_CHUNK_CAP(L) - 1) / ESMDIFF_RAMA_CHUNK_CAP(L)) < 16 ? (int64_t)16 \
+   : (((n) + ESMDIFF_RAMA_CHUNK_CAP(L) - 1) / ESMDIFF_RAMA_CHUNK_CAP(L)))
+#define ESMDIFF_RAMA_CHUNKS(n, L) (((n) + ESMDIFF_RAMA_CHUNK_FRAMES(n, L) - 1) / ESMDIFF_RAMA_CHUNK_FRAMES(n, L))
+#define ESMDIFF_RAMA_SCRATCH_BYTES(n, L) \
+  (ESMDIFF_RAMA_CHUNKS(n, L) <= 1 ? (int64_t)0 : ESMDIFF_RAMA_CHUNKS(n, L) * (int64_t)(L) * 48)
+int esmdiff_backbone_torsions(const double* X, int32_t n, int32_t L, int32_t atoms, const uint8_t* mask, double break_distance,
+                              double* phi, double* psi, double* omega, double* geom, void* stream);
+int esmdiff_ramachandran(const double* X, int32_t n, int32_t L, int32_t atoms, const uint8_t* mask, double break_distance,
+                         int32_t bins, int32_t* hist, int32_t* counts, double* sums, void* scratch, int64_t scratch_bytes,
+                         void* stream);
 
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
