@@ -74,6 +74,8 @@ EXPORTS = [
     "esmdiff_forward_logits_needed", "esmdiff_get_tail_rows",
     "esmdiff_layernorm_f32rows", "esmdiff_swiglu_f32", "esmdiff_qk_norm_rope_f32", "esmdiff_v_split",
     "esmdiff_attention_f32_parts", "esmdiff_gemm_split_k", "esmdiff_get_attention_scales",
+    "esmdiff_convert_weight", "esmdiff_interleave_swiglu", "esmdiff_split_weight_from", "esmdiff_weight_rownorm_max",
+    "esmdiff_embed_rows", "esmdiff_gather_table_rows", "esmdiff_sigma_mlp", "esmdiff_layernorm_16in",
 ]
 LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
 DSSP_MAX_L = 4096                            # ESMDIFF_DSSP_MAX_L
@@ -257,6 +259,14 @@ def lib():
     L.esmdiff_attention_f32_parts.argtypes = [vp, vp, vp, i32, f32, f32, vp, ctypes.POINTER(i32), i32, i32, i32, vp]
     L.esmdiff_gemm_split_k.argtypes = [vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, f32, vp]
     L.esmdiff_get_attention_scales.argtypes = [vp, i32, c_f32p, c_f32p]
+    L.esmdiff_convert_weight.argtypes = [vp, i32, vp, i32, ctypes.c_int64, vp]
+    L.esmdiff_interleave_swiglu.argtypes = [vp, i32, vp, i32, i32, i32, vp]
+    L.esmdiff_split_weight_from.argtypes = [vp, i32, vp, i32, i32, i32, i32, c_f32p]
+    L.esmdiff_weight_rownorm_max.argtypes = [vp, i32, ctypes.c_int64, i32, i32, c_f32p]
+    L.esmdiff_embed_rows.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
+    L.esmdiff_gather_table_rows.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    L.esmdiff_sigma_mlp.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    L.esmdiff_layernorm_16in.argtypes = [i32, vp, vp, vp, vp, i32, i32, vp]
     for n in EXPORTS:
         if n not in ("esmdiff_engine_destroy", "esmdiff_last_error", "esmdiff_encoder_destroy", "esmdiff_encoder_last_error"):
             getattr(L, n).restype = ctypes.c_int

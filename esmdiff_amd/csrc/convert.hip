@@ -6,11 +6,17 @@
 namespace ed {
 
 // f32 -> the TU's 16-bit operand type, round to nearest even (ed_half.h: bf16, or f16 — saturating — in the ed16 build)
-__device__ __forceinline__ uint32_t cv_f2bf(float a) { return ed_f2h(a); }
+// A NaN weight stays NaN in both builds: ed_sat's v_med3_f32 turned every NaN into +-65504 (tests/test_gpu_loader.py), so the f16 build steps around it; +-inf still saturate.
+__device__ __forceinline__ uint32_t cv_f2bf(float a) {
+#ifdef ED_F16
+  if (a != a) return 0x7e00u;   // the f16 quiet NaN
+#endif
+  return ed_f2h(a);
+}
 // a source tensor tagged ESMDIFF_BF16 is bfloat16 in BOTH builds (the caller's dtype, not the engine's)
 __device__ __forceinline__ uint32_t cv_bf2h(bf16_t b) {
 #ifdef ED_F16
-  return ed_f2h(__uint_as_float((uint32_t)b << 16));
+  return cv_f2bf(__uint_as_float((uint32_t)b << 16));
 #else
   return b;
 #endif

@@ -42,17 +42,27 @@ int esmdiff_split_rows(const float* src, int32_t ld, void* a2, float* rs, int32_
   return launched(nullptr, s, "split_rows");
 }
 
-int esmdiff_split_weight(const float* src, void* w2, int32_t N, int32_t N_pad, int32_t K, float* inv_scale_out) {
-  if (!src || !w2 || !inv_scale_out || N <= 0 || N_pad < N || N_pad % 256 || K <= 0 || K % 128) return ESMDIFF_E_INVALID;
+int esmdiff_split_weight_from(const void* src, int32_t src_dtype, void* w3, int32_t N, int32_t N_pad, int32_t K, int32_t interleave_h,
+                              float* inv_scale_out) {
+  if (!src || !w3 || !inv_scale_out || N <= 0 || N_pad < N || N_pad % 256 || K <= 0 || K % 128) return ESMDIFF_E_INVALID;
+  if (src_dtype != ESMDIFF_F32 && src_dtype != ESMDIFF_BF16)
+    return fail(nullptr, ESMDIFF_E_INVALID, "split_weight: src_dtype %d (0 f32, 1 bf16)", src_dtype);
+  if (interleave_h != 0 && (interleave_h < 0 || interleave_h % 32 || N != 2 * interleave_h))
+    return fail(nullptr, ESMDIFF_E_INVALID, "split_weight: interleave_h=%d must be 0, or a multiple of 32 with N (%d) == 2 interleave_h",
+                interleave_h, N);
   uint32_t* bits = nullptr;
   if (hipMalloc(&bits, 4) != hipSuccess) return fail(nullptr, ESMDIFF_E_HIP, "split_weight: hipMalloc failed");
   hipError_t s = hipSuccess;
-  if (N_pad > N) s = hipMemset((uint16_t*)w2 + (size_t)N * 3 * K, 0, (size_t)(N_pad - N) * 3 * K * 2);
-  if (s == hipSuccess) s = split_weight(src, ESMDIFF_F32, (uint16_t*)w2, N, K, bits, inv_scale_out);
+  if (N_pad > N) s = hipMemset((uint16_t*)w3 + (size_t)N * 3 * K, 0, (size_t)(N_pad - N) * 3 * K * 2);
+  if (s == hipSuccess) s = split_weight(src, src_dtype, (uint16_t*)w3, N, K, bits, inv_scale_out, interleave_h);
   if (s == hipSuccess) s = hipDeviceSynchronize();
   hipFree(bits);
   if (s != hipSuccess) return fail(nullptr, ESMDIFF_E_HIP, "split_weight: %s", hipGetErrorString(s));
   return 0;
+}
+
+int esmdiff_split_weight(const float* src, void* w2, int32_t N, int32_t N_pad, int32_t K, float* inv_scale_out) {
+  return esmdiff_split_weight_from(src, ESMDIFF_F32, w2, N, N_pad, K, 0, inv_scale_out);
 }
 
 int esmdiff_gemm_split(const void* a2, const float* rs, const void* w2, float w_inv_scale, float* out, const float* bias,
@@ -396,6 +406,80 @@ int esmdiff_decoder_set_pair_chunk_bytes(esmdiff_engine* e, int64_t bytes) {
   if (bytes < 0) return fail(e, ESMDIFF_E_INVALID, "pair chunk bytes %lld: positive, or 0 for the default", (long long)bytes);
   e->pair_chunk_bytes = bytes ? bytes : kDefaultPairChunkBytes;
   return 0;
+}
+
+// ---- weight conversion at create and the input stage, one launcher at a time (synchronous) ----
+static bool weight_dtype_ok(int32_t dt) { return dt == ESMDIFF_F32 || dt == ESMDIFF_BF16; }
+
+int esmdiff_convert_weight(const void* src, int32_t src_dtype, void* dst, int32_t dst_kind, int64_t n, void* stream) {
+  if (!src || !dst) return fail(nullptr, ESMDIFF_E_INVALID, "convert_weight: null pointer");
+  if (!weight_dtype_ok(src_dtype) || dst_kind < 0 || dst_kind > 2)
+    return fail(nullptr, ESMDIFF_E_INVALID, "convert_weight: src_dtype %d (0 f32, 1 bf16), dst_kind %d (0 bf16, 1 f16, 2 f32)", src_dtype, dst_kind);
+  if (n <= 0) return fail(nullptr, ESMDIFF_E_INVALID, "convert_weight: n=%lld must be positive", (long long)n);
+  const hipStream_t st = (hipStream_t)stream;
+  if (dst_kind == 2) return launched_sync(launch_to_f32(src, src_dtype, (float*)dst, n, st), st, "to_f32");
+  return launched_sync(ED_KN(dst_kind == 1, launch_to_bf16(src, src_dtype, (bf16_t*)dst, n, st)), st, "to_bf16");
+}
+
+int esmdiff_interleave_swiglu(const void* src, int32_t src_dtype, void* dst, int32_t dst_kind, int32_t H, int32_t K, void* stream) {
+  if (!src || !dst) return fail(nullptr, ESMDIFF_E_INVALID, "interleave_swiglu: null pointer");
+  if (!weight_dtype_ok(src_dtype) || (dst_kind != 0 && dst_kind != 1))
+    return fail(nullptr, ESMDIFF_E_INVALID, "interleave_swiglu: src_dtype %d (0 f32, 1 bf16), dst_kind %d (0 bf16, 1 f16)", src_dtype, dst_kind);
+  if (H <= 0 || H % 32 || K <= 0)
+    return fail(nullptr, ESMDIFF_E_INVALID, "interleave_swiglu: H=%d a positive multiple of 32, K=%d positive", H, K);
+  const hipStream_t st = (hipStream_t)stream;
+  return launched_sync(ED_KN(dst_kind == 1, launch_interleave_swiglu(src, src_dtype, (bf16_t*)dst, H, K, st)), st, "interleave_swiglu");
+}
+
+int esmdiff_weight_rownorm_max(const void* src, int32_t src_dtype, int64_t r0, int32_t rows, int32_t K, float* out) {
+  if (!src || !out) return fail(nullptr, ESMDIFF_E_INVALID, "weight_rownorm_max: null pointer");
+  if (!weight_dtype_ok(src_dtype) || r0 < 0 || rows <= 0 || K <= 0)
+    return fail(nullptr, ESMDIFF_E_INVALID, "weight_rownorm_max: src_dtype %d (0 f32, 1 bf16), r0=%lld >= 0, rows=%d and K=%d positive", src_dtype,
+                (long long)r0, rows, K);
+  uint32_t* bits = nullptr;
+  if (hipMalloc(&bits, 4) != hipSuccess) return fail(nullptr, ESMDIFF_E_HIP, "weight_rownorm_max: hipMalloc failed");
+  hipError_t s = weight_rownorm_max(src, src_dtype, r0, rows, K, bits, out);
+  if (s == hipSuccess) s = hipDeviceSynchronize();
+  hipFree(bits);
+  return launched(nullptr, s, "weight_rownorm_max");
+}
+
+int esmdiff_embed_rows(const int64_t* seq, const int64_t* xtok, const float* e_seq, const float* e_struct, const float* cvec,
+                       const float* cond, int32_t cond_stride, float* out, int32_t B, int32_t L, int32_t D, void* stream) {
+  if (!seq || !xtok || !e_seq || !e_struct || !cvec || !out) return fail(nullptr, ESMDIFF_E_INVALID, "embed_rows: null pointer");
+  if (B <= 0 || L <= 0 || (int64_t)B * L > 0x7fffffffll || D <= 0 || D % 4)
+    return fail(nullptr, ESMDIFF_E_INVALID, "embed_rows: B=%d L=%d must be positive with B * L < 2^31, D=%d a positive multiple of 4", B, L, D);
+  if (cond_stride < 0 || cond_stride % 4)
+    return fail(nullptr, ESMDIFF_E_INVALID, "embed_rows: cond_stride=%d must be a non-negative multiple of 4", cond_stride);
+  const hipStream_t st = (hipStream_t)stream;
+  return launched_sync(launch_embed(seq, xtok, e_seq, e_struct, cvec, cond, out, B, L, D, st, cond_stride), st, "embed");
+}
+
+int esmdiff_gather_table_rows(const int64_t* tok, const float* table, float* out, int32_t M, int32_t D, int32_t n_rows, void* stream) {
+  if (!tok || !table || !out) return fail(nullptr, ESMDIFF_E_INVALID, "gather_table_rows: null pointer");
+  if (M <= 0 || D <= 0 || D % 4 || n_rows <= 0)
+    return fail(nullptr, ESMDIFF_E_INVALID, "gather_table_rows: M=%d and n_rows=%d must be positive, D=%d a positive multiple of 4", M, n_rows, D);
+  const hipStream_t st = (hipStream_t)stream;
+  return launched_sync(launch_gather_rows(tok, table, out, M, D, n_rows, st), st, "gather_rows");
+}
+
+int esmdiff_sigma_mlp(const float* t_freq, const float* w1, const float* b1, const float* w2, const float* b2, float* hidden,
+                      float* cond, int32_t F, int32_t D, int32_t n_sigma, void* stream) {
+  if (!t_freq || !w1 || !b1 || !w2 || !b2 || !hidden || !cond) return fail(nullptr, ESMDIFF_E_INVALID, "sigma_mlp: null pointer");
+  if (F <= 0 || D <= 0 || n_sigma <= 0 || n_sigma > 65535)
+    return fail(nullptr, ESMDIFF_E_INVALID, "sigma_mlp: F=%d and D=%d must be positive, n_sigma=%d in 1 .. 65535", F, D, n_sigma);
+  const hipStream_t st = (hipStream_t)stream;
+  return launched_sync(launch_sigma_mlp(t_freq, w1, b1, w2, b2, hidden, cond, F, D, st, n_sigma), st, "sigma_mlp");
+}
+
+int esmdiff_layernorm_16in(int32_t dtype, const void* x16, const float* w, const float* b, void* y16, int32_t M, int32_t D,
+                           void* stream) {
+  if (!x16 || !w || !y16) return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_16in: null pointer");
+  if (dtype != 0 && dtype != 1) return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_16in: dtype %d (0 bf16, 1 f16)", dtype);
+  if (M <= 0 || D <= 0 || D % 4 || D > 2048)
+    return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_16in: M=%d must be positive, D=%d a positive multiple of 4 up to 2048", M, D);
+  const hipStream_t st = (hipStream_t)stream;
+  return launched_sync(ED_KN(dtype == 1, launch_layernorm_bf16_in((const bf16_t*)x16, w, b, (bf16_t*)y16, M, D, st)), st, "layernorm_16in");
 }
 
 }  // extern "C"

@@ -1040,6 +1040,124 @@ def attention_f32_parts(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: in
     return ctx
 
 
+# ---- weight conversion at create and the input stage, one launcher at a time (include/esmdiff_hip_test.h) ----
+_SRC_DT = {torch.float32: N.DT_F32, torch.bfloat16: N.DT_BF16}
+_DST_KIND = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}
+
+
+def _weight_src(t: torch.Tensor) -> int:
+    assert t.dtype in _SRC_DT and t.is_cuda and t.is_contiguous(), (t.dtype, t.device)
+    return _SRC_DT[t.dtype]
+
+
+def convert_weight(src: torch.Tensor, dst_dtype: torch.dtype, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """esmdiff_convert_weight: a float32 / bfloat16 tensor -> bfloat16 (round to nearest even), float16 (saturating) or float32
+    (exact), as the create entries convert a state dict.  out: a buffer of dst_dtype with at least src.numel() elements (the
+    elements beyond are not written)."""
+    _require_gpu()
+    n = src.numel()
+    if out is None:
+        out = torch.empty(src.shape, dtype=dst_dtype, device=src.device)
+    assert out.dtype == dst_dtype and out.is_contiguous() and out.numel() >= n
+    N.check(N.lib().esmdiff_convert_weight(_ptr(src), _weight_src(src), _ptr(out), _DST_KIND[dst_dtype], n, _stream()))
+    return out
+
+
+def interleave_swiglu(src: torch.Tensor, dst_dtype: torch.dtype) -> torch.Tensor:
+    """esmdiff_interleave_swiglu: the FFN-up weight [2H, K] = [gate rows | up rows] (float32 / bfloat16) -> [2H, K] bfloat16 /
+    float16 with rows in blocks of 32, [gate 32t..32t+31 | up 32t..32t+31]."""
+    _require_gpu()
+    H2, K = src.shape
+    assert dst_dtype in (torch.bfloat16, torch.float16) and H2 % 2 == 0
+    out = torch.empty(H2, K, dtype=dst_dtype, device=src.device)
+    N.check(N.lib().esmdiff_interleave_swiglu(_ptr(src), _weight_src(src), _ptr(out), _DST_KIND[dst_dtype], H2 // 2, K, _stream()))
+    return out
+
+
+def split_weight_from(W: torch.Tensor, *, interleave_h: int = 0, n_pad: Optional[int] = None):
+    """esmdiff_split_weight_from: split_weight from a float32 or bfloat16 [N, K] weight, rows interleaved as interleave_swiglu
+    interleaves them when interleave_h = N / 2 -> (w3 f16 [n_pad, 3K], 2^-k).  The padding rows come back as zeros."""
+    _require_gpu()
+    Nn, K = W.shape
+    n_pad = (Nn + 255) // 256 * 256 if n_pad is None else n_pad
+    w3 = torch.full((n_pad, 3 * K), float("nan"), dtype=torch.float16, device=W.device)
+    inv = ctypes.c_float(0)
+    torch.cuda.synchronize()
+    N.check(N.lib().esmdiff_split_weight_from(_ptr(W), _weight_src(W), _ptr(w3), Nn, n_pad, K, int(interleave_h), ctypes.byref(inv)))
+    return w3, float(inv.value)
+
+
+def weight_rownorm_max(W: torch.Tensor, r0: int, rows: int) -> float:
+    """esmdiff_weight_rownorm_max: the largest L2 norm among rows r0 .. r0 + rows - 1 of a float32 / bfloat16 [*, K] weight, as
+    an F32_SPLIT create measures the q / k / v thirds of a qkv weight."""
+    _require_gpu()
+    R, K = W.shape
+    assert 0 <= r0 and 0 < rows and r0 + rows <= R
+    out = ctypes.c_float(0)
+    torch.cuda.synchronize()
+    N.check(N.lib().esmdiff_weight_rownorm_max(_ptr(W), _weight_src(W), int(r0), int(rows), K, ctypes.byref(out)))
+    return float(out.value)
+
+
+def embed_rows(seq: torch.Tensor, xtok: torch.Tensor, e_seq: torch.Tensor, e_struct: torch.Tensor, cvec: torch.Tensor,
+               cond: Optional[torch.Tensor], cond_stride: int) -> torch.Tensor:
+    """esmdiff_embed_rows: the input stage alone.  seq, xtok int64 [B, L] (any values: the kernel clamps), e_seq f32 [64, D],
+    e_struct f32 [4101, D], cvec f32 [D], cond f32 (one vector with cond_stride 0, [B, cond_stride] otherwise) or None
+    -> f32 [B, L, D]."""
+    _require_gpu()
+    B, L = seq.shape
+    D = cvec.numel()
+    for t in (seq, xtok):
+        assert t.dtype == torch.int64 and t.shape == (B, L) and t.is_contiguous() and t.is_cuda
+    assert e_seq.shape == (64, D) and e_struct.shape == (STRUCTURE_VOCAB, D)
+    for t in (e_seq, e_struct, cvec) + (() if cond is None else (cond,)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda
+    assert cond is None or cond.numel() >= (B - 1) * cond_stride + D
+    out = torch.full((B, L, D), float("nan"), dtype=torch.float32, device=seq.device)
+    N.check(N.lib().esmdiff_embed_rows(_ptr(seq), _ptr(xtok), _ptr(e_seq), _ptr(e_struct), _ptr(cvec), _ptr(cond), int(cond_stride),
+                                       _ptr(out), B, L, D, _stream()))
+    return out
+
+
+def gather_table_rows(tok: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """esmdiff_gather_table_rows: out f32 [M, D] = table[tok clamped to the table's rows] (the structure decoder's embedding)."""
+    _require_gpu()
+    n_rows, D = table.shape
+    assert tok.dtype == torch.int64 and tok.dim() == 1 and tok.is_contiguous() and tok.is_cuda
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.is_cuda
+    out = torch.full((tok.numel(), D), float("nan"), dtype=torch.float32, device=tok.device)
+    N.check(N.lib().esmdiff_gather_table_rows(_ptr(tok), _ptr(table), _ptr(out), tok.numel(), D, n_rows, _stream()))
+    return out
+
+
+def sigma_mlp(t_freq: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor):
+    """esmdiff_sigma_mlp: t_freq f32 [n_sigma, F] -> (hidden = silu(w1 t_freq + b1), cond = w2 hidden + b2), f32 [n_sigma, D]."""
+    _require_gpu()
+    n_sigma, F = t_freq.shape
+    D = w1.shape[0]
+    assert w1.shape == (D, F) and w2.shape == (D, D) and b1.shape == (D,) and b2.shape == (D,)
+    for t in (t_freq, w1, b1, w2, b2):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda
+    hidden = torch.full((n_sigma, D), float("nan"), dtype=torch.float32, device=t_freq.device)
+    cond = torch.full((n_sigma, D), float("nan"), dtype=torch.float32, device=t_freq.device)
+    N.check(N.lib().esmdiff_sigma_mlp(_ptr(t_freq), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(hidden), _ptr(cond), F, D, n_sigma,
+                                      _stream()))
+    return hidden, cond
+
+
+def layernorm_16in(x16: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
+    """esmdiff_layernorm_16in: LayerNorm of a bfloat16 / float16 [M, D] input in that type's build (the head's LayerNorm after
+    GELU, the pLDDT and pairwise heads' LayerNorms) -> the same type."""
+    _require_gpu()
+    M, D = x16.shape
+    assert x16.dtype in (torch.bfloat16, torch.float16) and x16.is_contiguous() and x16.is_cuda
+    assert w.dtype == torch.float32 and w.numel() == D and (b is None or (b.dtype == torch.float32 and b.numel() == D))
+    y = torch.full((M, D), float("nan"), dtype=x16.dtype, device=x16.device)
+    N.check(N.lib().esmdiff_layernorm_16in(0 if x16.dtype == torch.bfloat16 else 1, _ptr(x16), _ptr(w), _ptr(b), _ptr(y), M, D,
+                                           _stream()))
+    return y
+
+
 def gemm_bf16_timed(A, W, out, epilogue, iters=20, bias=None, alpha=1.0) -> float:
     """Average milliseconds per launch, HIP events on the launch stream (esmdiff_gemm_bf16_timed, the one entry point
     that -DED_DEBUG adds to the library; that flag changes nothing else)."""

@@ -197,7 +197,40 @@ int esmdiff_gemm_split_k(const void* a3, const float* rs, const void* w3, float 
                          int32_t N, int32_t K, int32_t S, float div, void* stream);
 int esmdiff_get_attention_scales(esmdiff_engine* eng, int32_t layer, float* qk_out, float* v_out);
 
-/* ---- Needed rows (ESMDIFF_OPT_NEEDED_ROWS, esmdiff_ddpm_sample in esmdiff_hip.h), one forward at a time ----
+/* ---- Weight conversion at create (csrc/convert.hip, csrc/gemm_split.hip, csrc/attention_split.hip: what every create's loader,
+ * csrc/engine_weights.hip, runs on each tensor of the state dict) and the input stage (csrc/embed.hip, csrc/norm.hip), one launcher
+ * at a time (tests/test_gpu_loader.py).  All synchronous; every argument is checked before the first HIP call
+ * (ESMDIFF_E_INVALID, nothing touched).  src_dtype: esmdiff_dtype of the source tensor (ESMDIFF_F32 / ESMDIFF_BF16). ----
+ *   esmdiff_convert_weight      src [n] -> dst [n].  dst_kind 0: bfloat16, round to nearest even (ed::launch_to_bf16); 1: IEEE half,
+ *                               saturating at +-65504, NaN stays NaN (ed16::launch_to_bf16); 2: float32, exact (launch_to_f32)
+ *   esmdiff_interleave_swiglu   src [2H, K] (gate rows 0..H-1, up rows H..2H-1) -> dst [2H, K] of dst_kind 0 / 1 as above, rows in
+ *                               blocks of 32: [gate 32t..32t+31 | up 32t..32t+31]; H % 32 == 0
+ *   esmdiff_split_weight_from   esmdiff_split_weight from either source dtype, with the FFN-up row interleave: interleave_h = 0, or
+ *                               interleave_h % 32 == 0 and N == 2 interleave_h (rows permuted as esmdiff_interleave_swiglu permutes)
+ *   esmdiff_weight_rownorm_max  *out [host] = the largest L2 norm among rows r0 .. r0 + rows - 1 of src [*, K]
+ *   esmdiff_embed_rows          out f32 [B*L, D] = ((e_seq[s] + e_struct[t']) + cvec) + cond[(row / L) * cond_stride ..]: seq, xtok i64
+ *                               [B*L]; s = seq clamped to 0..63; t' = xtok with -1 -> MASK, clamped to 0..4100, then BOS / PAD / EOS /
+ *                               chainbreak where s is 0 / 1 / 2 / 31; e_seq f32 [64, D], e_struct f32 [4101, D], cvec f32 [D]; cond f32 or
+ *                               NULL, cond_stride >= 0 a multiple of 4 (0: one vector for every sample); D % 4 == 0
+ *   esmdiff_gather_table_rows   out f32 [M, D] = table[tok clamped to 0 .. n_rows-1]; tok i64 [M]; D % 4 == 0
+ *   esmdiff_sigma_mlp           hidden f32 [n_sigma, D] = silu(w1 [D, F] . t_freq [n_sigma, F] + b1), cond f32 [n_sigma, D] =
+ *                               w2 [D, D] . hidden + b2, float32
+ *   esmdiff_layernorm_16in      y16 [M, D] = LayerNorm(x16 [M, D]) * w (+ b; may be NULL), eps 1e-5: launch_layernorm_bf16_in.
+ *                               dtype 0: bf16 in and out (namespace ed), 1: f16 (ed16).  D % 4 == 0, D <= 2048 */
+int esmdiff_convert_weight(const void* src, int32_t src_dtype, void* dst, int32_t dst_kind, int64_t n, void* stream);
+int esmdiff_interleave_swiglu(const void* src, int32_t src_dtype, void* dst, int32_t dst_kind, int32_t H, int32_t K, void* stream);
+int esmdiff_split_weight_from(const void* src, int32_t src_dtype, void* w3, int32_t N, int32_t N_pad, int32_t K, int32_t interleave_h,
+                              float* inv_scale_out);
+int esmdiff_weight_rownorm_max(const void* src, int32_t src_dtype, int64_t r0, int32_t rows, int32_t K, float* out);
+int esmdiff_embed_rows(const int64_t* seq, const int64_t* xtok, const float* e_seq, const float* e_struct, const float* cvec,
+                       const float* cond, int32_t cond_stride, float* out, int32_t B, int32_t L, int32_t D, void* stream);
+int esmdiff_gather_table_rows(const int64_t* tok, const float* table, float* out, int32_t M, int32_t D, int32_t n_rows, void* stream);
+int esmdiff_sigma_mlp(const float* t_freq, const float* w1, const float* b1, const float* w2, const float* b2, float* hidden,
+                      float* cond, int32_t F, int32_t D, int32_t n_sigma, void* stream);
+int esmdiff_layernorm_16in(int32_t dtype, const void* x16, const float* w, const float* b, void* y16, int32_t M, int32_t D,
+                           void* stream);
+
+/* ---- Needed rows (ESMDIFF_OPT_NEEDED_ROWS,esmdiff_ddpm_sample in esmdiff_hip.h), one forward at a time ----
  *   esmdiff_forward_logits_needed  esmdiff_forward_logits as a forward of esmdiff_ddpm_sample runs it: the rows to keep are
  *                                  derived from x (those that hold MASK), and logits_out is written on those rows only — every
  *                                  other row of logits_out is left as it was.  Bit-identical to esmdiff_forward_logits on the rows
