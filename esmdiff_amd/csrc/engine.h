@@ -120,6 +120,14 @@ struct esmdiff_engine : eng::Owner {
   uint8_t* g_rowflag = nullptr;   // esmdiff_gibbs_step_rows with bounds: per-row report, reduced per prompt by the select kernel
   float* g_rowgap = nullptr;
   int ld_logits = 0, tfreq_rows = 0;
+  // [host] arrays of esmdiff_ddpm_sample (t_freq) and esmdiff_gibbs_sample (n_unmask_table) are copied here before their upload, so that
+  // the caller's array is consumed before the entry returns wherever it lives (an upload from PINNED memory would read it later).
+  // The upload from this pageable copy is staged by the runtime before hipMemcpyAsync returns: MEASURED, not promised by HIP, at
+  // 108 bytes, 4 KB and 1 MB (T = 1025), where the entry also came back without waiting (tests/test_gpu_stream_order.py).  A
+  // runtime that read the copy later would see the next call's assign() rewrite it; esmdiff_ddpm_sample's final-skip branch, which
+  // uploads from a local vector, does not rely on the staging and waits for the stream instead.
+  std::vector<float> tfreq_host;
+  std::vector<int32_t> nunmask_host;
   int sigma_rows = 1;   // sinusoid rows the next forward reads: 1 (all samples share sigma) or B (esmdiff_forward_logits_sigmas)
   // two-stream forward: the second half of a large batch runs on `side`, forked/joined with events
   std::vector<hipStream_t> side;

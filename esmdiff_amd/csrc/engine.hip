@@ -133,7 +133,10 @@ int esmdiff_set_gibbs_options(esmdiff_engine* e, int32_t strategy, const int32_t
   }
   if (n_set >= 4096) return fail(e, ESMDIFF_E_INVALID, "invalid_ids leaves no id to draw");
   HIP_TRY(e, hipSetDevice(e->device));
-  HIP_TRY(e, hipMemcpy(e->g_inv_mask, mask, sizeof mask, hipMemcpyHostToDevice));   // synchronous: ordered against earlier launches
+  // A blocking copy is ordered against the null stream and blocking streams only: a gibbs step still queued on a caller's
+  // non-blocking stream would read the new mask.  Wait for the device first, as esmdiff_set_lengths does.
+  HIP_TRY(e, hipDeviceSynchronize());
+  HIP_TRY(e, hipMemcpy(e->g_inv_mask, mask, sizeof mask, hipMemcpyHostToDevice));
   e->g_inv_on = n_set > 0;
   e->g_strategy = strategy;
   return 0;

@@ -163,7 +163,10 @@ int esmdiff_ddpm_sample(esmdiff_engine* e, const int64_t* seq, int64_t* x_inout,
   if (int r = check_lens(e, B, L)) return r;
   hipStream_t st = (hipStream_t)stream;
   const int F = e->cfg.freq_dim;
-  if (t_freq) HIP_TRY(e, hipMemcpyAsync(e->tfreq, t_freq, (size_t)(T + 1) * F * sizeof(float), hipMemcpyHostToDevice, st));
+  if (t_freq) {   // through the engine's own host copy: the caller's array is consumed here (engine.h: tfreq_host)
+    e->tfreq_host.assign(t_freq, t_freq + (size_t)(T + 1) * F);
+    HIP_TRY(e, hipMemcpyAsync(e->tfreq, e->tfreq_host.data(), e->tfreq_host.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  }
   Prof p{e, st};
   int shared = 0;
   if (int r = step0_shared_batch(e, seq, x_inout, B, L, st, &shared)) return r;
@@ -267,7 +270,8 @@ int esmdiff_gibbs_sample(esmdiff_engine* e, const int64_t* seq, int64_t* x_inout
   if (int r = check_lens(e, B, L)) return r;
   hipStream_t st = (hipStream_t)stream;
   if (int r = check_gibbs_filter(e, temperature, top_p, nullptr)) return r;
-  HIP_TRY(e, hipMemcpyAsync(e->g_nunmask, n_unmask_table, (size_t)T * B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  e->nunmask_host.assign(n_unmask_table, n_unmask_table + (size_t)T * B);   // the caller's array is consumed here (engine.h)
+  HIP_TRY(e, hipMemcpyAsync(e->g_nunmask, e->nunmask_host.data(), e->nunmask_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
   int shared = 0;
   if (int r = step0_shared_batch(e, seq, x_inout, B, L, st, &shared)) return r;   // (0 with coordinate conditioning)
   for (int i = 0; i < T; ++i) {

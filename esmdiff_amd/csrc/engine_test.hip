@@ -292,7 +292,7 @@ int esmdiff_pae_tm(const float* logits, const int64_t* tokens, float* tm_rows, f
   return launched_sync(launch_pae_tm(logits, tokens, tm_rows, pae, ptm, nb, L, max_bin, st), st, "pae_tm");
 }
 
-// ---- the float32-grade row kernels of F32 / F32_SPLIT engines, one launcher at a time (synchronous) ----
+// ---- the float32-grade row kernels of F32 / F32_SPLIT engines, one launcher at a time, enqueued on the caller's stream ----
 int esmdiff_layernorm_f32rows(const float* x, const float* w, const float* b, int32_t split, int32_t gelu_in, const void* delta,
                               int32_t delta_dtype, void* a3, float* rs, float* y32, int32_t M, int32_t D, void* stream) {
   if (!x || !w) return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_f32rows: null pointer");
@@ -303,13 +303,13 @@ int esmdiff_layernorm_f32rows(const float* x, const float* w, const float* b, in
   if (!split) {
     if (!y32 || gelu_in || delta || a3 || rs)
       return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_f32rows: the f32 kernel writes y32 only and takes neither gelu_in nor delta");
-    return launched_sync(launch_layernorm_f32(x, w, b, y32, M, D, st), st, "layernorm_f32");
+    return launched(nullptr, launch_layernorm_f32(x, w, b, y32, M, D, st), "layernorm_f32");
   }
   if (!a3 || !rs) return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_f32rows: the split kernel needs a3 and rs");
   if ((gelu_in != 0 && gelu_in != 1) || (delta_dtype != 0 && delta_dtype != 1))
     return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_f32rows: gelu_in %d (0 / 1), delta_dtype %d (0 bf16, 1 f16)", gelu_in, delta_dtype);
-  return launched_sync(launch_layernorm_split(x, w, b, (uint16_t*)a3, rs, y32, M, D, gelu_in, st, (const uint16_t*)delta, delta_dtype), st,
-                       "layernorm_split");
+  return launched(nullptr, launch_layernorm_split(x, w, b, (uint16_t*)a3, rs, y32, M, D, gelu_in, st, (const uint16_t*)delta, delta_dtype),
+                  "layernorm_split");
 }
 
 int esmdiff_swiglu_f32(const float* gu, float* mid, int32_t M, int32_t FH, void* stream) {
@@ -317,7 +317,7 @@ int esmdiff_swiglu_f32(const float* gu, float* mid, int32_t M, int32_t FH, void*
   if (M <= 0 || FH <= 0 || FH % 4)
     return fail(nullptr, ESMDIFF_E_INVALID, "swiglu_f32: M=%d must be positive, FH=%d a positive multiple of 4", M, FH);
   const hipStream_t st = (hipStream_t)stream;
-  return launched_sync(launch_swiglu_f32(gu, mid, M, FH, st), st, "swiglu_f32");
+  return launched(nullptr, launch_swiglu_f32(gu, mid, M, FH, st), "swiglu_f32");
 }
 
 int esmdiff_qk_norm_rope_f32(esmdiff_engine* e, const float* qkv, const float* q_ln_w, const float* k_ln_w, int32_t split,
@@ -335,8 +335,7 @@ int esmdiff_qk_norm_rope_f32(esmdiff_engine* e, const float* qkv, const float* q
   const hipError_t s = split ? launch_qk_norm_rope_split(qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, (uint16_t*)q, (uint16_t*)k, B, L, H,
                                                          q_scale, k_scale, st)
                              : launch_qk_norm_rope_f32(qkv, q_ln_w, k_ln_w, e->rope_cos, e->rope_sin, (float*)q, (float*)k, B, L, H, st);
-  const hipError_t s2 = hipStreamSynchronize(st);
-  return launched(e, s == hipSuccess ? s2 : s, split ? "qk_norm_rope_split" : "qk_norm_rope_f32");
+  return launched(e, s, split ? "qk_norm_rope_split" : "qk_norm_rope_f32");
 }
 
 int esmdiff_v_split(const float* qkv, void* v2, int32_t M, int32_t D, float scale, void* stream) {
@@ -345,7 +344,7 @@ int esmdiff_v_split(const float* qkv, void* v2, int32_t M, int32_t D, float scal
     return fail(nullptr, ESMDIFF_E_INVALID, "v_split: M=%d must be positive, D=%d a positive multiple of 4, scale=%g finite and positive", M, D,
                 (double)scale);
   const hipStream_t st = (hipStream_t)stream;
-  return launched_sync(launch_v_split(qkv, (uint16_t*)v2, M, D, scale, st), st, "v_split");
+  return launched(nullptr, launch_v_split(qkv, (uint16_t*)v2, M, D, scale, st), "v_split");
 }
 
 int esmdiff_attention_f32_parts(const void* q, const void* k, const void* v, int32_t split, float qk_scale_product, float v_scale,
@@ -371,9 +370,11 @@ int esmdiff_attention_f32_parts(const void* q, const void* k, const void* v, int
     else
       s = launch_attention_f32((const float*)q, (const float*)k, (const float*)v, ctx, B, L, H, st, dl);
   }
-  const hipError_t s2 = hipStreamSynchronize(st);   // synchronous: the length buffer and the caller's host copy die here
-  if (s == hipSuccess) s = s2;
-  if (dl) hipFree(dl);
+  if (dl) {   // with lengths the call waits: the length buffer and the caller's host copy die here
+    const hipError_t s2 = hipStreamSynchronize(st);
+    if (s == hipSuccess) s = s2;
+    hipFree(dl);
+  }
   return launched(nullptr, s, split ? "attention_split" : "attention_f32");
 }
 
@@ -387,7 +388,7 @@ int esmdiff_gemm_split_k(const void* a3, const float* rs, const void* w3, float 
   const hipStream_t st = (hipStream_t)stream;
   hipError_t s = launch_gemm256w4_splitk((const uint16_t*)a3, (const uint16_t*)w3, w_inv_scale, parts, M, N, K, S, st);
   if (s == hipSuccess) s = launch_splitk_reduce_resid(parts, rs, x, M, N, S, div, st);
-  return launched_sync(s, st, "gemm_split_k");
+  return launched(nullptr, s, "gemm_split_k");
 }
 
 int esmdiff_get_attention_scales(esmdiff_engine* e, int32_t layer, float* qk_out, float* v_out) {
@@ -408,7 +409,7 @@ int esmdiff_decoder_set_pair_chunk_bytes(esmdiff_engine* e, int64_t bytes) {
   return 0;
 }
 
-// ---- weight conversion at create and the input stage, one launcher at a time (synchronous) ----
+// ---- weight conversion at create and the input stage, one launcher at a time, enqueued on the caller's stream ----
 static bool weight_dtype_ok(int32_t dt) { return dt == ESMDIFF_F32 || dt == ESMDIFF_BF16; }
 
 int esmdiff_convert_weight(const void* src, int32_t src_dtype, void* dst, int32_t dst_kind, int64_t n, void* stream) {
@@ -417,8 +418,8 @@ int esmdiff_convert_weight(const void* src, int32_t src_dtype, void* dst, int32_
     return fail(nullptr, ESMDIFF_E_INVALID, "convert_weight: src_dtype %d (0 f32, 1 bf16), dst_kind %d (0 bf16, 1 f16, 2 f32)", src_dtype, dst_kind);
   if (n <= 0) return fail(nullptr, ESMDIFF_E_INVALID, "convert_weight: n=%lld must be positive", (long long)n);
   const hipStream_t st = (hipStream_t)stream;
-  if (dst_kind == 2) return launched_sync(launch_to_f32(src, src_dtype, (float*)dst, n, st), st, "to_f32");
-  return launched_sync(ED_KN(dst_kind == 1, launch_to_bf16(src, src_dtype, (bf16_t*)dst, n, st)), st, "to_bf16");
+  if (dst_kind == 2) return launched(nullptr, launch_to_f32(src, src_dtype, (float*)dst, n, st), "to_f32");
+  return launched(nullptr, ED_KN(dst_kind == 1, launch_to_bf16(src, src_dtype, (bf16_t*)dst, n, st)), "to_bf16");
 }
 
 int esmdiff_interleave_swiglu(const void* src, int32_t src_dtype, void* dst, int32_t dst_kind, int32_t H, int32_t K, void* stream) {
@@ -428,7 +429,7 @@ int esmdiff_interleave_swiglu(const void* src, int32_t src_dtype, void* dst, int
   if (H <= 0 || H % 32 || K <= 0)
     return fail(nullptr, ESMDIFF_E_INVALID, "interleave_swiglu: H=%d a positive multiple of 32, K=%d positive", H, K);
   const hipStream_t st = (hipStream_t)stream;
-  return launched_sync(ED_KN(dst_kind == 1, launch_interleave_swiglu(src, src_dtype, (bf16_t*)dst, H, K, st)), st, "interleave_swiglu");
+  return launched(nullptr, ED_KN(dst_kind == 1, launch_interleave_swiglu(src, src_dtype, (bf16_t*)dst, H, K, st)), "interleave_swiglu");
 }
 
 int esmdiff_weight_rownorm_max(const void* src, int32_t src_dtype, int64_t r0, int32_t rows, int32_t K, float* out) {
@@ -452,7 +453,7 @@ int esmdiff_embed_rows(const int64_t* seq, const int64_t* xtok, const float* e_s
   if (cond_stride < 0 || cond_stride % 4)
     return fail(nullptr, ESMDIFF_E_INVALID, "embed_rows: cond_stride=%d must be a non-negative multiple of 4", cond_stride);
   const hipStream_t st = (hipStream_t)stream;
-  return launched_sync(launch_embed(seq, xtok, e_seq, e_struct, cvec, cond, out, B, L, D, st, cond_stride), st, "embed");
+  return launched(nullptr, launch_embed(seq, xtok, e_seq, e_struct, cvec, cond, out, B, L, D, st, cond_stride), "embed");
 }
 
 int esmdiff_gather_table_rows(const int64_t* tok, const float* table, float* out, int32_t M, int32_t D, int32_t n_rows, void* stream) {
@@ -460,7 +461,7 @@ int esmdiff_gather_table_rows(const int64_t* tok, const float* table, float* out
   if (M <= 0 || D <= 0 || D % 4 || n_rows <= 0)
     return fail(nullptr, ESMDIFF_E_INVALID, "gather_table_rows: M=%d and n_rows=%d must be positive, D=%d a positive multiple of 4", M, n_rows, D);
   const hipStream_t st = (hipStream_t)stream;
-  return launched_sync(launch_gather_rows(tok, table, out, M, D, n_rows, st), st, "gather_rows");
+  return launched(nullptr, launch_gather_rows(tok, table, out, M, D, n_rows, st), "gather_rows");
 }
 
 int esmdiff_sigma_mlp(const float* t_freq, const float* w1, const float* b1, const float* w2, const float* b2, float* hidden,
@@ -469,7 +470,7 @@ int esmdiff_sigma_mlp(const float* t_freq, const float* w1, const float* b1, con
   if (F <= 0 || D <= 0 || n_sigma <= 0 || n_sigma > 65535)
     return fail(nullptr, ESMDIFF_E_INVALID, "sigma_mlp: F=%d and D=%d must be positive, n_sigma=%d in 1 .. 65535", F, D, n_sigma);
   const hipStream_t st = (hipStream_t)stream;
-  return launched_sync(launch_sigma_mlp(t_freq, w1, b1, w2, b2, hidden, cond, F, D, st, n_sigma), st, "sigma_mlp");
+  return launched(nullptr, launch_sigma_mlp(t_freq, w1, b1, w2, b2, hidden, cond, F, D, st, n_sigma), "sigma_mlp");
 }
 
 int esmdiff_layernorm_16in(int32_t dtype, const void* x16, const float* w, const float* b, void* y16, int32_t M, int32_t D,
@@ -479,7 +480,7 @@ int esmdiff_layernorm_16in(int32_t dtype, const void* x16, const float* w, const
   if (M <= 0 || D <= 0 || D % 4 || D > 2048)
     return fail(nullptr, ESMDIFF_E_INVALID, "layernorm_16in: M=%d must be positive, D=%d a positive multiple of 4 up to 2048", M, D);
   const hipStream_t st = (hipStream_t)stream;
-  return launched_sync(ED_KN(dtype == 1, launch_layernorm_bf16_in((const bf16_t*)x16, w, b, (bf16_t*)y16, M, D, st)), st, "layernorm_16in");
+  return launched(nullptr, ED_KN(dtype == 1, launch_layernorm_bf16_in((const bf16_t*)x16, w, b, (bf16_t*)y16, M, D, st)), "layernorm_16in");
 }
 
 }  // extern "C"

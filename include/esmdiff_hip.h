@@ -11,13 +11,21 @@
  * Conventions
  *   ownership  every pointer passed in/out is DEVICE memory owned by the caller
  *              (e.g. a PyTorch-ROCm tensor's data_ptr()) unless marked [host].
+ *              A [host] array, pageable or pinned, is consumed before the entry
+ *              returns: the caller may change or free it then.
  *              The engine owns only its bf16 weight copies and its workspace,
  *              both sized at create time for (max_batch, max_len).
  *   errors     every entry returns int: 0 = ok, <0 = esmdiff_status.  Nothing
  *              throws across the boundary.  esmdiff_last_error() gives the text.
  *   threading  one engine per (process, device); not thread-safe.  All work is
  *              enqueued on the caller's hipStream_t (passed as void*); no entry
- *              synchronises the stream except where stated.
+ *              synchronises the stream except where stated.  The stream may be
+ *              any stream, a non-blocking one included: an entry that takes a
+ *              stream launches nothing on the null stream, and an engine-owned
+ *              side stream is forked from and joined back into the caller's
+ *              (tests/test_gpu_stream_order.py).
+ *              esmdiff_set_lengths and esmdiff_set_gibbs_options, which take no
+ *              stream, wait for the whole device.
  *   dtypes     token ids int64 (the reference's LongTensor), logits float32,
  *              schedule scalars float32 computed by the HOST exactly as
  *              model.py:564-567,584-595 does and passed in.
@@ -362,7 +370,8 @@ int esmdiff_gibbs_step(esmdiff_engine* eng, int64_t* x_inout, const int64_t* seq
  * "random" (a uniformly random k-subset of the masked positions: the k smallest of one Philox uniform per position; needs the
  * rng noise source); invalid_ids [host, n_invalid]: codebook ids that are never drawn — masked after the nucleus cut exactly
  * like the special ids >= 4096.  Applies to every following esmdiff_gibbs_step / esmdiff_gibbs_sample of this engine;
- * (0, NULL, 0) restores the defaults.  Synchronous (a 512-byte upload). */
+ * (0, NULL, 0) restores the defaults.  Takes no stream: it waits for the whole device (hipDeviceSynchronize), so that no gibbs step still
+ * queued on any stream reads the new mask, then uploads 512 bytes with a blocking copy that is complete on return. */
 int esmdiff_set_gibbs_options(esmdiff_engine* eng, int32_t strategy, const int32_t* invalid_ids, int32_t n_invalid);
 
 /* esmdiff_gibbs_step (Philox source) with ONE PARAMETER SET PER PROMPT (ABI 8), and optionally a report of how close the step's
@@ -413,8 +422,9 @@ int esmdiff_set_frames(esmdiff_engine* eng, const float* rot, const float* trans
 /* Ragged batch for the following calls: B samples padded to one L, sample b valid on tokens [0, lens[b]) (lens counts BOS and
  * EOS; each in 3..max_len).  Padding sits at the end of a row and holds the pad ids (sequence 1, structure 4099 = never MASK).
  * A valid position's logits and ids then depend only on its own sample's valid positions: attention masks the padded keys and
- * writes zeros for padded query rows, every other kernel is row-wise.  lens is a HOST array, copied (synchronously) to a device
- * buffer of max_batch entries; NULL clears it.  Stateful like esmdiff_set_frames: while set, esmdiff_forward_logits[_sigmas],
+ * writes zeros for padded query rows, every other kernel is row-wise.  lens is a HOST array, copied to a device buffer of
+ * max_batch entries after a wait for the whole device (hipDeviceSynchronize: the entry takes no stream, and no forward still queued
+ * on any stream may read the new lengths), with a blocking copy that is complete on return; NULL clears it and waits for nothing.  Stateful like esmdiff_set_frames: while set, esmdiff_forward_logits[_sigmas],
  * esmdiff_ddpm_sample, esmdiff_gibbs_sample and the *_step_rows entries refuse (ESMDIFF_E_INVALID) a call whose B differs
  * from the set B or whose L is below a length, step-0 sharing is off, and esmdiff_describe_plan(B) reports
  * "ragged=1 valid_tokens=...".  The GEMMs still run the padded rows. */
@@ -439,7 +449,9 @@ int esmdiff_set_lengths(esmdiff_engine* eng, const int32_t* lens, int32_t B);
  * (/root/reference/slm/models/utils.py:64-76) — softmax over the 64 predicted-aligned-error bins (max bin 31 A) of every
  * token pair, PAE = expected bin centre, pTM = max_i mean_j E[1 / (1 + (e / d0)^2)] over non-special tokens; pairs with
  * BOS/EOS/special tokens carry the uniform-distribution value in `pae`, as esm leaves them.  Only the PAE slice of
- * linear2 is evaluated (the distogram / direction slices are training targets). */
+ * linear2 is evaluated (the distogram / direction slices are training targets).
+ * esmdiff_decoder_decode is enqueued on `stream` like a forward; its one wait: a call with ptm that finds the pairwise head's
+ * workspace too small (the first, or one with more pair rows than any before) synchronises `stream` before it frees and regrows it. */
 int esmdiff_decoder_create(const esmdiff_config* cfg, const esmdiff_weight* table, int32_t n_weights,
                            int32_t device, esmdiff_engine** out);
 int esmdiff_decoder_decode(esmdiff_engine* dec, const int64_t* tokens, float* bb_coords, float* plddt, float* ptm,

@@ -162,8 +162,9 @@ int esmdiff_encoder_nearest_code(const float* z, const float* code, const uint8_
                                  int64_t* tok, void* stream);
 
 /* ---- The float32-grade row kernels between the GEMMs of F32 and F32_SPLIT engines (csrc/strict.hip, csrc/gemm_split.hip,
- * csrc/attention_split.hip), one launcher at a time (tests/test_gpu_f32_rows.py).  All synchronous; every argument is checked
- * before the first HIP call (ESMDIFF_E_INVALID).  f16 buffers are IEEE half bits. ----
+ * csrc/attention_split.hip), one launcher at a time (tests/test_gpu_f32_rows.py).  Enqueued on `stream` without a wait, like the
+ * engine's own entries (esmdiff_attention_f32_parts waits for `stream` when lens is given, for its host array); every argument is
+ * checked before the first HIP call (ESMDIFF_E_INVALID).  f16 buffers are IEEE half bits. ----
  *   esmdiff_layernorm_f32rows  LayerNorm of x f32 [M, D] * w (+ b), eps 1e-5; D % 4 == 0, D <= 2048.
  *                              split 0 (launch_layernorm_f32): y32 f32 [M, D]; gelu_in 0, delta, a3 and rs NULL.
  *                              split 1 (launch_layernorm_split): LayerNorm of gelu(x) when gelu_in, of x + delta when delta
@@ -199,7 +200,8 @@ int esmdiff_get_attention_scales(esmdiff_engine* eng, int32_t layer, float* qk_o
 
 /* ---- Weight conversion at create (csrc/convert.hip, csrc/gemm_split.hip, csrc/attention_split.hip: what every create's loader,
  * csrc/engine_weights.hip, runs on each tensor of the state dict) and the input stage (csrc/embed.hip, csrc/norm.hip), one launcher
- * at a time (tests/test_gpu_loader.py).  All synchronous; every argument is checked before the first HIP call
+ * at a time (tests/test_gpu_loader.py).  Enqueued on `stream` without a wait, except esmdiff_split_weight_from and
+ * esmdiff_weight_rownorm_max, which take no stream and are synchronous; every argument is checked before the first HIP call
  * (ESMDIFF_E_INVALID, nothing touched).  src_dtype: esmdiff_dtype of the source tensor (ESMDIFF_F32 / ESMDIFF_BF16). ----
  *   esmdiff_convert_weight      src [n] -> dst [n].  dst_kind 0: bfloat16, round to nearest even (ed::launch_to_bf16); 1: IEEE half,
  *                               saturating at +-65504, NaN stays NaN (ed16::launch_to_bf16); 2: float32, exact (launch_to_f32)
