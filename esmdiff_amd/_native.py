@@ -58,7 +58,7 @@ EXPORTS = [
     "esmdiff_ddpm_step_rows", "esmdiff_logit_error_stats", "esmdiff_get_build_info", "esmdiff_describe_plan", "esmdiff_set_option",
     "esmdiff_get_sequence_logits", "esmdiff_gibbs_step_rows", "esmdiff_shared_forward_batch",
     "esmdiff_attention_f16", "esmdiff_qk_norm_rope", "esmdiff_add_layernorm", "esmdiff_geom_attention",
-    "esmdiff_set_lengths", "esmdiff_attention_ragged",
+    "esmdiff_set_lengths", "esmdiff_attention_ragged", "esmdiff_attention_16_parts",
     "esmdiff_q_xt", "esmdiff_nelbo_rows", "esmdiff_nelbo_eval",
     "esmdiff_superpose_pairs", "esmdiff_tm_pairs",
     "esmdiff_cluster_threshold", "esmdiff_cluster_gromos",
@@ -201,6 +201,7 @@ def lib():
     L.esmdiff_nelbo_rows.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.esmdiff_nelbo_eval.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp]
     L.esmdiff_attention_ragged.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(i32), i32, i32, vp]
+    L.esmdiff_attention_16_parts.argtypes = [i32, vp, vp, vp, vp, ctypes.POINTER(i32), i32, i32, i32, vp]
     L.esmdiff_decoder_create.argtypes = L.esmdiff_engine_create.argtypes
     L.esmdiff_decoder_decode.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]
     f64, f64p = ctypes.c_double, ctypes.POINTER(ctypes.c_double)

@@ -212,6 +212,31 @@ int esmdiff_qk_norm_rope(esmdiff_engine* e, const void* qkv, const float* q_ln_w
   return 0;
 }
 
+// attention_kernel_occ4 / attention_kernel_ragged_occ4 alone, on operands the caller made: no q/k LayerNorm, no rotary, no engine
+int esmdiff_attention_16_parts(int32_t dtype, const void* q, const void* k, const void* qkv, void* ctx, const int32_t* lens,
+                               int32_t B, int32_t L, int32_t H, void* stream) {
+  if (!q || !k || !qkv || !ctx) return fail(nullptr, ESMDIFF_E_INVALID, "attention_16_parts: null pointer");
+  if (dtype != 0 && dtype != 1) return fail(nullptr, ESMDIFF_E_INVALID, "attention_16_parts: dtype %d (0 bf16, 1 f16)", dtype);
+  if (B <= 0 || L <= 0 || H <= 0 || H > 32 || (int64_t)B * L > 0x3fffffffll)
+    return fail(nullptr, ESMDIFF_E_INVALID, "attention_16_parts: B=%d L=%d must be positive (B * L < 2^30), H=%d in 1 .. 32", B, L, H);
+  if (lens)   // the kernel indexes with them
+    for (int b = 0; b < B; ++b)
+      if (lens[b] < 1 || lens[b] > L)
+        return fail(nullptr, ESMDIFF_E_INVALID, "attention_16_parts: lens[%d] = %d outside 1..L (%d)", b, lens[b], L);
+  const hipStream_t st = (hipStream_t)stream;
+  int32_t* dl = nullptr;
+  if (lens && hipMalloc(&dl, (size_t)B * sizeof(int32_t)) != hipSuccess) return fail(nullptr, ESMDIFF_E_HIP, "attention_16_parts: hipMalloc failed");
+  hipError_t s = lens ? hipMemcpyAsync(dl, lens, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st) : hipSuccess;
+  if (s == hipSuccess)
+    s = ED_KN(dtype == 1, launch_attention((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)qkv, (bf16_t*)ctx, B, L, H, st, dl));
+  if (dl) {   // with lengths the call waits: the length buffer and the caller's host copy die here
+    const hipError_t s2 = hipStreamSynchronize(st);
+    if (s == hipSuccess) s = s2;
+    hipFree(dl);
+  }
+  return launched(nullptr, s, "attention_16_parts");
+}
+
 int esmdiff_add_layernorm(int32_t dtype, float* x, const void* delta, const void* delta2, int32_t write_x, const float* w,
                           const float* b, void* y, int32_t M, int32_t D, void* stream) {
   if (!x || !w || !y) return fail(nullptr, ESMDIFF_E_INVALID, "add_layernorm: null pointer");

@@ -1040,6 +1040,22 @@ def attention_f32_parts(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: in
     return ctx
 
 
+def attention_16_parts(q: torch.Tensor, k: torch.Tensor, qkv: torch.Tensor, B: int, L: int, H: int, *,
+                       lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """The 16-bit attention kernel alone (esmdiff_attention_16_parts) -> ctx [B*L, H*64] of the operands' type (NaN where the
+    kernel wrote nothing).  q, k bfloat16 / float16 [B*L, H*64], q already times log2(e)/8; qkv [B*L, 3*H*64], whose V third is read."""
+    _require_gpu()
+    D = H * 64
+    assert q.dtype in (torch.bfloat16, torch.float16)
+    for t, shape in zip((q, k, qkv), ((B * L, D), (B * L, D), (B * L, 3 * D))):
+        assert t.dtype == q.dtype and t.shape == shape and t.is_contiguous()
+    ctx = torch.full((B * L, D), float("nan"), dtype=q.dtype, device=q.device)
+    arr = None if lengths is None else (ctypes.c_int32 * B)(*[int(n) for n in lengths])
+    N.check(N.lib().esmdiff_attention_16_parts(int(q.dtype == torch.float16), _ptr(q), _ptr(k), _ptr(qkv), _ptr(ctx), arr, B, L, H,
+                                               _stream()))
+    return ctx
+
+
 # ---- weight conversion at create and the input stage, one launcher at a time (include/esmdiff_hip_test.h) ----
 _SRC_DT = {torch.float32: N.DT_F32, torch.bfloat16: N.DT_BF16}
 _DST_KIND = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}

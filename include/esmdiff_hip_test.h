@@ -110,6 +110,15 @@ int esmdiff_attention_ragged(esmdiff_engine* eng, const void* qkv, const float* 
 int esmdiff_qk_norm_rope(esmdiff_engine* eng, const void* qkv, const float* q_ln_w, const float* k_ln_w, void* q, void* k,
                          int32_t B, int32_t L, int32_t H, void* stream);
 
+/* The 16-bit attention kernel alone (csrc/attention.hip: attention_kernel_occ4, with lens its ragged twin), on operands the
+ * caller made: softmax(q k^T) v per 64-wide head, base 2.  dtype 0: bf16 (namespace ed), 1: f16 (ed16).  q, k [B*L, H*64] as
+ * launch_attention takes them: q already multiplied by log2(e)/8 and rounded to the 16-bit type (what esmdiff_qk_norm_rope
+ * writes).  qkv [B*L, 3*H*64]: only its V third is read, in place.  ctx [B*L, H*64].  lens: HOST int32 [B], each in 1..L, or
+ * NULL (as esmdiff_attention_f32_parts: with lens the call waits for `stream`, without it is enqueued and returns).  No engine;
+ * 1 <= H <= 32; every argument is checked before the first HIP call (ESMDIFF_E_INVALID). */
+int esmdiff_attention_16_parts(int32_t dtype, const void* q, const void* k, const void* qkv, void* ctx,
+                               const int32_t* lens, int32_t B, int32_t L, int32_t H, void* stream);
+
 /* Fused residual add + LayerNorm (csrc/norm.hip): v = (x + delta) + delta2 (16-bit [M,D] each, either may be NULL); x = v
  * when write_x; y [M,D] = LayerNorm(v) * w (+ b), eps 1e-5.  dtype 0: bf16 delta / y (namespace ed), 1: f16 (ed16).
  * M > 0, D % 256 == 0, 0 < D <= 2048. */

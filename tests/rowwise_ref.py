@@ -3,7 +3,9 @@ attention (csrc/geom.hip), q/k LayerNorm + rotary and the fused residual add + L
 (csrc/attention.hip).  tests/test_gpu_rowwise.py compares the kernels through them; tests/test_rowwise_bars_cpu.py shows
 that the same comparators pass the float64 reference rounded to each build's type and reject planted errors.
 The second half holds the same for the row kernels of the float32-grade engines (csrc/strict.hip, csrc/gemm_split.hip,
-csrc/attention_split.hip): tests/test_gpu_f32_rows.py and tests/test_f32_rows_bars_cpu.py.
+csrc/attention_split.hip): tests/test_gpu_f32_rows.py and tests/test_f32_rows_bars_cpu.py; and, after the float32-grade attention, for the 16-bit
+attention kernel on operands handed to it (attention16_*: cases for its lazy rescale, reference, an emulation of its tile loop):
+tests/test_gpu_attention16.py and tests/test_attention16_bars_cpu.py.
 
 Every bar has the form  |got - ref| <= OUT_EPS[type] * |ref| + coef * unit : the first term is the output rounding of the
 build (round to nearest: half an ulp, at most 2^-8 |x| for bfloat16, 2^-11 |x| for IEEE half, nothing for float32), the
@@ -443,32 +445,192 @@ def split_operand_value(x2: torch.Tensor, scale: float) -> torch.Tensor:
 
 
 ATT_KINDS = ("unit", "gain4", "gain8", "stairs_up", "stairs_down", "one_key")
+# ... and what the 16-bit kernel gets on top (attention16_* below): its lazy-rescale threshold is 8 log2 units, not 4
+ATT16_KINDS = ATT_KINDS + ("stairs_up7", "stairs_down7", "last_key", "first_key", "lone_query", "flat")
 # L: one stage (<= 64), the HALF tail (tail <= 32), the masked tail, exact tiles, 1 to 4 waves of 32 queries, several query blocks
 ATT_LS = (1, 31, 32, 33, 64, 65, 96, 97, 128, 129, 258)
 ATT_BH = ((1, 1), (3, 3), (2, 8))                                           # B H = 1, 9 (XCD slots left empty), 16
 
 
-def attention_case(kind: str, B: int, L: int, H: int, seed: int):
+def attention_case(kind: str, B: int, L: int, H: int, seed: int, lens=None):
     """q, k, v float32 [B*L, H*64] (CPU).  unit / gain4 / gain8: N(0, 1) rows times 1 / 4 / 8 on q and k (trained q/k LayerNorm
     gains).  stairs_up / stairs_down: the best logit rises / falls by 5 nats (7.2 log2 units, above the split kernel's lazy-rescale
     threshold of 4) from one 64-key tile to the next: a rescale at every tile, or never after the first.  one_key: key 2L/3
-    carries all the mass, every other p is below 2^-13 (the lo part of P is subnormal)."""
+    carries all the mass, every other p is below 2^-13 (the lo part of P is subnormal).
+    The kinds ATT16_KINDS adds, for the 16-bit kernel and its threshold of 8 (under which the 5-nat staircase lags: P reaches 2^7.2
+    and the maximum is raised at every second tile): stairs_up7 / stairs_down7: the staircase with 7 nats (10.1 log2 units) per
+    tile.  last_key / first_key: one_key with the heavy key at L - 1 (the sample's own last valid key, lens[b] - 1, when lens is
+    given) / at 0.  lone_query: the keys of stairs_up7 under unit-size queries, except query 32 w + (5 + 7 w) % 32 of every wave
+    w of 32 queries, which is aligned with the staircase: one lane decides for its wave.  flat: q = 0, every output is the mean
+    of the V rows."""
     g = torch.Generator().manual_seed(seed)
     shape = (B, L, H, 64)
     q, k, v = (torch.randn(shape, generator=g) for _ in range(3))
     if kind.startswith("gain"):
         q, k = q * float(kind[4:]), k * float(kind[4:])
+    elif kind == "flat":
+        q = torch.zeros(shape)
     elif kind != "unit":
         u = torch.randn(B, 1, H, 64, generator=g)
         u = u / u.norm(dim=-1, keepdim=True)
-        q = 8 * u + 0.3 * q                                                  # q . k / 8 = (u . k) + noise
-        if kind == "one_key":
-            k = 0.3 * k
-            k[:, (2 * L) // 3] = 12 * u[:, 0] + 0.3 * k[:, (2 * L) // 3]
+        if kind == "lone_query":
+            for q0 in range(0, L, 32):
+                i = q0 + (5 + 7 * (q0 // 32)) % 32
+                if i < L:
+                    q[:, i] = 8 * u[:, 0] + 0.3 * q[:, i]
         else:
+            q = 8 * u + 0.3 * q                                              # q . k / 8 = (u . k) + noise
+        if kind in ("one_key", "last_key", "first_key"):
+            k = 0.3 * k
+            for b in range(B):
+                n = L if lens is None else int(lens[b])
+                at = {"one_key": (2 * n) // 3, "last_key": n - 1, "first_key": 0}[kind]
+                k[b, at] = 12 * u[b, 0] + 0.3 * k[b, at]
+        else:
+            step = {"stairs_up": 5.0, "stairs_down": -5.0, "stairs_up7": 7.0, "stairs_down7": -7.0, "lone_query": 7.0}[kind]
             tile = (torch.arange(L) // 64).float()[None, :, None, None]
-            k = 0.3 * k + (5.0 if kind == "stairs_up" else -5.0) * tile * u
+            k = 0.3 * k + step * tile * u
     return tuple(t.reshape(B * L, H * 64).contiguous() for t in (q, k, v))
+
+
+# ---- the 16-bit attention kernel alone (csrc/attention.hip, attention_kernel.inc; esmdiff_attention_16_parts): its operands are
+# handed to it, so q and k carry no rounding of their own and the float64 reference starts from the very 16-bit values.
+# What is left: P = exp2(s - m) is rounded to the 16-bit type before P . V, independently per key: OUT_EPS sqrt(sum_k p_k^2 v_k^2);
+# and the float32 score arithmetic, as for the float32-grade kernels above: 2^-24 (1 + |q| kmax / 8) sum_k p_k |v_k|.
+#   unit = OUT_EPS[dtype] sqrt((p p) @ (v v)) + 2^-24 (1 + |q| kmax / 8) (p @ |v|);   bar = OUT_EPS |ref| + ATT16_COEF unit
+# ATT16_COEF = 4 x the largest needed_coef of attention16_emulate (the kernel's own arithmetic on the CPU, no plant) over every
+# case tests/test_gpu_attention16.py runs (attention16_runs, the ragged batch included), rounded up to a power of two.  Measured
+# on the CPU (tests/test_attention16_bars_cpu.py, EXPERIMENTS.md): the bf16 emulation needs 1.97 (stairs_down7 at B H L = 2 8 97; 1.71
+# on unit rows), the f16 one 1.77 on the staircases and unit rows but 12.50 on one_key at B H L = 3 3 32 (9.67 gain4, 7.38
+# last_key, 6.79 first_key): one key holds all the mass, so in the channels where its v is near 0 the output and the other
+# keys' P (~1e-5) lie below f16's normal range 2^-14, where the spacing is 2^-24 whatever the value and the unit's relative 2^-11
+# no longer describes a rounding.  4 x 12.50 = 50 -> 64.
+# ATT16_COEF_BUILD: the same rule on each build's own figures (bf16: 4 x 1.97 = 7.9 -> 8), so that the wide subnormal range of
+# f16 does not loosen the bar of the default bf16 engine eightfold.  The tests assert the build's bar, which implies ATT16_COEF's.
+# The kernels themselves, measured on an MI355X (tests/test_gpu_attention16.py): bf16 1.97, f16 12.50, at the same cases — the
+# emulation's figures to the third digit up to L = 129, within 0.03 of them at L = 258 and 1026.
+ATT16_COEF = 64.0
+ATT16_COEF_BUILD = {torch.bfloat16: 8.0, torch.float16: 64.0}
+ATT16_THR = 8.0                                                             # attention_kernel.inc: THR, log2 units
+ATT16_LS = ATT_LS
+ATT16_LONG = ((1, 1, 1026), ("stairs_up7", "stairs_up", "gain8"))           # one long chain: 17 tiles, 33 waves
+ATT16_RAGGED_LENS = (3, 33, 64, 65, 97, 129, 258)
+ATT16_RAGGED_H = 3
+ATT16_RAGGED_KINDS = ("gain8", "stairs_up7", "last_key")
+# the flat check needs no softmax reference: l = the number of keys and every P = 1 are exact, O is a float32 sum of L 16-bit values
+# (about 2^-24 of a partial sum ~ sqrt(L) sigma per addition: ~2^-24 sigma after the division by L) times a rounded 1 / L:
+# OUT_EPS |mean| + 4 x 2^-24 max|v|
+ATT16_FLAT_ABS = 4 * F32_EPS
+
+
+def attention16_runs():
+    """(B, H, L, kinds) of every plain launch of tests/test_gpu_attention16.py::test_attention16_parts_vs_float64."""
+    for L in ATT16_LS:
+        for B, H in ATT_BH + (((1, 24),) if L == 258 else ()):
+            yield B, H, L, ATT16_KINDS
+    (B, H, L), kinds = ATT16_LONG
+    yield B, H, L, kinds
+
+
+def attention16_operands(q, k, v, dtype: torch.dtype):
+    """What the kernel is handed, from a case's float32 q, k, v: q times log2(e)/8 (a float32 product, as qk_norm_rope forms
+    it) and k rounded to dtype; qkv [*, 3 D] with v rounded in its last third and NaN in the q and k thirds, which the kernel
+    must not read."""
+    qs = torch.tensor(QSCALE, dtype=torch.float32, device=q.device)
+    q16, k16, v16 = (q.float() * qs).to(dtype), k.to(dtype), v.to(dtype)
+    nan = torch.full_like(v16, float("nan"))
+    return q16.contiguous(), k16.contiguous(), torch.cat([nan, nan, v16], 1).contiguous()
+
+
+def _per_sample(fn, tensors, B, L, H, lens, out_dtype):
+    """fn(sample's rows ..., n) at each sample's own length; rows from lens[b] on stay +0."""
+    outs = None
+    for b, n in enumerate(lens):
+        res = fn(*(t[b * L:b * L + int(n)] for t in tensors), int(n))
+        res = res if isinstance(res, tuple) else (res,)
+        if outs is None:
+            outs = tuple(torch.zeros(B * L, H * 64, dtype=out_dtype, device=r.device) for r in res)
+        for o, r in zip(outs, res):
+            o[b * L:b * L + int(n)] = r
+    return outs if len(outs) > 1 else outs[0]
+
+
+def attention16_ref64(q16, k16, qkv16, B: int, L: int, H: int, dtype: torch.dtype, lens=None):
+    """softmax(q k^T / 8) v per head in float64 from the 16-bit operands the kernel was handed (q16 / (log2(e)/8) is q) ->
+    (ref, unit) [B*L, H*64] on the operands' device.  lens: every sample at its own length, (0, 0) on its padded rows."""
+    D = H * 64
+    if lens is not None:
+        return _per_sample(lambda a, b, c, n: attention16_ref64(a, b, c, 1, n, H, dtype), (q16, k16, qkv16), B, L, H, lens,
+                           torch.float64)
+    q = (q16.double() / QSCALE).view(B, L, H, 64).transpose(1, 2)
+    k = k16.double().view(B, L, H, 64).transpose(1, 2)
+    v = qkv16[:, 2 * D:].double().view(B, L, H, 64).transpose(1, 2)
+    p = torch.softmax(q @ k.transpose(-1, -2) / 8, -1)
+    ref = (p @ v).transpose(1, 2).reshape(B * L, D)
+    qn = q.norm(dim=-1, keepdim=True)
+    kmax = k.norm(dim=-1).amax(-1)[..., None, None]
+    unit = OUT_EPS[dtype] * torch.sqrt((p * p) @ (v * v)) + F32_EPS * (1 + qn * kmax / 8) * (p @ v.abs())
+    return ref, unit.transpose(1, 2).reshape(B * L, D)
+
+
+ATT16_PLANTS = ("no_o_rescale", "no_l_rescale", "drop_last_key", "tail_key_twice")
+
+
+def attention16_emulate(q16, k16, qkv16, B: int, L: int, H: int, dtype: torch.dtype, lens=None, *, thr: float = ATT16_THR,
+                        plant=None, stats=None):
+    """attention_kernel.inc's arithmetic in torch: float32 scores of the 16-bit operands (base 2: q16 carries log2(e)/8), keys in
+    tiles of 64 (a last tile of at most 32 valid keys computes 32; keys past the end are the clamped row L - 1 at a score of
+    -1e30), per wave of 32 queries one decision to raise the running maxima — when any of its queries' tile maximum exceeds its
+    running maximum by more than thr — with O and l of every query of the wave rescaled by exp2(m_old - m_new); P = exp2(s - m)
+    summed unrounded into l and rounded to dtype for P . V, float32 O, then O * (1 / l) rounded to dtype -> [B*L, H*64] dtype.
+    stats (a dict): "tiles" and "raises" count the (head, wave, tile) steps after each wave's first tile and the raises among
+    them; "pmax" the largest P.  plant (tests of the comparator only): no_o_rescale / no_l_rescale: O / l keeps its old scale
+    on a raise after tile 0; drop_last_key: key L - 1 is masked; tail_key_twice: the first clamped key of a partial last tile
+    (a copy of key L - 1) is not masked."""
+    assert plant is None or plant in ATT16_PLANTS, plant
+    D = H * 64
+    if lens is not None:
+        return _per_sample(lambda a, b, c, n: attention16_emulate(a, b, c, 1, n, H, dtype, thr=thr, plant=plant, stats=stats),
+                           (q16, k16, qkv16), B, L, H, lens, dtype)
+    f32 = torch.float32
+    q, k, v = (t.float().view(B, L, H, 64).transpose(1, 2) for t in (q16, k16, qkv16[:, 2 * D:]))   # (B, H, L, 64)
+    out = torch.empty(B, H, L, 64, dtype=dtype, device=q.device)
+    nkt = (L + 63) // 64
+    tail = L - (nkt - 1) * 64
+    for q0 in range(0, L, 32):
+        qw = q[:, :, q0:q0 + 32]
+        nq = qw.shape[2]
+        m = torch.full((B, H, nq), -1e30, dtype=f32, device=q.device)
+        l = torch.zeros(B, H, nq, dtype=f32, device=q.device)
+        o = torch.zeros(B, H, nq, 64, dtype=f32, device=q.device)
+        for kt in range(nkt):
+            last = kt == nkt - 1
+            idx = kt * 64 + torch.arange(32 if last and tail <= 32 else 64, device=q.device)
+            valid = idx < (L + 1 if plant == "tail_key_twice" and last else L)
+            if plant == "drop_last_key":
+                valid = valid & (idx != L - 1)
+            src = idx.clamp(max=L - 1)
+            s = qw @ k[:, :, src].transpose(-1, -2)
+            s = torch.where(valid, s, torch.full_like(s, -1e30))
+            mx = s.amax(-1)
+            up = ((mx - m) > thr).any(-1, keepdim=True)                      # wave-wide: (B, H, 1)
+            m_new = torch.maximum(m, mx)
+            alpha = torch.exp2(m - m_new)
+            m = torch.where(up, m_new, m)
+            if not (plant == "no_l_rescale" and kt > 0):
+                l = torch.where(up, l * alpha, l)
+            if not (plant == "no_o_rescale" and kt > 0):
+                o = torch.where(up[..., None], o * alpha[..., None], o)
+            p = torch.exp2(s - m[..., None])
+            l = l + p.sum(-1)
+            o = o + p.to(dtype).float() @ v[:, :, src]
+            if stats is not None:
+                stats["pmax"] = max(stats.get("pmax", 0.0), float(p.max()))
+                if kt > 0:
+                    stats["tiles"] = stats.get("tiles", 0) + up.numel()
+                    stats["raises"] = stats.get("raises", 0) + int(up.sum())
+        out[:, :, q0:q0 + nq] = (o * (1.0 / l)[..., None]).to(dtype)
+    return out.transpose(1, 2).reshape(B * L, D)
 
 
 # ---- SwiGLU of the F32 engine (swiglu_f32_kernel): mid = silu(g) u = g / (1 + exp(-g)) u.  exp, the add, the division and the

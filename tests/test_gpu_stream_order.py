@@ -377,6 +377,11 @@ def _kernel_case(name, tiny, alt):
         else:
             mk = lambda k: [_randn(B * L, D, seed=1 + k), _randn(B * L, D, seed=3 + k), _randn(B * L, 3 * D, seed=5 + k)]
             call = lambda b: E.attention_f32_parts(b[0], b[1], b[2], B, L, H)
+    elif name == "attention_16_parts":
+        B, L = 2, 65
+        mk = lambda k: [_randn(B * L, D, seed=1 + k, scale=0.18, dtype=BF16), _randn(B * L, D, seed=3 + k, dtype=BF16),
+                        _randn(B * L, 3 * D, seed=5 + k, dtype=BF16)]
+        call = lambda b: E.attention_16_parts(b[0], b[1], b[2], B, L, H)
     elif name == "embed_rows":
         def mk(k):
             g = _gen(20 + k)
@@ -403,8 +408,8 @@ def _kernel_case(name, tiny, alt):
 
 KERNEL_ENTRIES = ["gemm_bf16", "gemm_f16", "gemm_f32", "split_rows+gemm_split", "gemm_split_k", "branch_linear_layernorm",
                   "layernorm_bf16", "layernorm_16in", "add_layernorm", "layernorm_f32rows", "swiglu_f32", "qk_norm_rope",
-                  "qk_norm_rope_f32", "v_split", "attention_L65", "attention_f32_parts", "embed_rows", "gather_table_rows",
-                  "sigma_mlp", "convert_weight", "interleave_swiglu"]
+                  "qk_norm_rope_f32", "v_split", "attention_L65", "attention_f32_parts", "attention_16_parts", "embed_rows",
+                  "gather_table_rows", "sigma_mlp", "convert_weight", "interleave_swiglu"]
 
 
 @pytest.mark.parametrize("name", KERNEL_ENTRIES)
@@ -597,13 +602,19 @@ def _sync_case(name, tiny):
         D = tiny.cfg.d_model
         mk = lambda k: [_randn(2 * 33, 3 * D, seed=1 + k, dtype=BF16), 1 + 0.1 * _randn(D, seed=3 + k), 1 + 0.1 * _randn(D, seed=5 + k)]
         call = lambda b: tiny.attention_ragged(b[0], b[1], b[2], 2, 33, lengths=[33, 17])
+    elif name == "attention_16_parts_ragged":
+        from esmdiff_amd import engine as E
+        D = 512
+        mk = lambda k: [_randn(2 * 33, D, seed=1 + k, scale=0.18, dtype=BF16), _randn(2 * 33, D, seed=3 + k, dtype=BF16),
+                        _randn(2 * 33, 3 * D, seed=5 + k, dtype=BF16)]
+        call = lambda b: E.attention_16_parts(b[0], b[1], b[2], 2, 33, 8, lengths=[33, 17])
     else:
         raise KeyError(name)
     return _pair(mk) + (call,)
 
 
-SYNC_ENTRIES = ["attention_ragged", "superpose", "tm", "lddt_counts", "dssp", "contact_map", "native_contacts", "backbone_torsions",
-                "ramachandran", "threshold+gromos", "pair_msf", "fit", "moments", "js_pwd", "js_rg", "validity", "bonding_validity"]
+SYNC_ENTRIES = ["attention_ragged", "attention_16_parts_ragged", "superpose", "tm", "lddt_counts", "dssp", "contact_map", "native_contacts",
+                "backbone_torsions", "ramachandran", "threshold+gromos", "pair_msf", "fit", "moments", "js_pwd", "js_rg", "validity", "bonding_validity"]
 
 
 @pytest.mark.parametrize("name", SYNC_ENTRIES)
