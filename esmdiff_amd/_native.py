@@ -67,6 +67,7 @@ EXPORTS = [
     "esmdiff_dssp",
     "esmdiff_contact_map", "esmdiff_native_contacts",
     "esmdiff_backbone_torsions", "esmdiff_ramachandran",
+    "esmdiff_shape_frames", "esmdiff_debye_frames",
     "esmdiff_describe_gemm_choice", "esmdiff_gemm_workspace_floats",
     "esmdiff_dim6_to_backbone", "esmdiff_plddt_mean", "esmdiff_pair_features", "esmdiff_pae_tm",
     "esmdiff_decoder_set_pair_chunk_bytes",
@@ -82,6 +83,8 @@ DSSP_MAX_L = 4096                            # ESMDIFF_DSSP_MAX_L
 TM_MAX_L = 1280                              # ESMDIFF_TM_MAX_L
 CONTACT_MAX_L, CONTACT_TILE, CONTACT_MAX_CHUNKS = 4096, 64, 256    # ESMDIFF_CONTACT_MAX_L, ESMDIFF_CONTACT_TILE, ESMDIFF_CONTACT_MAX_CHUNKS
 RAMA_MAX_BINS = 72                           # ESMDIFF_RAMA_MAX_BINS
+SHAPE_MAX_L, SHAPE_MAX_BINS = 4096, 4096     # ESMDIFF_SHAPE_MAX_L, ESMDIFF_SHAPE_MAX_BINS
+DEBYE_MAX_Q, DEBYE_Q_CHUNK = 1024, 8         # ESMDIFF_DEBYE_MAX_Q, ESMDIFF_DEBYE_Q_CHUNK
 
 CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
@@ -134,6 +137,11 @@ def rama_scratch_bytes(n: int, L: int) -> int:
     """ESMDIFF_RAMA_SCRATCH_BYTES: the scratch esmdiff_ramachandran's sums need (none with one chunk)."""
     chunks = rama_chunks(n, L)
     return 0 if chunks <= 1 else chunks * L * 48
+
+
+def shape_waves(L: int) -> int:
+    """ESMDIFF_SHAPE_WAVES: the waves that share one frame in esmdiff_shape_frames / esmdiff_debye_frames; their sums' order follows it."""
+    return 1 if L <= 128 else 8
 
 
 def lib_path() -> Path:
@@ -224,6 +232,8 @@ def lib():
     L.esmdiff_native_contacts.argtypes = [vp, i32, vp, i32, i32, vp, vp, f64, i32, f64, f64, vp, vp, vp, vp, vp, vp]
     L.esmdiff_backbone_torsions.argtypes = [vp, i32, i32, i32, vp, f64, vp, vp, vp, vp, vp]
     L.esmdiff_ramachandran.argtypes = [vp, i32, i32, i32, vp, f64, i32, vp, vp, vp, vp, ctypes.c_int64, vp]
+    L.esmdiff_shape_frames.argtypes = [vp, i32, i32, vp, vp, vp, vp, f64, i32, vp]
+    L.esmdiff_debye_frames.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp]
     L.esmdiff_encoder_create.argtypes = [i32] * 9 + [ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.esmdiff_encoder_destroy.argtypes = [vp]
     L.esmdiff_encoder_destroy.restype = None

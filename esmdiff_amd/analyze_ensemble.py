@@ -4,6 +4,7 @@
                                            [--lddt] [--plddt_scale 1.0] [--flex] [--pca_components 3] [--dssp]
                                            [--contacts] [--contact_cutoff 8.0] [--contact_min_sep 3]
                                            [--torsions] [--rama_bins 36]
+                                           [--shape] [--pr_bins 100] [--saxs] [--saxs_qmax 0.5] [--saxs_points 51] [--saxs_data FILE]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
@@ -40,7 +41,18 @@ per target its phi / psi, its region string and the agreement of the samples wit
 best_model, per_residue), js_ramachandran: the Jensen-Shannon distance between the samples' maps and those of the targets taken
 together as one ensemble (thin with few targets: each target fills one cell per residue) and, with exactly two targets,
 region_switches: the residues whose region differs between the two, with the samples' share in each.  Samples and targets are read
-again as N / CA / C backbones, on the analysed subset."""
+again as N / CA / C backbones, on the analysed subset.
+--shape adds a "shape" block (esmdiff_amd/shape.py, csrc/shape.hip): per sample the number of residues, the centroid, the eigenvalues
+of the gyration tensor, Rg, asphericity, acylindricity, the relative shape anisotropy, the end-to-end distance, Dmax and the Kirkwood
+hydrodynamic radius; their summary (mean, std, min, max); the pair-distance distribution p(r) of the samples in --pr_bins cells up to
+the largest Dmax rounded up to a whole Angstrom; per target its own descriptors; and js_shape: the Jensen-Shannon distance between the
+samples' distribution of rg, ree, rh and asphericity and that of the targets taken together as one ensemble (thin with few targets:
+each target fills one cell per quantity).
+--saxs adds a "saxs" block: q (0 .. --saxs_qmax in --saxs_points steps, 1 / Angstrom), the mean Debye intensity of the samples as point
+scatterers at the CA positions, i0, the normalised curve, the Guinier fit (rg, i0, q_max, n_points) beside the coordinate Rg, and the
+dimensionless Kratky curve.  --saxs_data FILE (three whitespace-separated columns q, I, sigma; lines starting with # are ignored;
+implies --saxs) evaluates at the file's q instead and adds chi2_mean, the reduced chi^2 of the mean profile after the least-squares
+scale, and chi2_samples: that of every sample, with the best one."""
 from __future__ import annotations
 
 import argparse
@@ -49,7 +61,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import contacts, ensemble, flexibility, secondary, torsions
+from . import contacts, ensemble, flexibility, secondary, shape, torsions
 from .pdbio import load_coords, read_pdb_backbone, read_pdb_bfactors
 
 
@@ -136,6 +148,18 @@ def contacts_report(samples_path, target_paths, max_models: int = 100, seed: int
     return contacts.report(samples, np.stack(targets), cutoff, min_sep)
 
 
+def shape_report(samples_path, target_paths, max_models: int = 100, seed: int = 0, pr_bins: int = 100) -> dict:
+    """The --shape block, on the samples analyze() takes for the same max_models and seed."""
+    samples, targets, _, _ = load_ca(samples_path, target_paths, max_models, seed)
+    return shape.report(samples, np.stack(targets), pr_bins)
+
+
+def saxs_report(samples_path, target_paths, max_models: int = 100, seed: int = 0, q_max: float = 0.5, points: int = 51, data=None) -> dict:
+    """The --saxs block, on the same samples; data: the path of a q, I, sigma file or None."""
+    samples, _, _, _ = load_ca(samples_path, target_paths, max_models, seed)
+    return shape.saxs_report(samples, q_max, points, None if data is None else shape.read_saxs_data(data))
+
+
 def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0,
             flex: bool = False, pca_components: int = 3, dssp: bool = False) -> dict:
     samples, targets, n_all, keep = load_ca(samples_path, target_paths, max_models, seed)
@@ -178,6 +202,12 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--contact_min_sep", type=int, default=3, help="the smallest sequence separation |a - b| of a contact")
     ap.add_argument("--torsions", action="store_true", help="add the backbone torsions: Ramachandran statistics, regions, geometry, agreement with the targets")
     ap.add_argument("--rama_bins", type=int, default=36, help="cells per axis of the --torsions Ramachandran maps (1 to 72)")
+    ap.add_argument("--shape", action="store_true", help="add the gyration tensor's shape descriptors, Ree, Dmax, Rh and p(r)")
+    ap.add_argument("--pr_bins", type=int, default=100, help="cells of the --shape pair-distance distribution")
+    ap.add_argument("--saxs", action="store_true", help="add the Debye SAXS profile of the samples, its Guinier Rg and Kratky curve")
+    ap.add_argument("--saxs_qmax", type=float, default=0.5, help="the largest q of the --saxs profile (1 / Angstrom)")
+    ap.add_argument("--saxs_points", type=int, default=51, help="values of q of the --saxs profile, from 0 to --saxs_qmax")
+    ap.add_argument("--saxs_data", default=None, help="a measured curve (columns q, I, sigma): evaluate at its q and add the reduced chi^2")
     return ap
 
 
@@ -190,6 +220,10 @@ def main(argv=None) -> Path:
     if args.torsions:
         keep = load_ca(args.samples, args.targets, args.max_models, args.seed)[3]
         report["torsions"] = torsions_report(args.samples, args.targets, keep, args.rama_bins)
+    if args.shape:
+        report["shape"] = shape_report(args.samples, args.targets, args.max_models, args.seed, args.pr_bins)
+    if args.saxs or args.saxs_data:
+        report["saxs"] = saxs_report(args.samples, args.targets, args.max_models, args.seed, args.saxs_qmax, args.saxs_points, args.saxs_data)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

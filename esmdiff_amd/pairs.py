@@ -1,5 +1,5 @@
 """The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
-csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip and csrc/torsions.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip and csrc/shape.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
 on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
 host-facing layers above it.
 Row blocks are contiguous slices (A[r0:r1]): a slice carries its own pointer, dtype and shape.  There is no CPU fallback."""
@@ -223,6 +223,44 @@ def ramachandran(X, mask, break_distance: float, bins: int, sums: bool = True):
            invalid=lambda: f"esmdiff_ramachandran: invalid argument: L = {L} (at least 1), bins = {bins} (at least 1), "
                            f"break_distance = {break_distance} (positive and finite)")
     return hist, counts, out
+
+
+def shape_frames(X, mask, width: Optional[float] = None, bins: int = 0):
+    """One esmdiff_shape_frames call: X f64 (n, L, 3), mask u8 (n, L) or None -> count i32 (n,), desc f64 (n, 12) (the centroid, the six
+    sums of (r - c)(r - c)^T undivided, sum_inv_d, dmax, ree) and, with a `width`, hist i64 (bins + 1,): the pair distances of all frames
+    in cells of that width, the last cell the overflow (else None, and never allocated)."""
+    assert X.dim() == 3 and X.shape[-1] == 3 and X.dtype == torch.float64, f"f64 (n, L, 3) coordinates, got {X.dtype} {tuple(X.shape)}"
+    n, L = X.shape[:2]
+    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    count, desc = _new((n,), torch.int32), _new((n, 12))
+    bins = int(bins)
+    hist = None if width is None else _new((bins + 1 if 1 <= bins <= N.SHAPE_MAX_BINS else 1,), torch.int64)   # refused: nothing is written
+    code = N.lib().esmdiff_shape_frames(_p(X), n, L, _p(mask), _p(count), _p(desc), _p(hist), 0.0 if width is None else float(width),
+                                        bins, _stream())
+    _check("esmdiff_shape_frames", code,
+           capacity=lambda: f"esmdiff_shape_frames: L = {L} or bins = {bins} is beyond the kernel's limits ({N.SHAPE_MAX_L} residues: a "
+                            f"frame is staged in LDS; {N.SHAPE_MAX_BINS} cells); there is no slow path",
+           invalid=lambda: f"esmdiff_shape_frames: invalid argument: L = {L} (at least 1), bins = {bins} (at least 1), width = {width} "
+                           f"(positive and finite)")
+    return count, desc, hist
+
+
+def debye_frames(X, mask, q, ff=None):
+    """One esmdiff_debye_frames call: X f64 (n, L, 3), mask u8 (n, L) or None, q f64 (Q,) and ff f64 (L, Q) or None on the device ->
+    intensity f64 (n, Q).  The entry does not look at q: its values are the caller's to check (esmdiff_amd/shape.py does)."""
+    assert X.dim() == 3 and X.shape[-1] == 3 and X.dtype == torch.float64, f"f64 (n, L, 3) coordinates, got {X.dtype} {tuple(X.shape)}"
+    n, L = X.shape[:2]
+    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    assert q.dim() == 1 and q.dtype == torch.float64 and q.is_cuda, "q is f64 (Q,) on the device"
+    Q = q.shape[0]
+    assert ff is None or (ff.dtype == torch.float64 and ff.is_cuda and tuple(ff.shape) == (L, Q)), f"the form factors are f64 ({L}, {Q}) on the device"
+    intensity = _new((n, Q))
+    code = N.lib().esmdiff_debye_frames(_p(X), n, L, _p(mask), _p(q), Q, _p(ff), _p(intensity), _stream())
+    _check("esmdiff_debye_frames", code,
+           capacity=lambda: f"esmdiff_debye_frames: L = {L} or Q = {Q} is beyond the kernel's limits ({N.SHAPE_MAX_L} residues: a frame "
+                            f"is staged in LDS; {N.DEBYE_MAX_Q} values of q a call); there is no slow path",
+           invalid=lambda: f"esmdiff_debye_frames: invalid argument: L = {L} (at least 1), Q = {Q} (at least 1)")
+    return intensity
 
 
 def adjacency(n: int) -> torch.Tensor:

@@ -755,6 +755,59 @@ int esmdiff_ramachandran(const double* X, int32_t n, int32_t L, int32_t atoms, c
                          int32_t bins, int32_t* hist, int32_t* counts, double* sums, void* scratch, int64_t scratch_bytes,
                          void* stream);
 
+/* Size, shape and scattering of every frame of an ensemble of CA traces (float64 coordinates in Angstrom, device pointers in and out;
+ * each call synchronises `stream`): DESIGN.md §3.25, held to the numpy restatement tests/shape_ref.py.  (An addition; the ABI number
+ * stays.)  X f64 [n, L, 3]; mask u8 [n, L] or NULL (all given).  A residue is VALID in a frame when it is not masked and none of its
+ * three coordinates is NaN; a masked coordinate is never read.  A distance is d = sqrt((dx dx + dy dy) + dz dz) with no FMA contraction
+ * and the correctly rounded square root and division.  No float atomics.  Every element of every output that is not NULL is
+ * written; the caller zeroes nothing; a frame's row does not depend on n or on the other frames; n == 0 succeeds.  A NULL required
+ * pointer, n < 0, L < 1 (and with hist: bins < 1, a width that is not positive and finite; for Debye Q < 1) return
+ * ESMDIFF_E_INVALID before anything is launched and touch no output; L > ESMDIFF_SHAPE_MAX_L (one frame of the longest chain, 96 KiB of
+ * float64 planes, has to fit in LDS: the limit and the reason of ESMDIFF_CONTACT_MAX_L) returns ESMDIFF_E_CAPACITY.
+ *
+ * THE ORDER OF EVERY SUM is a function of L alone, through W = ESMDIFF_SHAPE_WAVES(L) (the waves that share a frame):
+ *   over residues  lane l of 64 adds the terms of the residues b = l, l + 64, l + 128 ... in increasing b, starting from +0.0, a
+ *                  residue that is not valid adding nothing; the 64 lane sums v are combined by the xor butterfly
+ *                  v[l] = v[l] + v[l ^ off] for off = 32, 16, 8, 4, 2, 1.
+ *   over pairs     a < b, both valid.  Wave w of W takes the rows a = w, w + W, w + 2 W ... in that order; in row a lane l takes
+ *                  b = a + 1 + l, a + 1 + l + 64 ... in increasing b.  A lane keeps ONE sum, starting from +0.0, across all the
+ *                  rows of its wave; a pair that is not valid adds nothing.  Then the butterfly above per wave, and for W = 8 the
+ *                  wave sums as ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)).
+ * So two runs are bit-identical and tests/shape_ref.py follows the orders bit for bit.
+ *
+ * esmdiff_shape_frames: per frame i, over its N_i valid residues,
+ *   count i32 [n]       N_i
+ *   desc  f64 [n, 12]   [0..2]  the centroid c = (sum of r) / N_i, component by component (over residues; one division)
+ *                       [3..8]  the sums of (r - c)(r - c)^T in the order xx, yy, zz, xy, xz, yz, taken in a second pass about that
+ *                               centroid (over residues) and NOT divided: the gyration tensor is these / N_i, and the caller divides
+ *                       [9]     sum_inv_d = the sum of 1 / d_ab (over pairs); +inf when two valid residues coincide
+ *                       [10]    dmax = the largest d_ab
+ *                       [11]    ree = |r_{L-1} - r_0|, NaN unless both ends are valid (L == 1: 0)
+ *                       N_i == 0: the centroid is NaN, the six sums, sum_inv_d and dmax are 0, ree is NaN.  N_i == 1: the centroid
+ *                       is the residue, the six sums, sum_inv_d and dmax are 0.
+ *   hist  i64 [bins + 1] or NULL (width and bins are then ignored): over all frames and valid pairs a < b, cell
+ *                       (int)floor(d / width), every cell >= bins counted in cell `bins` (overflow).  Zeroed by the entry; integer
+ *                       atomics.  bins > ESMDIFF_SHAPE_MAX_BINS (the workgroup's histogram in LDS) returns ESMDIFF_E_CAPACITY.
+ *
+ * esmdiff_debye_frames: intensity f64 [n, Q], I_i(q) = sum_a f_a^2 + 2 sum_{a<b} f_a f_b s(q d_ab) over valid residues and pairs, with
+ * q f64 [Q] ON THE DEVICE and ff f64 [L, Q] the form factor of residue a at q[k] at ff[a Q + k], or NULL: every f is 1 (point
+ * scatterers).  x = q d is one float64 product, s(x) = sin(x) / x for x != 0 and exactly 1.0 for x == 0 (q = 0 and coincident atoms
+ * give no NaN), a pair's term is (f_a f_b) s — s itself with ff == NULL — added in the order over pairs; sum_a f_a^2 is summed in
+ * the order over residues, and I = that + 2.0 (pair sum).  With ff == NULL, I(q = 0) is N_i^2 exactly.  The order for a given
+ * (frame, q) does not depend on n, on Q or on the position of q in the array (the kernel walks ESMDIFF_DEBYE_Q_CHUNK values of q at
+ * a time, each with a sum of its own): the same q gives the same bits inside any q array.  A frame without a valid residue gives 0.
+ * The entry cannot inspect q without a copy: a negative or non-finite q is the caller's to reject (esmdiff_amd/shape.py does).
+ * Q > ESMDIFF_DEBYE_MAX_Q returns ESMDIFF_E_CAPACITY. */
+#define ESMDIFF_SHAPE_MAX_L 4096
+#define ESMDIFF_SHAPE_MAX_BINS 4096
+#define ESMDIFF_SHAPE_WAVES(L) ((L) <= 128 ? 1 : 8)
+#define ESMDIFF_DEBYE_MAX_Q 1024
+#define ESMDIFF_DEBYE_Q_CHUNK 8
+int esmdiff_shape_frames(const double* X, int32_t n, int32_t L, const uint8_t* mask, int32_t* count, double* desc, int64_t* hist,
+                         double width, int32_t bins, void* stream);
+int esmdiff_debye_frames(const double* X, int32_t n, int32_t L, const uint8_t* mask, const double* q, int32_t Q, const double* ff,
+                         double* intensity, void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
