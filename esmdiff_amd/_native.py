@@ -77,6 +77,8 @@ EXPORTS = [
     "esmdiff_attention_f32_parts", "esmdiff_gemm_split_k", "esmdiff_get_attention_scales",
     "esmdiff_convert_weight", "esmdiff_interleave_swiglu", "esmdiff_split_weight_from", "esmdiff_weight_rownorm_max",
     "esmdiff_embed_rows", "esmdiff_gather_table_rows", "esmdiff_sigma_mlp", "esmdiff_layernorm_16in",
+    "esmdiff_mask_row_list", "esmdiff_gather_rows16", "esmdiff_add_layernorm_rows", "esmdiff_copy_masked_logits",
+    "esmdiff_ddpm_step_mapped", "esmdiff_move_token_rows", "esmdiff_samples_with_mask", "esmdiff_rows_identical",
 ]
 LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
 DSSP_MAX_L = 4096                            # ESMDIFF_DSSP_MAX_L
@@ -278,6 +280,14 @@ def lib():
     L.esmdiff_gather_table_rows.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     L.esmdiff_sigma_mlp.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     L.esmdiff_layernorm_16in.argtypes = [i32, vp, vp, vp, vp, i32, i32, vp]
+    L.esmdiff_mask_row_list.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+    L.esmdiff_gather_rows16.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.esmdiff_add_layernorm_rows.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
+    L.esmdiff_copy_masked_logits.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp]
+    L.esmdiff_ddpm_step_mapped.argtypes = [vp, vp, i32, i32, f32, f32, i32, ctypes.POINTER(Rng), i32, i32, i32, i32, vp, vp]
+    L.esmdiff_move_token_rows.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    L.esmdiff_samples_with_mask.argtypes = [vp, i32, i32, vp, vp]
+    L.esmdiff_rows_identical.argtypes = [vp, vp, i32, i32, vp, vp]
     for n in EXPORTS:
         if n not in ("esmdiff_engine_destroy", "esmdiff_last_error", "esmdiff_encoder_destroy", "esmdiff_encoder_last_error"):
             getattr(L, n).restype = ctypes.c_int

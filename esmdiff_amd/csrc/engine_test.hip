@@ -508,4 +508,68 @@ int esmdiff_layernorm_16in(int32_t dtype, const void* x16, const float* w, const
   return launched(nullptr, ED_KN(dtype == 1, launch_layernorm_bf16_in((const bf16_t*)x16, w, b, (bf16_t*)y16, M, D, st)), "layernorm_16in");
 }
 
+// ---- the needed-rows and sub-batch bookkeeping kernels, one launcher at a time, enqueued on the caller's stream ----
+int esmdiff_mask_row_list(const int64_t* x, int32_t B, int32_t L, int32_t np, int32_t* list, int32_t* map, int32_t* count,
+                          void* stream) {
+  if (!x || !list || !map || !count) return fail(nullptr, ESMDIFF_E_INVALID, "mask_row_list: null pointer");
+  if (B <= 0 || L <= 0 || np <= 0 || np > B || (int64_t)B * L > 0x7fffffffll)
+    return fail(nullptr, ESMDIFF_E_INVALID, "mask_row_list: B=%d L=%d must be positive with B * L < 2^31, np=%d in 1 .. B", B, L, np);
+  return launched(nullptr, launch_mask_row_list(x, B, L, np, list, map, count, (hipStream_t)stream), "mask_row_list");
+}
+
+int esmdiff_gather_rows16(const void* src, const int32_t* list, void* dst, int32_t n, int32_t D, void* stream) {
+  if (!src || !list || !dst) return fail(nullptr, ESMDIFF_E_INVALID, "gather_rows16: null pointer");
+  if (n <= 0 || D <= 0 || D % 8) return fail(nullptr, ESMDIFF_E_INVALID, "gather_rows16: n=%d must be positive, D=%d a positive multiple of 8", n, D);
+  return launched(nullptr, launch_gather_rows16((const uint16_t*)src, list, (uint16_t*)dst, n, D, (hipStream_t)stream), "gather_rows16");
+}
+
+int esmdiff_add_layernorm_rows(int32_t dtype, const float* x, const void* delta, const int32_t* rows, const void* delta2,
+                               float* x_out, const float* w, const float* b, void* y, int32_t M, int32_t D, void* stream) {
+  if (!x || !w || !y) return fail(nullptr, ESMDIFF_E_INVALID, "add_layernorm_rows: null pointer");
+  if (dtype != 0 && dtype != 1) return fail(nullptr, ESMDIFF_E_INVALID, "add_layernorm_rows: dtype %d (0 bf16, 1 f16)", dtype);
+  if (M <= 0 || D <= 0) return fail(nullptr, ESMDIFF_E_INVALID, "add_layernorm_rows: M=%d D=%d must be positive", M, D);
+  return launched(nullptr, ED_KN(dtype, launch_add_layernorm_rows_bf16(x, (const bf16_t*)delta, rows, (const bf16_t*)delta2, x_out, w, b,
+                                                                       (bf16_t*)y, M, D, (hipStream_t)stream)), "add_layernorm_rows");
+}
+
+int esmdiff_copy_masked_logits(const int64_t* x, const float* logits, int32_t ld, const int32_t* map, float* out, int32_t ld_out,
+                               int32_t V, int32_t rows, void* stream) {
+  if (!x || !logits || !out) return fail(nullptr, ESMDIFF_E_INVALID, "copy_masked_logits: null pointer");
+  if (rows <= 0 || V <= 0 || ld < V || ld_out < V)
+    return fail(nullptr, ESMDIFF_E_INVALID, "copy_masked_logits: rows=%d V=%d must be positive, ld=%d and ld_out=%d at least V", rows, V, ld, ld_out);
+  return launched(nullptr, launch_copy_masked_logits(x, logits, ld, map, out, ld_out, V, rows, (hipStream_t)stream), "copy_masked_logits");
+}
+
+int esmdiff_ddpm_step_mapped(int64_t* x, const float* logits, int32_t ld, int32_t V, float mc_t, float mc_s, int32_t final_,
+                             const esmdiff_rng* rng, int32_t step, int32_t B, int32_t L, int32_t logits_period,
+                             const int32_t* row_map, void* stream) {
+  if (!x || !logits || (!final_ && !rng)) return fail(nullptr, ESMDIFF_E_INVALID, "ddpm_step_mapped: null pointer");
+  if (B <= 0 || L <= 0 || (int64_t)B * L > 0x7fffffffll || V <= ESMDIFF_MASK_ID || ld < V || logits_period < 0)
+    return fail(nullptr, ESMDIFF_E_INVALID, "ddpm_step_mapped: B=%d L=%d must be positive with B * L < 2^31, V=%d above the mask column, ld=%d at "
+                "least V, logits_period=%d not negative", B, L, V, ld, logits_period);
+  return launched(nullptr, launch_ddpm_step(x, logits, ld, V, mc_t, mc_s, final_, nullptr, 1, rng ? rng->seed : 0,
+                                            rng ? rng->sample_offset : 0, step, B, L, (hipStream_t)stream, logits_period, 0.f, nullptr,
+                                            row_map), "ddpm_step_mapped");
+}
+
+int esmdiff_move_token_rows(const int64_t* src, int64_t* dst, const int32_t* idx, int32_t n, int32_t L, int32_t gather,
+                            void* stream) {
+  if (!src || !dst || !idx) return fail(nullptr, ESMDIFF_E_INVALID, "move_token_rows: null pointer");
+  if (n < 0 || L <= 0 || (gather != 0 && gather != 1))
+    return fail(nullptr, ESMDIFF_E_INVALID, "move_token_rows: n=%d not negative, L=%d positive, gather %d (0 scatter, 1 gather)", n, L, gather);
+  return launched(nullptr, launch_move_token_rows(src, dst, idx, n, L, gather, (hipStream_t)stream), "move_token_rows");
+}
+
+int esmdiff_samples_with_mask(const int64_t* x, int32_t B, int32_t L, int32_t* has, void* stream) {
+  if (!x || !has) return fail(nullptr, ESMDIFF_E_INVALID, "samples_with_mask: null pointer");
+  if (B <= 0 || L <= 0) return fail(nullptr, ESMDIFF_E_INVALID, "samples_with_mask: B=%d L=%d must be positive", B, L);
+  return launched(nullptr, launch_samples_with_mask(x, B, L, has, (hipStream_t)stream), "samples_with_mask");
+}
+
+int esmdiff_rows_identical(const int64_t* seq, const int64_t* x, int32_t B, int32_t L, int32_t* flag, void* stream) {
+  if (!seq || !x || !flag) return fail(nullptr, ESMDIFF_E_INVALID, "rows_identical: null pointer");
+  if (B <= 0 || L <= 0) return fail(nullptr, ESMDIFF_E_INVALID, "rows_identical: B=%d L=%d must be positive", B, L);
+  return launched(nullptr, launch_rows_identical(seq, x, B, L, flag, (hipStream_t)stream), "rows_identical");
+}
+
 }  // extern "C"

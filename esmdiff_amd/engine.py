@@ -1215,6 +1215,101 @@ def add_layernorm(dtype: torch.dtype, x: torch.Tensor, delta: Optional[torch.Ten
                                           _ptr(None if b is None else b.float().contiguous()), _ptr(y), M, D, _stream()))
     return y
 
+
+# ---- the needed-rows and sub-batch bookkeeping kernels, one at a time (include/esmdiff_hip_test.h).  Every output is a buffer
+# of the caller's, written in place: the tests hand in buffers filled with a sentinel and look at what was left alone. ----
+def _dev(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    assert t.dtype == dtype and t.is_cuda and t.is_contiguous(), (t.dtype, t.device)
+    return t
+
+
+def mask_row_list(x: torch.Tensor, n_parts: int, rows_list: torch.Tensor, rows_map: torch.Tensor, count: torch.Tensor) -> None:
+    """esmdiff_mask_row_list: x i64 [B, L] cut into n_parts -> rows_list / rows_map i32 [>= B L], count i32 [>= n_parts]."""
+    _require_gpu()
+    B, L = x.shape
+    assert rows_list.numel() >= B * L and rows_map.numel() >= B * L and count.numel() >= n_parts
+    N.check(N.lib().esmdiff_mask_row_list(_ptr(_dev(x, torch.int64)), B, L, int(n_parts), _ptr(_dev(rows_list, torch.int32)),
+                                          _ptr(_dev(rows_map, torch.int32)), _ptr(_dev(count, torch.int32)), _stream()))
+
+
+def gather_rows16(src: torch.Tensor, rows: torch.Tensor, dst: torch.Tensor) -> None:
+    """esmdiff_gather_rows16: dst [i] = src [rows[i]] for the rows.numel() first rows of dst; 2-byte elements of any dtype."""
+    _require_gpu()
+    n, D = rows.numel(), src.shape[1]
+    assert src.element_size() == 2 and dst.dtype == src.dtype and src.is_contiguous() and dst.is_contiguous() and src.is_cuda
+    assert dst.shape[1] == D and dst.shape[0] >= n
+    N.check(N.lib().esmdiff_gather_rows16(_ptr(src), _ptr(_dev(rows, torch.int32)), _ptr(dst), n, D, _stream()))
+
+
+def add_layernorm_rows(dtype: torch.dtype, x: torch.Tensor, delta: Optional[torch.Tensor], rows: torch.Tensor,
+                       delta2: Optional[torch.Tensor], x_out: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor],
+                       y: torch.Tensor) -> None:
+    """esmdiff_add_layernorm_rows on M = rows.numel() compact rows: x f32 and delta (dtype) are full-size [*, D], delta2 (dtype)
+    is compact [M, D]; x_out f32 and y (dtype) [>= M, D] receive compact rows 0 .. M - 1.  dtype as add_layernorm."""
+    _require_gpu()
+    M, D = rows.numel(), x.shape[1]
+    assert dtype in (torch.bfloat16, torch.float16) and _dev(x, torch.float32).dim() == 2
+    assert delta is None or _dev(delta, dtype).shape == x.shape
+    assert delta2 is None or _dev(delta2, dtype).shape == (M, D)
+    assert _dev(x_out, torch.float32).shape[1] == D and _dev(y, dtype).shape[1] == D and x_out.shape[0] >= M and y.shape[0] >= M
+    N.check(N.lib().esmdiff_add_layernorm_rows(0 if dtype == torch.bfloat16 else 1, _ptr(x), _ptr(delta), _ptr(_dev(rows, torch.int32)),
+                                               _ptr(delta2), _ptr(x_out), _ptr(_dev(w, torch.float32)),
+                                               _ptr(None if b is None else _dev(b, torch.float32)), _ptr(y), M, D, _stream()))
+
+
+def copy_masked_logits(x: torch.Tensor, logits: torch.Tensor, rows_map: Optional[torch.Tensor], out: torch.Tensor, V: int) -> None:
+    """esmdiff_copy_masked_logits: out [row, :V] = logits [rows_map[row] (or row), :V] on the rows of x (i64, flat) that hold
+    MASK; logits / out f32 [>= rows, ld] / [>= rows, ld_out]."""
+    _require_gpu()
+    rows = x.numel()
+    assert _dev(logits, torch.float32).dim() == 2 and _dev(out, torch.float32).dim() == 2
+    assert logits.shape[0] >= rows and out.shape[0] >= rows
+    N.check(N.lib().esmdiff_copy_masked_logits(_ptr(_dev(x, torch.int64)), _ptr(logits), logits.shape[1],
+                                               _ptr(None if rows_map is None else _dev(rows_map, torch.int32)), _ptr(out),
+                                               out.shape[1], int(V), rows, _stream()))
+
+
+def ddpm_step_mapped(x: torch.Tensor, logits: torch.Tensor, V: int, mc_t: float, mc_s: float, *, final: bool = False, seed: int = 0,
+                     sample_offset: int = 0, step: int = 0, logits_period: int = 0,
+                     rows_map: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """esmdiff_ddpm_step_mapped: Engine.ddpm_step's in-place update of x i64 [B, L] with Philox noise, each row reading the
+    logits row (of logits f32 [*, ld]) that logits_period and rows_map send it to."""
+    _require_gpu()
+    B, L = x.shape
+    assert _dev(logits, torch.float32).dim() == 2
+    rng = N.Rng(int(seed), int(sample_offset))
+    N.check(N.lib().esmdiff_ddpm_step_mapped(_ptr(_dev(x, torch.int64)), _ptr(logits), logits.shape[1], int(V), float(mc_t),
+                                             float(mc_s), int(final), ctypes.byref(rng), int(step), B, L, int(logits_period),
+                                             _ptr(None if rows_map is None else _dev(rows_map, torch.int32)), _stream()))
+    return x
+
+
+def move_token_rows(src: torch.Tensor, dst: torch.Tensor, idx: torch.Tensor, n: int, gather: bool) -> None:
+    """esmdiff_move_token_rows: n rows of L int64: dst [i] = src [idx[i]] (gather) or dst [idx[i]] = src [i] (scatter)."""
+    _require_gpu()
+    L = src.shape[1]
+    assert _dev(src, torch.int64).dim() == 2 and _dev(dst, torch.int64).shape[1] == L and idx.numel() >= n
+    N.check(N.lib().esmdiff_move_token_rows(_ptr(src), _ptr(dst), _ptr(_dev(idx, torch.int32)), int(n), L, int(bool(gather)),
+                                            _stream()))
+
+
+def samples_with_mask(x: torch.Tensor, has: torch.Tensor) -> None:
+    """esmdiff_samples_with_mask: has i32 [b] = 1 if row b of x i64 [B, L] holds a MASK, else 0."""
+    _require_gpu()
+    B, L = x.shape
+    assert has.numel() >= B
+    N.check(N.lib().esmdiff_samples_with_mask(_ptr(_dev(x, torch.int64)), B, L, _ptr(_dev(has, torch.int32)), _stream()))
+
+
+def rows_identical(seq: torch.Tensor, x: torch.Tensor, flag: torch.Tensor) -> None:
+    """esmdiff_rows_identical: flag i32 [0] = non-zero if every row of seq and of x (i64 [B, L]) equals its row 0, else 0."""
+    _require_gpu()
+    B, L = x.shape
+    assert seq.shape == x.shape
+    N.check(N.lib().esmdiff_rows_identical(_ptr(_dev(seq, torch.int64)), _ptr(_dev(x, torch.int64)), B, L,
+                                           _ptr(_dev(flag, torch.int32)), _stream()))
+
+
 GEOM_DTYPES = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}
 
 

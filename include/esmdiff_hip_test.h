@@ -254,6 +254,43 @@ int esmdiff_forward_logits_needed(esmdiff_engine* eng, const int64_t* seq, const
                                   float* logits_out, int32_t ld_logits, int32_t B, int32_t L, void* stream);
 int esmdiff_get_tail_rows(esmdiff_engine* eng, int64_t* rows_out, int32_t reset);
 
+/* ---- The needed-rows and sub-batch bookkeeping kernels (csrc/sampler.hip, csrc/norm.hip), one launcher at a time
+ * (tests/test_gpu_row_bookkeeping.py against tests/needed_rows_ref.py).  No engine; enqueued on `stream` without a wait; every
+ * argument is checked before the first HIP call (ESMDIFF_E_INVALID, nothing touched).  MASK = ESMDIFF_MASK_ID. ----
+ *   esmdiff_mask_row_list       x i64 [B, L] cut into np parts (part pi = samples [B pi / np, B (pi + 1) / np), first row t0, `rows`
+ *                               rows): list i32 [t0 + i] = the i-th row of the part that holds MASK, relative to t0, ascending;
+ *                               map i32 [t0 + r] = t0 + (count * 8 <= rows * 7 ? i : r) on those rows; count i32 [np] (device memory
+ *                               here; the engine hands pinned host memory).  Every other entry of list and map is left as it was.
+ *                               1 <= np <= B, B * L < 2^31
+ *   esmdiff_gather_rows16       dst [i, :] = src [list[i], :], n rows of D 16-bit values; D % 8 == 0
+ *   esmdiff_add_layernorm_rows  the fused add + LayerNorm on M compact rows: v = (x [rows[i]] + delta [rows[i]]) + delta2 [i]
+ *                               (x f32 and delta 16-bit of the full batch, delta2 16-bit [M, D]; either delta may be NULL),
+ *                               x_out f32 [i] = v, y [i] = LayerNorm(v) * w (+ b), eps 1e-5; x is only read.  dtype 0: bf16, 1: f16.
+ *                               D % 256 == 0, 0 < D <= 2048
+ *   esmdiff_copy_masked_logits  out [row, 0 .. V) = logits [map ? map[row] : row, 0 .. V) on the rows of x i64 [rows] that hold MASK
+ *                               (row strides ld / ld_out >= V); nothing else of out is written
+ *   esmdiff_ddpm_step_mapped    the update of esmdiff_ddpm_step with Philox noise, reading the logits of row r at row
+ *                               row_map[p] of `logits`, p = ((r / L) % logits_period) * L + r % L when logits_period > 0, else r
+ *                               (row_map NULL: row p itself).  V <= 5120; rng may be NULL on a final pass
+ *   esmdiff_move_token_rows     gather 1: dst [i, :] = src [idx[i], :]; gather 0: dst [idx[i], :] = src [i, :]; n rows of L int64.
+ *                               n = 0 does nothing
+ *   esmdiff_samples_with_mask   has i32 [b] = 1 if row b of x i64 [B, L] holds a MASK, else 0
+ *   esmdiff_rows_identical      flag i32 [1] = non-zero if every row of seq and of x (i64 [B, L] each) equals its row 0, else 0 */
+int esmdiff_mask_row_list(const int64_t* x, int32_t B, int32_t L, int32_t np, int32_t* list, int32_t* map, int32_t* count,
+                          void* stream);
+int esmdiff_gather_rows16(const void* src, const int32_t* list, void* dst, int32_t n, int32_t D, void* stream);
+int esmdiff_add_layernorm_rows(int32_t dtype, const float* x, const void* delta, const int32_t* rows, const void* delta2,
+                               float* x_out, const float* w, const float* b, void* y, int32_t M, int32_t D, void* stream);
+int esmdiff_copy_masked_logits(const int64_t* x, const float* logits, int32_t ld, const int32_t* map, float* out, int32_t ld_out,
+                               int32_t V, int32_t rows, void* stream);
+int esmdiff_ddpm_step_mapped(int64_t* x, const float* logits, int32_t ld, int32_t V, float mc_t, float mc_s, int32_t final_,
+                             const esmdiff_rng* rng, int32_t step, int32_t B, int32_t L, int32_t logits_period,
+                             const int32_t* row_map, void* stream);
+int esmdiff_move_token_rows(const int64_t* src, int64_t* dst, const int32_t* idx, int32_t n, int32_t L, int32_t gather,
+                            void* stream);
+int esmdiff_samples_with_mask(const int64_t* x, int32_t B, int32_t L, int32_t* has, void* stream);
+int esmdiff_rows_identical(const int64_t* seq, const int64_t* x, int32_t B, int32_t L, int32_t* flag, void* stream);
+
 /* Accumulated per-section device time of the esmdiff_forward_logits/ddpm_sample calls since profiling was
  * enabled: esmdiff_set_profiling(eng, 1) brackets every launch with HIP events on the launch stream (no sync);
  * mode 2 brackets only the dominant kernel (FFN-up GEMM, section 6), cheap enough for a timed region; 0 = off. sections: 0 embed, 1 layernorm, 2 gemm_qkv,

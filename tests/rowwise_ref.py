@@ -218,6 +218,21 @@ def attention_ref64(qkv: torch.Tensor, q_w, k_w, B: int, L: int, H: int, dtype: 
 LN_COEF = 4.0
 
 
+# The bar's output term OUT_EPS |ref| describes a rounding to nearest only inside the normal range of the type.  Below 2^-14 an f16
+# output is subnormal and rounds with half a spacing of 2^-25 whatever its size; without a bias y = n w crosses zero, so such outputs
+# occur in every large case.  The arithmetic term covers them where LN_COEF 2^-24 rstd |w| max|v| >= 2^-25, i.e. rstd |w| max|v| >=
+# 1/8.  A row of D >= 256 unit-variance values has rstd max|v| >= 2.6 (its largest value lies that many deviations out), so gains of
+# at least 1 / 16 keep every f16 case inside the bar's model; below that the float64 reference itself, rounded to f16, misses the
+# bar (tests/test_rowwise_bars_cpu.py: 8.6 x at |w| = 0.0036).  bfloat16 has float32's exponent range: no such floor.
+LN_MIN_GAIN = 1.0 / 16
+
+
+def ln_gains(D: int, g: torch.Generator) -> torch.Tensor:
+    """w = 1 + 0.3 randn with |w| kept at or above LN_MIN_GAIN (sign kept)."""
+    w = 1 + 0.3 * torch.randn(D, generator=g)
+    return torch.where(w.abs() < LN_MIN_GAIN, torch.copysign(torch.tensor(LN_MIN_GAIN), w), w)
+
+
 def add_ln_ref64(v32: torch.Tensor, w, b, *, eps: float = LN_EPS):
     """v32: the float32 sum (x + delta) + delta2 -> (ref float64, unit float64)."""
     y, rstd, vmax = ln64(v32, w, b, eps=eps)

@@ -112,6 +112,33 @@ def test_ids_bit_identical_and_work_shrinks(eng, B, L):
     eng.set_needed_rows(True)
 
 
+@pytest.mark.parametrize("B,L", SHAPES[:2])
+def test_ids_bit_identical_shared_step0_with_compact_tail(eng, B, L):
+    """N samples inpainted from one structure: every sample starts from the same prior with half of its rows masked, so step-0
+    sharing and the compact tail are on in the same forward and the update reads row_map[((row / L) % shared) L + row % L]
+    (csrc/sampler.hip).  Needed rows, step-0 sharing and final skip all on against all three off: the same ids."""
+    from esmdiff_amd.schedule import ddpm_schedule
+    sch = ddpm_schedule(T, eps=0.3)
+    g = torch.Generator().manual_seed(B * 1000 + L + 1)
+    seq = _seq(B, L, g).cuda()
+    prior = _priors(B, L, g)["every_second"][:1].repeat(B, 1)
+    try:
+        want, c_off, t_off = _sample(eng, seq, sch, prior, False)
+        eng.set_step0_sharing(True)
+        eng.set_final_skip(True)
+        got, c_on, t_on = _sample(eng, seq, sch, prior, True)
+    finally:
+        eng.set_step0_sharing(False)
+        eng.set_final_skip(False)
+        eng.set_needed_rows(True)
+    assert torch.equal(got, want), (B, L, int((got != want).sum()))
+    assert c_off["token_rows"] == t_off == (T + 1) * B * L
+    if (B, L) == (24, 258):
+        assert eng.shared_forward_batch(B, L) < B
+        assert c_on["token_rows"] < (T + 1) * B * L, c_on       # step 0 ran on the shared sub-batch
+        assert t_on < c_on["token_rows"], (t_on, c_on)          # and its tail on the masked rows of that sub-batch
+
+
 def test_ids_bit_identical_ragged(eng):
     """A ragged batch (set_lengths): padding rows hold the pad id, never MASK, and drop out of the row lists by themselves."""
     from esmdiff_amd.schedule import ddpm_schedule

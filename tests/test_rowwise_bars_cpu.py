@@ -149,6 +149,28 @@ def test_add_ln_bar_passes_the_rounded_reference_and_rejects_plants(dtype):
     assert not _passes(r[-1:]) and _passes(r[:-1])                            # only the low-variance row can tell
 
 
+def test_add_ln_bar_and_f16_subnormal_outputs():
+    """Why the LayerNorm cases keep their gains at or above rr.LN_MIN_GAIN: without a bias an f16 output under 2^-14 is subnormal
+    and rounds by up to 2^-25, which the bar's relative output term does not describe.  With a gain of 0.0036 in one column (what
+    1 + 0.3 randn gives at seed 1792) the float64 reference rounded to f16 — the best any f16 kernel can do — misses the bar; with
+    the gains of rr.ln_gains it passes, as does bfloat16 with either."""
+    M, D = 1027, 1792
+    g = torch.Generator().manual_seed(D)
+    w = 1 + 0.3 * torch.randn(D, generator=g)
+    assert 0.003 < float(w.abs().min()) < 0.004
+    x = torch.randn(M, D, generator=g) * 3 + torch.randn(M, 1, generator=g)
+    ref, unit = rr.add_ln_ref64(x, w, None)
+    r = rr.ratio(ref.half(), ref, torch.float16, rr.LN_COEF * unit)
+    assert not _passes(r) and float(ref.reshape(-1)[int(r.argmax())].abs()) < 2.0 ** -14
+    assert _passes(rr.ratio(ref.bfloat16(), ref, torch.bfloat16, rr.LN_COEF * unit))
+    wk = rr.ln_gains(D, torch.Generator().manual_seed(D))
+    assert float(wk.abs().min()) == rr.LN_MIN_GAIN and torch.equal(wk[w.abs() >= rr.LN_MIN_GAIN], w[w.abs() >= rr.LN_MIN_GAIN])
+    ref, unit = rr.add_ln_ref64(x, wk, None)
+    assert _passes(rr.ratio(ref.half(), ref, torch.float16, rr.LN_COEF * unit))
+    _, rstd, vmax = rr.ln64(x, wk)
+    assert float((rstd * vmax).min()) * rr.LN_MIN_GAIN >= 1 / 8                # the condition the floor was derived from
+
+
 # ---------------------------------------------------------------------------------------------------------------
 def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     """esmdiff_geom_attention / esmdiff_add_layernorm validate everything before their first HIP call, so these run
