@@ -68,6 +68,7 @@ EXPORTS = [
     "esmdiff_contact_map", "esmdiff_native_contacts",
     "esmdiff_backbone_torsions", "esmdiff_ramachandran",
     "esmdiff_shape_frames", "esmdiff_debye_frames",
+    "esmdiff_sasa_frames", "esmdiff_cooccurrence",
     "esmdiff_describe_gemm_choice", "esmdiff_gemm_workspace_floats",
     "esmdiff_dim6_to_backbone", "esmdiff_plddt_mean", "esmdiff_pair_features", "esmdiff_pae_tm",
     "esmdiff_decoder_set_pair_chunk_bytes",
@@ -87,6 +88,8 @@ CONTACT_MAX_L, CONTACT_TILE, CONTACT_MAX_CHUNKS = 4096, 64, 256    # ESMDIFF_CON
 RAMA_MAX_BINS = 72                           # ESMDIFF_RAMA_MAX_BINS
 SHAPE_MAX_L, SHAPE_MAX_BINS = 4096, 4096     # ESMDIFF_SHAPE_MAX_L, ESMDIFF_SHAPE_MAX_BINS
 DEBYE_MAX_Q, DEBYE_Q_CHUNK = 1024, 8         # ESMDIFF_DEBYE_MAX_Q, ESMDIFF_DEBYE_Q_CHUNK
+SASA_MAX_ATOMS, SASA_MAX_POINTS = 4096, 1024    # ESMDIFF_SASA_MAX_ATOMS, ESMDIFF_SASA_MAX_POINTS
+COOCC_MAX_L = 32768                          # ESMDIFF_COOCC_MAX_L
 
 CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
@@ -144,6 +147,11 @@ def rama_scratch_bytes(n: int, L: int) -> int:
 def shape_waves(L: int) -> int:
     """ESMDIFF_SHAPE_WAVES: the waves that share one frame in esmdiff_shape_frames / esmdiff_debye_frames; their sums' order follows it."""
     return 1 if L <= 128 else 8
+
+
+def coocc_scratch_bytes(n: int, L: int) -> int:
+    """ESMDIFF_COOCC_SCRATCH_BYTES: the scratch esmdiff_cooccurrence needs: a word per residue and 64 frames, in two planes."""
+    return ((n + 63) // 64) * L * 16
 
 
 def lib_path() -> Path:
@@ -236,6 +244,8 @@ def lib():
     L.esmdiff_ramachandran.argtypes = [vp, i32, i32, i32, vp, f64, i32, vp, vp, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_shape_frames.argtypes = [vp, i32, i32, vp, vp, vp, vp, f64, i32, vp]
     L.esmdiff_debye_frames.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp]
+    L.esmdiff_sasa_frames.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, f64, vp, vp, vp, vp, vp, vp, vp]
+    L.esmdiff_cooccurrence.argtypes = [vp, i32, i32, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_encoder_create.argtypes = [i32] * 9 + [ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.esmdiff_encoder_destroy.argtypes = [vp]
     L.esmdiff_encoder_destroy.restype = None

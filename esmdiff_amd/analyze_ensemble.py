@@ -5,6 +5,7 @@
                                            [--contacts] [--contact_cutoff 8.0] [--contact_min_sep 3]
                                            [--torsions] [--rama_bins 36]
                                            [--shape] [--pr_bins 100] [--saxs] [--saxs_qmax 0.5] [--saxs_points 51] [--saxs_data FILE]
+                                           [--sasa] [--sasa_points 96] [--sasa_probe 1.4] [--sasa_threshold 0.2]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
@@ -52,7 +53,13 @@ each target fills one cell per quantity).
 scatterers at the CA positions, i0, the normalised curve, the Guinier fit (rg, i0, q_max, n_points) beside the coordinate Rg, and the
 dimensionless Kratky curve.  --saxs_data FILE (three whitespace-separated columns q, I, sigma; lines starting with # are ignored;
 implies --saxs) evaluates at the file's q instead and adds chi2_mean, the reduced chi^2 of the mean profile after the least-squares
-scale, and chi2_samples: that of every sample, with the best one."""
+scale, and chi2_samples: that of every sample, with the best one.
+--sasa adds a "sasa" block (esmdiff_amd/accessibility.py, csrc/sasa.hip; Shrake & Rupley on N / CA / C and the inferred O, parity with
+NACCESS / freesasa / mdtraj unpinned): the parameters (--sasa_points, --sasa_probe, --sasa_threshold, the radii), per residue the mean
+area, the mean relative exposure and the share of samples in which it is exposed, per sample the total area with its summary, per target
+its own per-residue values and exposed_jaccard (the Jaccard index of the residues the target exposes and those the samples expose in
+more than half of their frames) and, with exactly two targets, exposure_switches: the residues exposed in one target only, with the
+samples' frequency of each.  Samples and targets are read again as N / CA / C backbones, on the analysed subset."""
 from __future__ import annotations
 
 import argparse
@@ -61,7 +68,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import contacts, ensemble, flexibility, secondary, shape, torsions
+from . import accessibility, contacts, ensemble, flexibility, secondary, shape, torsions
 from .pdbio import load_coords, read_pdb_backbone, read_pdb_bfactors
 
 
@@ -160,6 +167,15 @@ def saxs_report(samples_path, target_paths, max_models: int = 100, seed: int = 0
     return shape.saxs_report(samples, q_max, points, None if data is None else shape.read_saxs_data(data))
 
 
+def sasa_report(samples_path, target_paths, keep=None, points: int = 96, probe: float = 1.4, threshold: float = 0.2) -> dict:
+    """The --sasa block: the files read again as N / CA / C backbones (`keep`: the analysed subset of the samples' models), O inferred."""
+    backbones = load_coords(Path(samples_path), max_n_model=None, ca_only=False, verbose=False)
+    if keep is not None:
+        backbones = backbones[keep]
+    targets = [load_coords(Path(p), max_n_model=None, ca_only=False, verbose=False)[0] for p in target_paths]
+    return accessibility.report(backbones, targets, points, probe, threshold)
+
+
 def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0,
             flex: bool = False, pca_components: int = 3, dssp: bool = False) -> dict:
     samples, targets, n_all, keep = load_ca(samples_path, target_paths, max_models, seed)
@@ -208,6 +224,10 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--saxs_qmax", type=float, default=0.5, help="the largest q of the --saxs profile (1 / Angstrom)")
     ap.add_argument("--saxs_points", type=int, default=51, help="values of q of the --saxs profile, from 0 to --saxs_qmax")
     ap.add_argument("--saxs_data", default=None, help="a measured curve (columns q, I, sigma): evaluate at its q and add the reduced chi^2")
+    ap.add_argument("--sasa", action="store_true", help="add the backbone's solvent accessibility: areas, relative exposure, exposed frequency")
+    ap.add_argument("--sasa_points", type=int, default=96, help="points on every atom's sphere of the --sasa point test (1 to 1024)")
+    ap.add_argument("--sasa_probe", type=float, default=1.4, help="probe radius of --sasa (Angstrom)")
+    ap.add_argument("--sasa_threshold", type=float, default=0.2, help="relative exposure above which --sasa calls a residue exposed")
     return ap
 
 
@@ -224,6 +244,9 @@ def main(argv=None) -> Path:
         report["shape"] = shape_report(args.samples, args.targets, args.max_models, args.seed, args.pr_bins)
     if args.saxs or args.saxs_data:
         report["saxs"] = saxs_report(args.samples, args.targets, args.max_models, args.seed, args.saxs_qmax, args.saxs_points, args.saxs_data)
+    if args.sasa:
+        keep = load_ca(args.samples, args.targets, args.max_models, args.seed)[3]
+        report["sasa"] = sasa_report(args.samples, args.targets, keep, args.sasa_points, args.sasa_probe, args.sasa_threshold)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

@@ -1,5 +1,5 @@
 """The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
-csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip and csrc/shape.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip, csrc/shape.hip and csrc/sasa.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
 on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
 host-facing layers above it.
 Row blocks are contiguous slices (A[r0:r1]): a slice carries its own pointer, dtype and shape.  There is no CPU fallback."""
@@ -261,6 +261,49 @@ def debye_frames(X, mask, q, ff=None):
                             f"is staged in LDS; {N.DEBYE_MAX_Q} values of q a call); there is no slow path",
            invalid=lambda: f"esmdiff_debye_frames: invalid argument: L = {L} (at least 1), Q = {Q} (at least 1)")
     return intensity
+
+
+SASA_OUTPUTS = ("count", "sum_count", "valid", "exposed", "exposed_count", "present_count")
+
+
+def sasa_frames(X, mask, radii, points, threshold: float = 0.0, want=SASA_OUTPUTS) -> dict:
+    """One esmdiff_sasa_frames call: X f64 (n, L, A, 3) with A = 1, 3 or 4, mask u8 (n, L) or None, radii f64 (L, A) already expanded by
+    the probe and points f64 (P, 3), all on the device -> {name: tensor} for the names in `want`: count i32 (n, L, A) (-1 for an absent
+    atom), sum_count i64 (L, A), valid i32 (L, A), exposed u8 (n, L) (0, 1, or 2 for a residue without atoms), exposed_count and
+    present_count i32 (L,).  What is not wanted is never allocated."""
+    assert X.dim() == 4 and X.shape[3] == 3 and X.dtype == torch.float64, f"f64 (n, L, A, 3) atoms, got {X.dtype} {tuple(X.shape)}"
+    n, L, A = X.shape[:3]
+    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    assert radii.dtype == torch.float64 and radii.is_cuda and tuple(radii.shape) == (L, A), f"the radii are f64 ({L}, {A}) on the device"
+    assert points.dim() == 2 and points.shape[1] == 3 and points.dtype == torch.float64 and points.is_cuda, "the points are f64 (P, 3) on the device"
+    P = points.shape[0]
+    assert set(want) <= set(SASA_OUTPUTS), f"outputs are {SASA_OUTPUTS}"
+    shapes = {"count": ((n, L, A), torch.int32), "sum_count": ((L, A), torch.int64), "valid": ((L, A), torch.int32),
+              "exposed": ((n, L), torch.uint8), "exposed_count": ((L,), torch.int32), "present_count": ((L,), torch.int32)}
+    res = {k: _new(*shapes[k]) for k in want}
+    code = N.lib().esmdiff_sasa_frames(_p(X), n, L, A, _p(mask), _p(radii), _p(points), P, float(threshold),
+                                       *[_p(res.get(k)) for k in SASA_OUTPUTS], _stream())
+    _check("esmdiff_sasa_frames", code,
+           capacity=lambda: f"esmdiff_sasa_frames: {L} x {A} atoms or P = {P} is beyond the kernel's limits ({N.SASA_MAX_ATOMS} atoms: a "
+                            f"frame is staged in LDS; {N.SASA_MAX_POINTS} points); there is no slow path",
+           invalid=lambda: f"esmdiff_sasa_frames: invalid argument: L = {L} (at least 1), A = {A} (1, 3 or 4), P = {P} (at least 1), "
+                           f"threshold = {threshold} (not NaN)")
+    return res
+
+
+def cooccurrence(flags):
+    """One esmdiff_cooccurrence call: flags u8 (n, L) on the device, 0 or 1 and anything else undefined -> out i32 (3, L, L): the frames
+    where a and b are both defined, of those the frames where a is 1, and where both are 1."""
+    assert flags.dim() == 2 and flags.dtype == torch.uint8 and flags.is_cuda, f"u8 (n, L) flags on the device, got {flags.dtype} {tuple(flags.shape)}"
+    n, L = flags.shape
+    out = _new((3, L, L), torch.int32)
+    size = N.coocc_scratch_bytes(n, L)
+    scratch = _new((size // 8,), torch.int64) if size else None
+    code = N.lib().esmdiff_cooccurrence(_p(flags), n, L, _p(out), _p(scratch), size, _stream())
+    _check("esmdiff_cooccurrence", code,
+           capacity=lambda: f"esmdiff_cooccurrence: L = {L} is beyond the entry's limit ({N.COOCC_MAX_L} residues)",
+           invalid=lambda: f"esmdiff_cooccurrence: invalid argument: L = {L} (at least 1)")
+    return out
 
 
 def adjacency(n: int) -> torch.Tensor:

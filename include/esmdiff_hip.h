@@ -808,6 +808,53 @@ int esmdiff_shape_frames(const double* X, int32_t n, int32_t L, const uint8_t* m
 int esmdiff_debye_frames(const double* X, int32_t n, int32_t L, const uint8_t* mask, const double* q, int32_t Q, const double* ff,
                          double* intensity, void* stream);
 
+/* Solvent accessibility of every frame of an ensemble of backbones by the point test of Shrake & Rupley 1973, and the co-occurrence
+ * counts of a table of two-state flags (float64 coordinates in Angstrom, device pointers in and out; each call synchronises `stream`):
+ * DESIGN.md §3.26, held exactly to the numpy restatement tests/sasa_ref.py.  (An addition; the ABI number stays.)  Parity with
+ * NACCESS / freesasa / mdtraj is unpinned: only the definition below is tested.
+ *
+ * esmdiff_sasa_frames: X f64 [n, L, A, 3] with A = 1, 3 or 4 atoms a residue; mask u8 [n, L] or NULL (all given); radii f64 [L, A], the
+ * radius of every atom ALREADY EXPANDED by the probe; points f64 [P, 3], the unit points of the test sphere (the entry evaluates no
+ * cosine: esmdiff_amd.accessibility.sphere_points makes the golden-section spiral in numpy).  An atom is ABSENT in a frame when its
+ * residue is masked or one of its coordinates is NaN: it has no count and buries nothing, and a masked coordinate is never read.
+ * Point k of atom i with centre c and radius R is p = c + R u_k, one product and one add per component with no FMA; it is BURIED
+ * when some other atom j present in the frame has ((dx dx + dy dy) + dz dz) < R_j R_j, d = p - c_j, strictly; atoms of the same
+ * residue and bonded neighbours are ordinary neighbours; an atom is never tested against itself.  The kernel culls candidates
+ * conservatively (csrc/sasa.hip argues the margin): no count depends on it.  Outputs, each may be NULL, each one that is not is
+ * written in full and the caller zeroes nothing:
+ *   count         i32 [n, L, A]  the exposed points of the atom, -1 for an absent atom
+ *   sum_count     i64 [L, A]     the sum of count over the frames where the atom is present
+ *   valid         i32 [L, A]     the number of those frames
+ *   exposed       u8  [n, L]     2 when no atom of the residue is present; else, with the atom area (s c) / P, s = 12.566370614359172
+ *                                (R R), c the count as float64, the residue area ((a0 + a1) + a2) + a3 over its present atoms and the
+ *                                same sum with every c = P, 1 when area / that sum > threshold and 0 when not: one division, one
+ *                                comparison
+ *   exposed_count i32 [L]        the frames with flag 1
+ *   present_count i32 [L]        the frames with flag 0 or 1
+ * The reductions over frames are integer atomics; memory for them is O(L A) whatever n is.  n == 0 zeroes the four ensemble outputs.
+ * A NULL input, n < 0, L < 1, A not 1, 3 or 4, P < 1, or a NaN threshold with one of the last three outputs return ESMDIFF_E_INVALID;
+ * L A > ESMDIFF_SASA_MAX_ATOMS (one frame's x, y, z, R planes and its counts, 144 KiB, have to fit in LDS) or
+ * P > ESMDIFF_SASA_MAX_POINTS return ESMDIFF_E_CAPACITY; both before anything is launched or written.  Coordinates and radii are
+ * assumed below 1e150 in magnitude (no square overflows).
+ *
+ * esmdiff_cooccurrence: flags u8 [n, L], 0 or 1, anything else undefined (2 above) -> out i32 [3, L, L]:
+ *   out[0][a][b]  the frames in which a and b are both defined
+ *   out[1][a][b]  of those, the frames in which a is 1
+ *   out[2][a][b]  of those, the frames in which both are 1
+ * Nothing in it knows about exposure.  A first pass packs 64 frames into a word per residue by ballot (a plane of ones and a plane
+ * of defined), a second ANDs the words of a and b and counts bits.  scratch: ESMDIFF_COOCC_SCRATCH_BYTES(n, L) bytes on the device,
+ * 8-byte aligned, need not be zeroed; a smaller scratch_bytes returns ESMDIFF_E_CAPACITY, as does L > ESMDIFF_COOCC_MAX_L.  n == 0
+ * needs no scratch (it may be NULL) and gives zeros.  NULL flags or out, a NULL scratch where one is needed, n < 0, L < 1 return
+ * ESMDIFF_E_INVALID.  A refused call writes nothing. */
+#define ESMDIFF_SASA_MAX_ATOMS 4096
+#define ESMDIFF_SASA_MAX_POINTS 1024
+#define ESMDIFF_COOCC_MAX_L 32768
+#define ESMDIFF_COOCC_SCRATCH_BYTES(n, L) ((((int64_t)(n) + 63) / 64) * (int64_t)(L) * 16)
+int esmdiff_sasa_frames(const double* X, int32_t n, int32_t L, int32_t A, const uint8_t* mask, const double* radii, const double* points,
+                        int32_t P, double threshold, int32_t* count, int64_t* sum_count, int32_t* valid, uint8_t* exposed,
+                        int32_t* exposed_count, int32_t* present_count, void* stream);
+int esmdiff_cooccurrence(const uint8_t* flags, int32_t n, int32_t L, int32_t* out, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
