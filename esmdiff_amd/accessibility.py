@@ -35,11 +35,8 @@ does) or A = 1 (CA only: there is no default radius, the caller gives one).  A t
 removes whole residues.  Results are numpy on the host.  There is no CPU fallback."""
 from __future__ import annotations
 
-import ctypes
 import math
-import os
 from dataclasses import dataclass
-from pathlib import Path
 from typing import Optional
 
 import numpy as np
@@ -48,7 +45,7 @@ import torch
 from . import _native as N
 from . import pairs
 from .flexibility import flexibility_correlation
-from .secondary import infer_oxygen
+from .metrics import js_columns
 
 DEFAULT_RADII = (1.65, 1.87, 1.76, 1.40)     # N, CA, C, O: a stated convention (united-atom radii), not a pinned program
 PROBE, POINTS, THRESHOLD = 1.4, 96, 0.2
@@ -71,18 +68,8 @@ def sphere_points(P: int) -> np.ndarray:
 
 def atom_array(backbone) -> np.ndarray:
     """-> float64 (n, L, A, 3) on the host with A = 4 or 1 (the module's text states what is accepted)."""
-    if isinstance(backbone, (str, os.PathLike)):
-        from .pdbio import load_coords
-        backbone = load_coords(Path(backbone), max_n_model=None, ca_only=False, verbose=False)
-    x = backbone.detach().cpu().numpy() if torch.is_tensor(backbone) else np.asarray(backbone)
-    x = np.asarray(x, np.float64)
-    if x.ndim == 3:
-        x = x[None] if x.shape[1] in (1, 3, 4) else x[:, :, None, :]
-    if x.ndim != 4 or x.shape[2] not in (1, 3, 4) or x.shape[3] != 3 or x.shape[1] == 0:
-        raise AssertionError(f"atoms should be (n, L, A, 3) with A = 4 (N, CA, C, O), 3 (N, CA, C) or 1 (CA), got {tuple(x.shape)}")
-    if x.shape[2] == 3:
-        x = np.concatenate([x, infer_oxygen(x)[:, :, None]], axis=2)
-    return np.ascontiguousarray(x)
+    return pairs.atoms(backbone, (1, 3, 4), infer_o=True, ca_traces=True,
+                       what="atoms should be (n, L, A, 3) with A = 4 (N, CA, C, O), 3 (N, CA, C) or 1 (CA)")
 
 
 def expanded_radii(radii, probe: float, L: int, A: int) -> np.ndarray:
@@ -118,16 +105,11 @@ def _residue_sum(a: np.ndarray) -> np.ndarray:
 
 def _device_args(backbone, radii, probe, points, mask):
     """-> X f64 (n, L, A, 3), mask u8 or None, expanded radii (L, A) and points (P, 3) on the device, and the last two on the host."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("esmdiff_amd.accessibility needs an MI355X (gfx950); there is no CPU fallback")
+    pairs.need_device("esmdiff_amd.accessibility")
     x = atom_array(backbone)
     n, L, A = x.shape[:3]
     R, u = expanded_radii(radii, probe, L, A), sphere_points(points)
-    mk = None
-    if mask is not None:
-        m = (mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)).astype(bool)
-        given = np.broadcast_to(m[None] if m.ndim == 1 else m, (n, L))
-        mk = None if given.all() else torch.as_tensor(np.ascontiguousarray(given, dtype=np.uint8), device="cuda")
+    mk = pairs.given_mask(mask, n, L)[1]
     return torch.as_tensor(x, device="cuda"), mk, torch.as_tensor(R, device="cuda"), torch.as_tensor(u, device="cuda"), R, u
 
 
@@ -296,19 +278,7 @@ def js_sasa(ensembles, ref_key: str = "target", n_bins: int = 50, rounded: bool 
     """{name: JS distance} between the distribution of the total area over the frames of each ensemble of `ensembles` and over those
     of ensembles[ref_key] — js_rg's conventions (bins spanning the reference's range, pseudo count 1e-6, rounded to 4 decimals, the
     reference against itself 0), through the same esmdiff_metrics_js_columns."""
-    lib = N.lib()
-    cols = {k: torch.as_tensor(np.ascontiguousarray(sasa(v, **kw).total()[:, None]), device="cuda") for k, v in ensembles.items()}
-    ref, res = cols[ref_key], {}
-    for k, v in cols.items():
-        if k == ref_key:
-            continue
-        value = ctypes.c_double(0.0)
-        code = lib.esmdiff_metrics_js_columns(pairs._p(v), v.shape[0], None, pairs._p(ref), ref.shape[0], None, 1, int(n_bins), 0,
-                                              ctypes.byref(value), pairs._stream())
-        pairs._check("esmdiff_metrics_js_columns", code)
-        res[k] = float(np.around(value.value, decimals=4)) if rounded else float(value.value)
-    res[ref_key] = 0.0
-    return res
+    return js_columns({k: sasa(v, **kw).total() for k, v in ensembles.items()}, ref_key, n_bins, rounded)
 
 
 def _summary(v: np.ndarray) -> dict:

@@ -50,6 +50,7 @@ UNITS = {
     "superpose": [],          # float64 only: the shipped code objects hold no packed op (the scan of tests/test_host_cpu.py passes without geom's flags)
     "cluster": [],            # integers only (ballots, popcounts, LDS atomics)
     "flex": [],               # float64 only, as superpose (csrc/ed_kabsch.h is shared with it)
+    # lddt and contacts share the native-pair scan of csrc/ed_native_pairs.h; csrc/ed_f64.h's dist and sq3 take the bits of the unit's flag
     "lddt": ["-ffp-contract=off"],       # float64 distances, integer counts, equal to numpy's: no FMA (tests/lddt_ref.py)
     "dssp": ["-ffp-contract=off"],       # float64 hydrogen-bond energies with numpy's bits, integer codes (tests/dssp_ref.py)
     "contacts": ["-ffp-contract=off"],   # float64 distances and sums in a fixed order, integer counts, numpy's bits (tests/contacts_ref.py)

@@ -90,8 +90,7 @@ def cluster_matrix(d, cutoff: float, larger_is_closer: bool = False, block_rows:
         raise ValueError(f"cluster_matrix takes a square matrix, got {shape}")
     n = int(shape[0])
     _check_n(n, "cluster_matrix")
-    if not torch.cuda.is_available():
-        raise RuntimeError("esmdiff_amd.clustering needs an MI355X (gfx950); there is no CPU fallback")
+    pairs.need_device("esmdiff_amd.clustering")
     if not torch.is_tensor(d):
         d = np.asarray(d)
     adj = pairs.adjacency(n)

@@ -18,34 +18,25 @@
 //   contact_fold_kernel    one thread per element (a, b) of the L x L maps adds the chunk partials in increasing chunk index
 //                          (s = part[0]; s += part[1]; ...), reading the tile of (min, max) for the lower triangle.
 //                          Both write 0 where |a - b| < min_sep.
-//   native_contacts_kernel the layout of lddt_pairs_kernel: one WORKGROUP of 8 waves per (tile of <= 8 models, native j, chunk of rows),
-//                          the tile staged in LDS as planes with masked residues as NaN, a wave per row a, the native's contacts of
-//                          the row found 64 candidates at a time (one ballot) and compacted into the wave's ring as (b, lambda d0);
-//                          full waves then score the ring against every model of the tile.  kept / total are zeroed by the entry and
-//                          summed with integer atomics; the per-residue outputs have one writer each.
-//                          q_soft (SOFT = true) is summed without atomics in this order, a function of L alone: the k-th contact of
-//                          row a (increasing b) goes to lane k % 64, which adds its terms in increasing k; the 64 lane sums are
-//                          combined by the xor butterfly of ed_wave.h (offsets 32, 16 .. 1); wave w adds the row sums of rows
-//                          a = w, w + 8, w + 16 ... in that order; the eight wave sums are combined as
+//   native_contacts_kernel the native-pair scan of ed_native_pairs.h, the layout of lddt_pairs_kernel, with the contacts policy: the pair
+//                          filter is min_sep and cutoff, the ring holds lambda d0 (one product), and a pair is kept when d < lambda d0.
+//                          q_soft (SOFT = true) is the scan's float64 sum of 1 / (1 + exp(beta (d - lambda d0))), a pair whose model
+//                          residue is missing adding 0, summed without atomics in the order stated there: lanes, butterfly, rows
+//                          a = w, w + 8, w + 16 ... per wave; the eight wave sums are then combined as
 //                          ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)).  With q_soft the rows are therefore never split over
-//                          workgroups (one row chunk).  A pair whose model residue is missing adds 0.
+//                          workgroups (one row chunk).
 #include <math.h>
 
-#include "ed_wave.h"
-#include "kernels.h"
+#include "ed_native_pairs.h"
 
 namespace ed {
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int CM_TILE = ESMDIFF_CONTACT_TILE;          // 64 residues a side
 constexpr int CM_THREADS = 256, CM_GRID = 16, CM_BLOCK = CM_TILE / CM_GRID;   // 16 x 16 threads, 4 x 4 pairs each
 constexpr int CM_FRAMES = 8;                           // frames staged per barrier pair: 2 strips x 8 x 3 x 64 f64 = 24 KiB
 constexpr int CM_CELLS = CM_TILE * CM_TILE;
 static_assert(CM_BLOCK == 4 && CM_GRID * CM_GRID == CM_THREADS, "the thread grid covers the tile");
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 struct CmArgs {
   const double* X;
@@ -103,7 +94,7 @@ __global__ __launch_bounds__(CM_THREADS) void contact_map_kernel(const CmArgs p)
 #pragma unroll
         for (int j = 0; j < CM_BLOCK; ++j) {
           const double dx = b[j][0] - a[i][0], dy = b[j][1] - a[i][1], dz = b[j][2] - a[i][2];
-          const double d2 = (dx * dx + dy * dy) + dz * dz;
+          const double d2 = sq3(dx, dy, dz);
           const double d = sqrt(d2);
           const bool ok = d == d;                      // NaN: a residue of the pair is missing in this frame
           valid[i][j] += ok ? 1 : 0;
@@ -167,142 +158,45 @@ __global__ __launch_bounds__(256) void contact_fold_kernel(const CmArgs p) {
 }
 
 // ---- native contacts -------------------------------------------------------------------------------------------------------------
-constexpr int NC_TILE = 8;                             // models per workgroup
-constexpr int NC_THREADS = 512, NC_WAVES = NC_THREADS / 64;
-constexpr int NC_RING = 128;                           // pairs a wave can hold: fewer than 64 waiting + the 64 of one step
-constexpr int NC_MODEL_LDS = 144 * 1024;               // dynamic LDS for the tile; the rings and the wave sums take 12.5 KiB of the CU's 160 KiB
-static_assert(24 * ESMDIFF_CONTACT_MAX_L <= NC_MODEL_LDS, "one model of the longest chain fits");
+static_assert(24 * ESMDIFF_CONTACT_MAX_L <= NP_MODEL_LDS, "one model of the longest chain fits");
 
-struct NcArgs {
-  const double *A, *B;
-  const uint8_t *maskA, *maskB;
-  int32_t *kept, *total, *kept_res, *total_res;
+struct NcArgs : NativePairArgs {
+  int min_sep;                                           // first: with it last native_contacts_kernel<false> measured 1 - 1.6 % slower (EXPERIMENTS.md)
   double* q_soft;
   double cutoff, lambda, beta;
-  int n, m, L, tile, tiles, min_sep;
 };
 
-__device__ __forceinline__ double dist(double dx, double dy, double dz) { return sqrt((dx * dx + dy * dy) + dz * dz); }
-
-// grid (model tiles x m, row chunks; one row chunk with SOFT).  Dynamic LDS: f64 [tile][3][L].
-template <bool SOFT>
-__global__ __launch_bounds__(NC_THREADS) void native_contacts_kernel(const NcArgs p) {
-  extern __shared__ double s_model[];
-  __shared__ double s_ld[NC_WAVES][NC_RING];
-  __shared__ int s_b[NC_WAVES][NC_RING];
-  __shared__ double s_q[NC_WAVES][NC_TILE];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = p.L;
-  const int first_tile = blockIdx.x % p.tiles == 0;        // the one tile of native j that reports the native's own counts
-  const int j = blockIdx.x / p.tiles, i0 = (blockIdx.x % p.tiles) * p.tile;
-  const int tm = min(p.tile, p.n - i0);
-
-  for (int i = 0; i < tm; ++i) {
-    const double* src = p.A + (int64_t)(i0 + i) * L * 3;
-    const uint8_t* mk = p.maskA ? p.maskA + (int64_t)(i0 + i) * L : nullptr;
-    for (int e = tid; e < 3 * L; e += NC_THREADS) {
-      const int b = e / 3, c = e - 3 * b;
-      s_model[(i * 3 + c) * L + b] = (mk && !mk[b]) ? quiet_nan() : src[e];
+template <bool WITH_SOFT>
+struct NcPolicy {
+  static constexpr bool SOFT = WITH_SOFT;
+  const NcArgs p;
+  __device__ int min_sep() const { return p.min_sep; }
+  __device__ double cutoff() const { return p.cutoff; }
+  __device__ double payload(double d0) const { return p.lambda * d0; }   // one float64 product
+  __device__ int score(double d, double ld, double& soft) const {
+    if (SOFT) {
+      const double term = 1.0 / (1.0 + exp(p.beta * (d - ld)));
+      soft = d == d ? term : 0.0;
     }
+    return d < ld ? 1 : 0;                                 // d is NaN for a masked model residue: never kept
   }
-  __syncthreads();
-
-  const double* Bj = p.B + (int64_t)j * L * 3;
-  const uint8_t* mb = p.maskB ? p.maskB + (int64_t)j * L : nullptr;
-  double* ring_ld = s_ld[wave];
-  int* ring_b = s_b[wave];
-  int ksum[NC_TILE] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double qsum[NC_TILE] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int tsum = 0;
-
-  for (int a = blockIdx.y * NC_WAVES + wave; a < L; a += NC_WAVES * gridDim.y) {   // a is the same in every lane of the wave
-    int acc[NC_TILE] = {0, 0, 0, 0, 0, 0, 0, 0};
-    double qacc[NC_TILE] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int head = 0, waiting = 0, trow = 0;
-
-    // every lane below `count` takes one waiting pair and scores it against the tile
-    auto score = [&](int count) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      const bool on = lane < count;
-      const int slot = (head + lane) & (NC_RING - 1);
-      const int b = on ? ring_b[slot] : a;
-      const double ld = on ? ring_ld[slot] : 0.0;
+  // one row chunk: this workgroup saw every row of native j
+  __device__ void finish(const double* sums, int i0, int tm, int j) const {
+    __shared__ double s_q[NP_TILE][NP_WAVES];
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0) {
 #pragma unroll
-      for (int i = 0; i < NC_TILE; ++i) {
-        if (i < tm) {
-          const double* M = s_model + (i * 3) * L;
-          const double d = dist(M[b] - M[a], M[L + b] - M[L + a], M[2 * L + b] - M[2 * L + a]);
-          acc[i] += (on && d < ld) ? 1 : 0;                // d is NaN for a masked model residue: never kept
-          if (SOFT) {
-            const double term = 1.0 / (1.0 + exp(p.beta * (d - ld)));
-            qacc[i] += (on && d == d) ? term : 0.0;
-          }
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    };
-
-    if (!mb || mb[a]) {
-      const double ax = Bj[3 * a], ay = Bj[3 * a + 1], az = Bj[3 * a + 2];
-      for (int b0 = 0; b0 < L; b0 += 64) {
-        const int b = b0 + lane;
-        const int sep = a > b ? a - b : b - a;
-        bool in = false;
-        double d0 = 0.0;
-        if (b < L && sep >= p.min_sep && (!mb || mb[b])) {
-          d0 = dist(Bj[3 * b] - ax, Bj[3 * b + 1] - ay, Bj[3 * b + 2] - az);
-          in = d0 < p.cutoff;
-        }
-        const u64 bits = __ballot(in);
-        if (!bits) continue;
-        if (in) {
-          const int slot = (head + waiting + __popcll(bits & ((1ull << lane) - 1))) & (NC_RING - 1);
-          ring_b[slot] = b;
-          ring_ld[slot] = p.lambda * d0;                   // one float64 product
-        }
-        const int found = __popcll(bits);
-        waiting += found;                                  // < 64 before, <= 127 now: the ring holds them
-        trow += found;
-        if (waiting >= 64) {
-          score(64);
-          head = (head + 64) & (NC_RING - 1);
-          waiting -= 64;
-        }
-      }
-      if (waiting > 0) score(waiting);
-    }
-
-#pragma unroll
-    for (int i = 0; i < NC_TILE; ++i) {
-      if (i < tm) {
-        const int r = wave_sum(acc[i]);
-        ksum[i] += r;
-        if (SOFT) qsum[i] += wave_sum(qacc[i]);
-        if (lane == 0 && p.kept_res) p.kept_res[((int64_t)(i0 + i) * p.m + j) * L + a] = r;
-      }
-    }
-    tsum += trow;
-    if (lane == 0 && first_tile && p.total_res) p.total_res[(int64_t)j * L + a] = trow;
-  }
-
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NC_TILE; ++i)
-      if (i < tm && ksum[i]) atomicAdd(&p.kept[(int64_t)(i0 + i) * p.m + j], ksum[i]);
-    if (first_tile && tsum) atomicAdd(&p.total[j], tsum);
-  }
-  if (SOFT) {                                              // one row chunk: this workgroup saw every row of native j
-    if (lane == 0) {
-#pragma unroll
-      for (int i = 0; i < NC_TILE; ++i) s_q[wave][i] = qsum[i];
+      for (int i = 0; i < NP_TILE; ++i) s_q[i][tid >> 6] = sums[i];
     }
     __syncthreads();
-    if (tid < tm)
-      p.q_soft[(int64_t)(i0 + tid) * p.m + j] = ((s_q[0][tid] + s_q[1][tid]) + (s_q[2][tid] + s_q[3][tid])) +
-                                                ((s_q[4][tid] + s_q[5][tid]) + (s_q[6][tid] + s_q[7][tid]));
+    if (tid < tm) p.q_soft[(int64_t)(i0 + tid) * p.m + j] = tree8(s_q[tid]);
   }
+};
+
+// one row chunk with SOFT
+template <bool SOFT>
+__global__ __launch_bounds__(NP_THREADS) void native_contacts_kernel(const NcArgs p) {
+  native_pair_scan(p, NcPolicy<SOFT>{p});
 }
 
 }  // namespace
@@ -354,22 +248,8 @@ int esmdiff_native_contacts(const double* A, int32_t n, const double* B, int32_t
   p.kept = kept, p.total = total, p.kept_res = kept_res, p.total_res = total_res, p.q_soft = q_soft;
   p.cutoff = cutoff, p.lambda = lambda, p.beta = beta;
   p.n = n, p.m = m, p.L = L, p.min_sep = min_sep;
-  p.tile = std::max(1, std::min(std::min(NC_TILE, (int)n), NC_MODEL_LDS / (24 * L)));
-  const int tiles = p.tiles = (n + p.tile - 1) / p.tile;
-  const int64_t groups = (int64_t)tiles * m;
-  if (groups > INT32_MAX) return ESMDIFF_E_CAPACITY;       // grid.x
-  // rows are split over workgroups only while the launch would leave CUs idle, and never with q_soft (its order of summation)
-  const int max_chunks = (L + NC_WAVES - 1) / NC_WAVES;
-  const int chunks = q_soft ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(max_chunks, 1024 / groups));
-  const int lds = p.tile * 24 * L;
-
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(kept, 0, (size_t)n * m * sizeof(int32_t), st) != hipSuccess) return ESMDIFF_E_HIP;
-  if (hipMemsetAsync(total, 0, (size_t)m * sizeof(int32_t), st) != hipSuccess) return ESMDIFF_E_HIP;
-  const auto kernel = q_soft ? native_contacts_kernel<true> : native_contacts_kernel<false>;
-  if (ensure_dynamic_lds((const void*)kernel, lds) != hipSuccess) return ESMDIFF_E_HIP;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)groups, chunks), dim3(NC_THREADS), (size_t)lds, st, p);
-  return finish_entry(st);
+  // never split over row chunks with q_soft (its order of summation)
+  return launch_native_pairs(q_soft ? native_contacts_kernel<true> : native_contacts_kernel<false>, p, !q_soft, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 //                        zeroed: two runs are bit-identical.
 #include <math.h>
 
+#include "ed_f64.h"
 #include "kernels.h"
 
 namespace ed {
@@ -46,8 +47,6 @@ struct DsspArgs {
   double* energy;
   int n, L;
 };
-
-__device__ __forceinline__ double dist(double dx, double dy, double dz) { return sqrt((dx * dx + dy * dy) + dz * dz); }
 
 __device__ __forceinline__ bool finite3(const double* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 
@@ -90,7 +89,7 @@ __global__ __launch_bounds__(DSSP_THREADS) void dssp_hbond_kernel(const DsspArgs
   const uint8_t* mk = p.mask ? p.mask + (int64_t)blockIdx.x * L : nullptr;
   int32_t* acc_out = p.acceptor + (int64_t)blockIdx.x * L * 2;
   double* en_out = p.energy + (int64_t)blockIdx.x * L * 2;
-  const double inf = __longlong_as_double(0x7ff0000000000000ll), nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double inf = __longlong_as_double(0x7ff0000000000000ll), nan = quiet_nan();
 
   for (int t0 = 0; t0 < L; t0 += tile) {
     const int tl = min(tile, L - t0);

@@ -34,6 +34,7 @@
 
 #include <cmath>
 
+#include "ed_f64.h"
 #include "ed_wave.h"
 #include "kernels.h"
 
@@ -49,9 +50,6 @@ constexpr double SA_MARGIN = 1e-6, SA_MARGIN_REL = 1.0 / 1099511627776.0;      /
 constexpr double SA_FOUR_PI = 12.566370614359172;          // 4.0 * math.pi
 static_assert(SA_ATOM_BYTES * ESMDIFF_SASA_MAX_ATOMS <= 144 * 1024, "the largest frame fits LDS");
 static_assert(SA_ATOM_BYTES * SA_SMALL * SA_WAVES <= 144 * 1024, "eight short frames fit LDS");
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ __forceinline__ double sq3(double dx, double dy, double dz) { return (dx * dx + dy * dy) + dz * dz; }
 
 struct SasaArgs {
   const double* X;
@@ -72,7 +70,8 @@ __global__ __launch_bounds__(SA_THREADS) void sasa_frames_kernel(const SasaArgs 
   extern __shared__ double s_planes[];
   const int L = p.L, A = p.A, NA = L * A, P = p.P;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int W = NA <= SA_SMALL ? 1 : SA_WAVES, teams = SA_WAVES / W, team = wave / W, w = wave % W, T = 64 * W, t = w * 64 + lane;
+  const WaveTeam g = wave_team(wave, NA <= SA_SMALL ? 1 : SA_WAVES, SA_WAVES);
+  const int W = g.W, teams = g.teams, team = g.team, w = g.w, T = g.T, t = w * 64 + lane;
   const int64_t frame0 = (int64_t)blockIdx.x * teams, frame = frame0 + team;
   const bool active = frame < p.n;
   double *sx = s_planes + (size_t)team * 4 * NA, *sy = sx + NA, *sz = sy + NA, *sr = sz + NA;

@@ -36,6 +36,7 @@
 
 #include <cmath>
 
+#include "ed_f64.h"
 #include "ed_wave.h"
 #include "kernels.h"
 
@@ -50,35 +51,21 @@ static_assert(SH_QCHUNK == 8, "eight sums per lane");
 static_assert(SH_WAVES == 8, "the fixed tree below combines eight wave sums");
 static_assert(24 * ESMDIFF_SHAPE_MAX_L + 4 * (ESMDIFF_SHAPE_MAX_BINS + 1) <= 144 * 1024, "the longest chain and the widest histogram fit LDS");
 
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ __forceinline__ double dist(double dx, double dy, double dz) { return sqrt((dx * dx + dy * dy) + dz * dz); }
-__device__ __forceinline__ double tree8(const double* s) { return ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7])); }
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double o = __shfl_xor(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
-// which frame this thread works on, and where in its team
-struct Team {
-  int W, frame, w, t, T, lane;
+// which frame this thread works on, where in its team (ed_wave.h), and the team's planes
+struct Team : WaveTeam {
+  int t, frame;
   double *x, *y, *z;
   bool active;
 };
 
 __device__ __forceinline__ Team team_of(double* planes, int n, int L) {
   Team m;
-  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  m.W = ESMDIFF_SHAPE_WAVES(L);
-  const int teams = SH_WAVES / m.W, team = wave / m.W;
-  m.w = wave % m.W, m.lane = tid & 63, m.T = 64 * m.W, m.t = m.w * 64 + m.lane;
-  m.frame = blockIdx.x * teams + team;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  static_cast<WaveTeam&>(m) = wave_team(wave, ESMDIFF_SHAPE_WAVES(L), SH_WAVES);
+  m.t = m.w * 64 + m.lane;
+  m.frame = blockIdx.x * m.teams + m.team;
   m.active = m.frame < n;
-  m.x = planes + (size_t)team * 3 * L, m.y = m.x + L, m.z = m.y + L;
+  m.x = planes + (size_t)m.team * 3 * L, m.y = m.x + L, m.z = m.y + L;
   return m;
 }
 

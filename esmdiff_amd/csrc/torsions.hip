@@ -23,6 +23,7 @@
 
 #include <cmath>
 
+#include "ed_f64.h"
 #include "kernels.h"
 
 namespace ed {
@@ -30,8 +31,6 @@ namespace {
 
 constexpr int TOR_THREADS = 256;
 constexpr double DEG = 57.29577951308232;
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 struct V3 {
   double x, y, z;

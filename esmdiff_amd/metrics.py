@@ -84,6 +84,19 @@ def js_rg(ca_coords_dict, ref_key: str = "target", n_bins: int = 50, weights: Op
     return _round(res, rounded)
 
 
+def js_columns(columns: dict, ref_key: str = "target", n_bins: int = 50, rounded: bool = True) -> Dict[str, float]:
+    """{name: 1-D finite values} -> {name: the Jensen-Shannon distance between the distribution of its values and of columns[ref_key]'s}
+    with js_rg's conventions (bins spanning the reference's range, pseudo count 1e-6, rounded to 4 decimals, the reference against
+    itself 0), through esmdiff_metrics_js_columns.  An empty column, and every column against an empty reference, gives NaN."""
+    L_ = N.lib()
+    dev = {k: torch.as_tensor(np.ascontiguousarray(v, dtype=np.float64)[:, None], device="cuda") for k, v in columns.items()}
+    ref = dev[ref_key]
+    res = {k: _call(L_.esmdiff_metrics_js_columns, _p(v), v.shape[0], None, _p(ref), ref.shape[0], None, 1, int(n_bins), 0)
+           if v.shape[0] and ref.shape[0] else float("nan") for k, v in dev.items() if k != ref_key}
+    res[ref_key] = 0.0
+    return _round(res, rounded)
+
+
 def pairwise_distance_ca(ca, k: int = 1) -> torch.Tensor:
     """eval_utils.py:90-102 on the device: (n, L, 3) -> (n, D) CA distances of the pairs (i, j >= i + k), triu order."""
     d = _dev(ca)

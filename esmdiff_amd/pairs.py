@@ -1,7 +1,8 @@
 """The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
 csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip, csrc/shape.hip and csrc/sasa.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
 on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
-host-facing layers above it.
+host-facing layers above it.  The frame-wise layers (secondary, torsions, accessibility) share one input stage here: need_device,
+atoms and given_mask; every frame-wise entry below asserts its input through _frames.
 Row blocks are contiguous slices (A[r0:r1]): a slice carries its own pointer, dtype and shape.  There is no CPU fallback."""
 from __future__ import annotations
 
@@ -19,10 +20,15 @@ LDDT_R0 = 15.0
 LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
 
 
+def need_device(what: str):
+    """The one refusal of a host without the device; what: the module or function that was called."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{what} needs an MI355X (gfx950); there is no CPU fallback")
+
+
 def coords(x, what: str = "coords") -> torch.Tensor:
     """A path (pdbio.load_coords), an array or a tensor -> float64 (n, L, 3) on the device."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("esmdiff_amd.ensemble needs an MI355X (gfx950); there is no CPU fallback")
+    need_device("esmdiff_amd.ensemble")
     if isinstance(x, (str, os.PathLike)):
         from .pdbio import load_coords
         x = load_coords(Path(x), max_n_model=None, verbose=False)
@@ -58,6 +64,35 @@ def pair_args(a, b, mask_a, mask_b):
     return A, B, ma, valid_mask(B, mask_b)
 
 
+def atoms(x, allowed, infer_o: bool = False, ca_traces: bool = False, what: str = "atoms should be (n, L, A, 3)") -> np.ndarray:
+    """The input stage of the frame-wise layers (secondary, torsions, accessibility).  x: a PDB path (N / CA / C of every MODEL), an
+    array or a tensor, (L, A, 3) or (n, L, A, 3) with A in `allowed` -> float64 (n, L, A, 3) on the host.  infer_o: A = 3 gains the
+    inferred carbonyl O (secondary.infer_oxygen) and leaves as A = 4.  ca_traces: a 3-D input whose middle axis is no atom count (1, 3
+    or 4) is (n, L, 3) CA traces and leaves as A = 1.  what: the text of the shape error, up to ", got"."""
+    if isinstance(x, (str, os.PathLike)):
+        from .pdbio import load_coords
+        x = load_coords(Path(x), max_n_model=None, ca_only=False, verbose=False)
+    x = np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, np.float64)
+    if x.ndim == 3:
+        x = x[:, :, None, :] if ca_traces and x.shape[1] not in (1, 3, 4) else x[None]
+    if x.ndim != 4 or x.shape[2] not in allowed or x.shape[3] != 3 or x.shape[1] == 0:
+        raise AssertionError(f"{what}, got {tuple(x.shape)}")
+    if infer_o and x.shape[2] == 3:
+        from .secondary import infer_oxygen
+        x = np.concatenate([x, infer_oxygen(x)[:, :, None]], axis=2)
+    return np.ascontiguousarray(x)
+
+
+def given_mask(mask, n: int, L: int):
+    """mask: (n, L) or (L,), an array or a tensor, or None -> the residues the caller gives as bool (n, L) on the host, and as u8 (n, L)
+    on the device, None when all are given."""
+    if mask is None:
+        return np.ones((n, L), bool), None
+    m = (mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)).astype(bool)
+    given = np.broadcast_to(m[None] if m.ndim == 1 else m, (n, L)).copy()
+    return given, None if given.all() else torch.as_tensor(given.astype(np.uint8), device="cuda")
+
+
 def _p(t: Optional[torch.Tensor]):
     assert t is None or t.is_contiguous(), "a row block should be a contiguous slice"
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
@@ -70,6 +105,17 @@ def _stream():
 def _sizes(A: torch.Tensor, B: Optional[torch.Tensor]):
     assert B is None or B.shape[1:] == A.shape[1:], f"structures of different lengths: {A.shape[1]} and {B.shape[1]}"
     return A.shape[0], (A if B is None else B).shape[0], A.shape[1]
+
+
+def _frames(X, mask, last):
+    """What every frame-wise entry asserts of its input: X is f64 (n, L) + last, where an entry of `last` is a size, a tuple of sizes
+    or None (any: the entry itself refuses), and mask is u8 (n, L) or None -> n, L."""
+    text = ", ".join("A" if d is None else " or ".join(map(str, d)) if isinstance(d, tuple) else str(d) for d in last)
+    fits = X.dim() == 2 + len(last) and all(d is None or s in (d if isinstance(d, tuple) else (d,)) for s, d in zip(X.shape[2:], last))
+    assert fits and X.dtype == torch.float64, f"f64 (n, L, {text}) frames, got {X.dtype} {tuple(X.shape)}"
+    n, L = X.shape[:2]
+    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    return n, L
 
 
 def _new(shape, dtype=torch.float64) -> torch.Tensor:
@@ -134,9 +180,7 @@ def lddt(A, B, ma, mb, r0: float = LDDT_R0, thresholds=LDDT_THRESHOLDS, seq_sep:
 def dssp(X, mask, no_donor, counts: bool = True):
     """One esmdiff_dssp call: X f64 (n, L, 4, 3) N / CA / C / O, mask u8 (n, L) or None, no_donor u8 (L,) or None -> ss u8 (n, L),
     counts i32 (L, 8) (None without `counts`), acceptor i32 (n, L, 2), energy f64 (n, L, 2)."""
-    assert X.dim() == 4 and tuple(X.shape[2:]) == (4, 3) and X.dtype == torch.float64, f"f64 (n, L, 4, 3) backbones, got {X.dtype} {tuple(X.shape)}"
-    n, L = X.shape[:2]
-    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    n, L = _frames(X, mask, (4, 3))
     assert no_donor is None or (no_donor.dtype == torch.uint8 and tuple(no_donor.shape) == (L,)), "no_donor is u8 (L,)"
     ss, table = _new((n, L), torch.uint8), _new((L, 8), torch.int32) if counts else None
     acceptor, energy = _new((n, L, 2), torch.int32), _new((n, L, 2))
@@ -149,9 +193,7 @@ def contact_map(X, mask, cutoff: float, min_sep: int, sums: bool = True):
     """One esmdiff_contact_map call: X f64 (n, L, 3), mask u8 (n, L) or None -> valid i32 (L, L), count i32 (L, L), and with `sums`
     sum_d, sum_d2 f64 (L, L) (else None, and never allocated).  The (n, L, L) distances are never stored: the scratch holds
     N.contact_chunks(n, L) partial tiles per tile of the triangle, and nothing when that is one chunk."""
-    assert X.dim() == 3 and X.shape[-1] == 3 and X.dtype == torch.float64, f"f64 (n, L, 3) coordinates, got {X.dtype} {tuple(X.shape)}"
-    n, L = X.shape[:2]
-    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    n, L = _frames(X, mask, (3,))
     valid, count = _new((L, L), torch.int32), _new((L, L), torch.int32)
     sum_d, sum_d2 = (_new((L, L)), _new((L, L))) if sums else (None, None)
     size = N.contact_scratch_bytes(n, L) if 2 <= L <= N.CONTACT_MAX_L and n >= 1 else 0
@@ -182,21 +224,13 @@ def native_contacts(A, B, ma, mb, cutoff: float, min_sep: int, lam: float, beta:
     return kept, total, kept_res, total_res, q_soft
 
 
-def _backbone_sizes(X, mask):
-    assert X.dim() == 4 and X.shape[2] in (3, 4) and X.shape[3] == 3 and X.dtype == torch.float64, \
-        f"f64 (n, L, 3 or 4, 3) backbones, got {X.dtype} {tuple(X.shape)}"
-    n, L, atoms = X.shape[:3]
-    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
-    return n, L, atoms
-
-
 def backbone_torsions(X, mask, break_distance: float, geometry: bool = False):
     """One esmdiff_backbone_torsions call: X f64 (n, L, 3 or 4, 3) N / CA / C (/ O, never read), mask u8 (n, L) or None -> phi, psi,
     omega f64 (n, L) in radians (NaN where undefined) and, with `geometry`, geom f64 (n, L, 6) (else None, and never allocated)."""
-    n, L, atoms = _backbone_sizes(X, mask)
+    n, L = _frames(X, mask, ((3, 4), 3))
     phi, psi, omega = _new((n, L)), _new((n, L)), _new((n, L))
     geom = _new((n, L, 6)) if geometry else None
-    code = N.lib().esmdiff_backbone_torsions(_p(X), n, L, atoms, _p(mask), float(break_distance), _p(phi), _p(psi), _p(omega), _p(geom),
+    code = N.lib().esmdiff_backbone_torsions(_p(X), n, L, X.shape[2], _p(mask), float(break_distance), _p(phi), _p(psi), _p(omega), _p(geom),
                                              _stream())
     _check("esmdiff_backbone_torsions", code,
            invalid=lambda: f"esmdiff_backbone_torsions: invalid argument: L = {L} (at least 1), break_distance = {break_distance} "
@@ -209,14 +243,14 @@ def ramachandran(X, mask, break_distance: float, bins: int, sums: bool = True):
     """One esmdiff_ramachandran call: X and mask as backbone_torsions takes them -> hist i32 (L, bins, bins), counts i32 (L, 5) and, with
     `sums`, sums f64 (L, 6) (else None, and never allocated).  No (n, L) angle array exists: the scratch holds N.rama_chunks(n, L)
     partial sums per residue, and nothing when that is one chunk."""
-    n, L, atoms = _backbone_sizes(X, mask)
+    n, L = _frames(X, mask, ((3, 4), 3))
     bins = int(bins)
     ok = 1 <= bins <= N.RAMA_MAX_BINS
     hist, counts = _new((L, bins, bins) if ok else (1,), torch.int32), _new((L, 5), torch.int32)     # not ok: the entry refuses, writes nothing
     out = _new((L, 6)) if sums else None
     size = N.rama_scratch_bytes(n, L) if sums else 0
     scratch = _new((size // 8,)) if size else None
-    code = N.lib().esmdiff_ramachandran(_p(X), n, L, atoms, _p(mask), float(break_distance), bins, _p(hist), _p(counts), _p(out),
+    code = N.lib().esmdiff_ramachandran(_p(X), n, L, X.shape[2], _p(mask), float(break_distance), bins, _p(hist), _p(counts), _p(out),
                                         _p(scratch), size, _stream())
     _check("esmdiff_ramachandran", code,
            capacity=lambda: f"esmdiff_ramachandran: bins = {bins} is beyond the kernel's limit ({N.RAMA_MAX_BINS} per axis)",
@@ -229,9 +263,7 @@ def shape_frames(X, mask, width: Optional[float] = None, bins: int = 0):
     """One esmdiff_shape_frames call: X f64 (n, L, 3), mask u8 (n, L) or None -> count i32 (n,), desc f64 (n, 12) (the centroid, the six
     sums of (r - c)(r - c)^T undivided, sum_inv_d, dmax, ree) and, with a `width`, hist i64 (bins + 1,): the pair distances of all frames
     in cells of that width, the last cell the overflow (else None, and never allocated)."""
-    assert X.dim() == 3 and X.shape[-1] == 3 and X.dtype == torch.float64, f"f64 (n, L, 3) coordinates, got {X.dtype} {tuple(X.shape)}"
-    n, L = X.shape[:2]
-    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    n, L = _frames(X, mask, (3,))
     count, desc = _new((n,), torch.int32), _new((n, 12))
     bins = int(bins)
     hist = None if width is None else _new((bins + 1 if 1 <= bins <= N.SHAPE_MAX_BINS else 1,), torch.int64)   # refused: nothing is written
@@ -248,9 +280,7 @@ def shape_frames(X, mask, width: Optional[float] = None, bins: int = 0):
 def debye_frames(X, mask, q, ff=None):
     """One esmdiff_debye_frames call: X f64 (n, L, 3), mask u8 (n, L) or None, q f64 (Q,) and ff f64 (L, Q) or None on the device ->
     intensity f64 (n, Q).  The entry does not look at q: its values are the caller's to check (esmdiff_amd/shape.py does)."""
-    assert X.dim() == 3 and X.shape[-1] == 3 and X.dtype == torch.float64, f"f64 (n, L, 3) coordinates, got {X.dtype} {tuple(X.shape)}"
-    n, L = X.shape[:2]
-    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    n, L = _frames(X, mask, (3,))
     assert q.dim() == 1 and q.dtype == torch.float64 and q.is_cuda, "q is f64 (Q,) on the device"
     Q = q.shape[0]
     assert ff is None or (ff.dtype == torch.float64 and ff.is_cuda and tuple(ff.shape) == (L, Q)), f"the form factors are f64 ({L}, {Q}) on the device"
@@ -271,9 +301,7 @@ def sasa_frames(X, mask, radii, points, threshold: float = 0.0, want=SASA_OUTPUT
     the probe and points f64 (P, 3), all on the device -> {name: tensor} for the names in `want`: count i32 (n, L, A) (-1 for an absent
     atom), sum_count i64 (L, A), valid i32 (L, A), exposed u8 (n, L) (0, 1, or 2 for a residue without atoms), exposed_count and
     present_count i32 (L,).  What is not wanted is never allocated."""
-    assert X.dim() == 4 and X.shape[3] == 3 and X.dtype == torch.float64, f"f64 (n, L, A, 3) atoms, got {X.dtype} {tuple(X.shape)}"
-    n, L, A = X.shape[:3]
-    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == (n, L)), "the mask is u8 (n, L)"
+    (n, L), A = _frames(X, mask, (None, 3)), X.shape[2]
     assert radii.dtype == torch.float64 and radii.is_cuda and tuple(radii.shape) == (L, A), f"the radii are f64 ({L}, {A}) on the device"
     assert points.dim() == 2 and points.shape[1] == 3 and points.dtype == torch.float64 and points.is_cuda, "the points are f64 (P, 3) on the device"
     P = points.shape[0]
@@ -330,12 +358,6 @@ def gromos(adj: torch.Tensor):
     return out, k
 
 
-def _flex_sizes(A: torch.Tensor, mask: Optional[torch.Tensor]):
-    assert A.dim() == 3 and A.shape[-1] == 3 and A.dtype == torch.float64, f"f64 (n, L, 3) coordinates, got {A.dtype} {tuple(A.shape)}"
-    assert mask is None or (mask.dtype == torch.uint8 and tuple(mask.shape) == tuple(A.shape[:2])), "the mask is u8 (n, L)"
-    return A.shape[0], A.shape[1]
-
-
 def _flex_invalid(entry: str, n: int, L: int):
     return lambda: f"{entry}: invalid argument: n = {n} (at least 1), L = {L} (at least 2)"
 
@@ -344,7 +366,7 @@ def pair_msf(A, ma):
     """One esmdiff_flex_pair_msf call -> sum_sq f64 (L,), count i64 (L,): over the pairs i < j of A (n, L, 3) fitted on the residues
     valid in both, the sum of each residue's squared deviation and the number of pairs it was valid in.  The (n, n, L) deviations are
     never stored: the scratch holds N.flex_pair_slots(n) partial sums per residue."""
-    n, L = _flex_sizes(A, ma)
+    n, L = _frames(A, ma, (3,))
     sum_sq, count = _new((L,)), _new((L,), torch.int64)
     size = N.flex_pair_slots(n) * L * 12
     scratch = _new((size // 4,), torch.int32)
@@ -357,7 +379,7 @@ def pair_msf(A, ma):
 def fit(A, ma, ref, mref):
     """One esmdiff_flex_fit call: every A[i] fitted onto ref (L, 3) on the residues valid in both (mref u8 (L,) or None) ->
     aligned f64 (n, L, 3) (the whole structure moved; a NaN coordinate stays NaN), rmsd f64 (n,).  Fewer than 2 common residues: NaN."""
-    n, L = _flex_sizes(A, ma)
+    n, L = _frames(A, ma, (3,))
     assert ref.dtype == torch.float64 and tuple(ref.shape) == (L, 3), f"the reference is f64 ({L}, 3), got {tuple(ref.shape)}"
     assert mref is None or (mref.dtype == torch.uint8 and tuple(mref.shape) == (L,)), "the reference's mask is u8 (L,)"
     aligned, rmsd = _new((n, L, 3)), _new((n,))
@@ -369,7 +391,7 @@ def fit(A, ma, ref, mref):
 def moments(X, mask):
     """One esmdiff_flex_moments call -> mean f64 (L, 3), msf f64 (L,), count i32 (L,): per residue, over the structures valid there,
     the mean position and the mean squared distance from it (NaN where count is 0)."""
-    n, L = _flex_sizes(X, mask)
+    n, L = _frames(X, mask, (3,))
     mean, msf, count = _new((L, 3)), _new((L,)), _new((L,), torch.int32)
     code = N.lib().esmdiff_flex_moments(_p(X), n, L, _p(mask), _p(mean), _p(msf), _p(count), _stream())
     _check("esmdiff_flex_moments", code, invalid=_flex_invalid("esmdiff_flex_moments", n, L))

@@ -14,9 +14,7 @@ placing it the same way on targets treats both alike.  With a crystal structure'
 25-27 are GGG with the file's O and TTT with the inferred one, 0.13 A apart in RMSD).  There is no CPU fallback."""
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
-from pathlib import Path
 from typing import Optional
 
 import numpy as np
@@ -53,18 +51,7 @@ def infer_oxygen(backbone) -> np.ndarray:
 def backbone_array(backbone) -> np.ndarray:
     """A PDB path (N / CA / C of every MODEL), an array or a tensor, (L, A, 3) or (n, L, A, 3) with A = 4 (N, CA, C, O) or A = 3 (O is
     inferred) -> float64 (n, L, 4, 3) on the host."""
-    if isinstance(backbone, (str, os.PathLike)):
-        from .pdbio import load_coords
-        backbone = load_coords(Path(backbone), max_n_model=None, ca_only=False, verbose=False)
-    x = backbone.detach().cpu().numpy() if torch.is_tensor(backbone) else np.asarray(backbone)
-    x = np.asarray(x, np.float64)
-    if x.ndim == 3:
-        x = x[None]
-    if x.ndim != 4 or x.shape[2] not in (3, 4) or x.shape[3] != 3 or x.shape[1] == 0:
-        raise AssertionError(f"backbones should be (n, L, 4, 3) N / CA / C / O or (n, L, 3, 3) N / CA / C, got {tuple(x.shape)}")
-    if x.shape[2] == 3:
-        x = np.concatenate([x, infer_oxygen(x)[:, :, None]], axis=2)
-    return np.ascontiguousarray(x)
+    return pairs.atoms(backbone, (3, 4), infer_o=True, what="backbones should be (n, L, 4, 3) N / CA / C / O or (n, L, 3, 3) N / CA / C")
 
 
 def reduce_codes(codes) -> np.ndarray:
@@ -123,20 +110,15 @@ class SecondaryStructure:
 def dssp(backbone, sequence: Optional[str] = None, mask=None) -> SecondaryStructure:
     """The DSSP states of every structure.  backbone: see backbone_array; sequence: one-letter codes, sets the no-donor flag of
     prolines (None: every residue's N carries an H); mask (n, L) or (L,): residues to leave out."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("esmdiff_amd.secondary needs an MI355X (gfx950); there is no CPU fallback")
+    pairs.need_device("esmdiff_amd.secondary")
     x = backbone_array(backbone)
     n, L = x.shape[:2]
-    given = np.ones((n, L), bool)
-    if mask is not None:
-        m = (mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)).astype(bool)
-        given = np.broadcast_to(m[None] if m.ndim == 1 else m, (n, L)).copy()
+    given, mk = pairs.given_mask(mask, n, L)
     no_donor = None
     if sequence is not None:
         assert len(sequence) == L, f"a sequence of {len(sequence)} residues for backbones of {L}"
         no_donor = torch.as_tensor(np.array([c == "P" for c in sequence], np.uint8), device="cuda")
     X = torch.as_tensor(x, device="cuda")
-    mk = None if given.all() else torch.as_tensor(given.astype(np.uint8), device="cuda")
     ss, counts, acceptor, energy = pairs.dssp(X, mk, no_donor)
     present = given & np.isfinite(x[:, :, :3]).all((2, 3))
     return SecondaryStructure(ss.cpu().numpy(), present, counts.cpu().numpy(), acceptor.cpu().numpy(), energy.cpu().numpy())

@@ -25,7 +25,6 @@ NaN coordinate is absent in that frame, `mask` (n, L) or (L,) removes more.  q i
 on the host.  There is no CPU fallback."""
 from __future__ import annotations
 
-import ctypes
 import math
 from dataclasses import dataclass
 from typing import Optional
@@ -35,6 +34,7 @@ import torch
 
 from . import _native as N
 from . import pairs
+from .metrics import js_columns
 
 QUANTITIES = ("rg", "asphericity", "acylindricity", "anisotropy", "ree", "dmax", "rh")
 
@@ -237,30 +237,9 @@ def js_shape(ensembles, ref_key: str = "target", quantities=("rg", "ree", "rh", 
     the frames of each ensemble of `ensembles` ({name: (n, L, 3)}) and over those of ensembles[ref_key] — js_rg's conventions (bins
     spanning the reference's range, pseudo count 1e-6, rounded to 4 decimals, the reference against itself 0), through the same
     esmdiff_metrics_js_columns.  Frames where a quantity is undefined are left out of it."""
-    lib = N.lib()
     desc = {k: frames(v) for k, v in ensembles.items()}
-    out = {}
-    for name in quantities:
-        cols = {}
-        for k, d in desc.items():
-            v = getattr(d, name)
-            cols[k] = torch.as_tensor(np.ascontiguousarray(v[np.isfinite(v)], dtype=np.float64)[:, None], device="cuda")
-        ref = cols[ref_key]
-        res = {}
-        for k, v in cols.items():
-            if k == ref_key:
-                continue
-            if v.shape[0] == 0 or ref.shape[0] == 0:
-                res[k] = float("nan")
-                continue
-            value = ctypes.c_double(0.0)
-            code = lib.esmdiff_metrics_js_columns(pairs._p(v), v.shape[0], None, pairs._p(ref), ref.shape[0], None, 1, int(n_bins), 0,
-                                                  ctypes.byref(value), pairs._stream())
-            pairs._check("esmdiff_metrics_js_columns", code)
-            res[k] = float(np.around(value.value, decimals=4)) if rounded else float(value.value)
-        res[ref_key] = 0.0
-        out[name] = res
-    return out
+    finite = lambda v: v[np.isfinite(v)]
+    return {name: js_columns({k: finite(getattr(d, name)) for k, d in desc.items()}, ref_key, n_bins, rounded) for name in quantities}
 
 
 def _per_frame(d: ShapeFrames) -> dict:

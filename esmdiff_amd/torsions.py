@@ -28,9 +28,7 @@ Inputs follow esmdiff_amd/secondary.py: Angstrom, arrays, tensors or a PDB path,
 floats on the host.  There is no CPU fallback."""
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
-from pathlib import Path
 from typing import Optional
 
 import numpy as np
@@ -56,35 +54,16 @@ IDEAL = {"n_ca": 1.458, "ca_c": 1.525, "c_n": 1.329, "n_ca_c": 111.0, "ca_c_n": 
 QUANTITIES = tuple(IDEAL)
 
 
-def _need_device(what: str):
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"esmdiff_amd.torsions.{what} needs an MI355X (gfx950); there is no CPU fallback")
-
-
 def backbone_array(backbone) -> np.ndarray:
     """A PDB path (N / CA / C of every MODEL), an array or a tensor, (L, A, 3) or (n, L, A, 3) with A = 3 or 4 -> float64 (n, L, A, 3)
     on the host, as it is (no O is inferred: none is read)."""
-    if isinstance(backbone, (str, os.PathLike)):
-        from .pdbio import load_coords
-        backbone = load_coords(Path(backbone), max_n_model=None, ca_only=False, verbose=False)
-    x = backbone.detach().cpu().numpy() if torch.is_tensor(backbone) else np.asarray(backbone)
-    x = np.asarray(x, np.float64)
-    if x.ndim == 3:
-        x = x[None]
-    if x.ndim != 4 or x.shape[2] not in (3, 4) or x.shape[3] != 3 or x.shape[1] == 0:
-        raise AssertionError(f"backbones should be (n, L, 3, 3) N / CA / C or (n, L, 4, 3) N / CA / C / O, got {tuple(x.shape)}")
-    return np.ascontiguousarray(x)
+    return pairs.atoms(backbone, (3, 4), what="backbones should be (n, L, 3, 3) N / CA / C or (n, L, 4, 3) N / CA / C / O")
 
 
 def _device_args(backbone, mask):
     """-> X f64 on the device, mask u8 on the device or None, present bool (n, L) on the host."""
     x = backbone_array(backbone)
-    n, L = x.shape[:2]
-    given = np.ones((n, L), bool)
-    if mask is not None:
-        m = (mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)).astype(bool)
-        given = np.broadcast_to(m[None] if m.ndim == 1 else m, (n, L)).copy()
-    mk = None if given.all() else torch.as_tensor(given.astype(np.uint8), device="cuda")
+    given, mk = pairs.given_mask(mask, *x.shape[:2])
     return torch.as_tensor(x, device="cuda"), mk, given & np.isfinite(x[:, :, :3]).all((2, 3))
 
 
@@ -106,7 +85,7 @@ class BackboneTorsions:
 
 def torsions(backbone, mask=None, break_distance: float = BREAK_DISTANCE, geometry: bool = False, degrees: bool = True) -> BackboneTorsions:
     """The torsions of every structure: one esmdiff_backbone_torsions call.  geometry: also the bond lengths and bond angles."""
-    _need_device("torsions")
+    pairs.need_device("esmdiff_amd.torsions.torsions")
     X, mk, present = _device_args(backbone, mask)
     phi, psi, omega, geom = pairs.backbone_torsions(X, mk, break_distance, geometry)
     scale = DEG if degrees else 1.0
@@ -193,7 +172,7 @@ class RamachandranMap:
 
 def ramachandran(samples, bins: int = 36, mask=None, break_distance: float = BREAK_DISTANCE) -> RamachandranMap:
     """The per-residue Ramachandran maps of an ensemble: one esmdiff_ramachandran call."""
-    _need_device("ramachandran")
+    pairs.need_device("esmdiff_amd.torsions.ramachandran")
     X, mk, _ = _device_args(samples, mask)
     hist, counts, sums = pairs.ramachandran(X, mk, break_distance, bins)
     return RamachandranMap(hist.cpu().numpy(), counts.cpu().numpy(), sums.cpu().numpy(), int(bins), int(X.shape[0]))
@@ -343,7 +322,7 @@ def geometry_summary(backbone, ideal=IDEAL, length_tol: float = 0.05, angle_tol:
 def report(samples, targets=(), bins: int = 36, break_distance: float = BREAK_DISTANCE) -> dict:
     """The "torsions" block of analyze_ensemble: samples (n, L, A, 3), targets [(L, A, 3)].  js_ramachandran takes the targets together
     as one ensemble: with few targets that reference map is thin (a handful of cells per residue)."""
-    _need_device("report")
+    pairs.need_device("esmdiff_amd.torsions.report")
     samples = backbone_array(samples)
     m = ramachandran(samples, bins, break_distance=break_distance)
     s = torsions(samples, break_distance=break_distance, geometry=True)
