@@ -18,6 +18,9 @@ EPI_BF16, EPI_RESID_F32, EPI_SWIGLU_BF16, EPI_BIAS_GELU_BF16, EPI_BIAS_F32 = ran
 DT_F32, DT_BF16 = 0, 1
 PRECISION = {"bf16": 0, "f32": 1, "f32_split": 2, "f16": 3}       # esmdiff_precision
 F32EPI_STORE, F32EPI_BIAS_GELU, F32EPI_RESID_DIV = range(3)
+# launcher codes of the split GEMM alone (csrc/gemm256w4_split.hip): 3 is what STORE with a bias runs as (never passed in),
+# 4 the fused SwiGLU writing f32 [M, N / 2] (esmdiff_gemm_split accepts it)
+F32EPI_SPLIT_STORE_BIAS, F32EPI_SPLIT_SWIGLU = 3, 4
 SECTIONS = ["embed", "layernorm", "gemm_qkv", "qk_norm_rope", "attention", "gemm_out", "gemm_ffn_up",
             "gemm_ffn_down", "head", "sampler"]
 

@@ -949,16 +949,18 @@ def split_weight(W: torch.Tensor):
 def gemm_split(a2: torch.Tensor, rs: Optional[torch.Tensor], w2: torch.Tensor, w_inv: float, n_out: int,
                epilogue: int = 0, *, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
                div: float = 1.0) -> torch.Tensor:
-    """out f32 [M, n_out] = epi(A . W^T) from split operands on three f16 MFMA passes (esmdiff_gemm_split)."""
+    """out f32 [M, n_out] = epi(A . W^T) from split operands on three f16 MFMA passes (esmdiff_gemm_split).
+    epilogue N.F32EPI_SPLIT_SWIGLU: w2 rows interleaved gate / up in blocks of 32, out f32 [M, n_pad / 2] = silu(gate) * up."""
     _require_gpu()
     M, K3 = a2.shape
     n_pad = w2.shape[0]
+    width = n_pad // 2 if epilogue == N.F32EPI_SPLIT_SWIGLU else n_pad
     assert a2.dtype == w2.dtype == torch.float16 and w2.shape[1] == K3 and a2.is_contiguous() and w2.is_contiguous()
     if out is None:
         if epilogue == N.F32EPI_RESID_DIV:
             raise ValueError("the residual epilogue updates `out` in place: pass it")
-        out = torch.empty(M, n_pad, dtype=torch.float32, device=a2.device)      # the kernel writes whole padded rows
-    assert out.dtype == torch.float32 and out.stride(1) == 1 and out.stride(0) >= n_pad
+        out = torch.empty(M, width, dtype=torch.float32, device=a2.device)      # the kernel writes whole padded rows
+    assert out.dtype == torch.float32 and out.stride(1) == 1 and out.stride(0) >= width
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() >= n_pad
     N.check(N.lib().esmdiff_gemm_split(_ptr(a2), _ptr(rs), _ptr(w2), float(w_inv), _ptr(out), _ptr(bias), M, n_pad, K3 // 3,
@@ -967,16 +969,20 @@ def gemm_split(a2: torch.Tensor, rs: Optional[torch.Tensor], w2: torch.Tensor, w
 
 
 def gemm_split_k(a2: torch.Tensor, rs: Optional[torch.Tensor], w2: torch.Tensor, w_inv: float, x: torch.Tensor, S: int,
-                 div: float = 1.0) -> torch.Tensor:
+                 div: float = 1.0, *, parts: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The K-sliced split GEMM and its reduce (esmdiff_gemm_split_k): x f32 [M, N] += (sum of the S slice products of
-    a2 [M, 3K] . w2 [N, 3K]^T * w_inv) * rs / div, in place; returns the slice planes f32 [S, M rounded up to 256, N]."""
+    a2 [M, 3K] . w2 [N, 3K]^T * w_inv) * rs / div, in place; returns the slice planes f32 [S, M rounded up to 256, N] (the caller's
+    `parts` when given; rows M .. of each plane are unspecified)."""
     _require_gpu()
     M, K3 = a2.shape
     Nn = w2.shape[0]
     assert a2.dtype == w2.dtype == torch.float16 and w2.shape[1] == K3 and a2.is_contiguous() and w2.is_contiguous()
     assert x.dtype == torch.float32 and x.shape == (M, Nn) and x.is_contiguous()
     assert rs is None or (rs.dtype == torch.float32 and rs.numel() == M)
-    parts = torch.empty(max(int(S), 1), (M + 255) // 256 * 256, Nn, dtype=torch.float32, device=a2.device)
+    shape = (max(int(S), 1), (M + 255) // 256 * 256, Nn)
+    if parts is None:
+        parts = torch.empty(shape, dtype=torch.float32, device=a2.device)
+    assert parts.dtype == torch.float32 and tuple(parts.shape) == shape and parts.is_contiguous() and parts.device == a2.device
     N.check(N.lib().esmdiff_gemm_split_k(_ptr(a2), _ptr(rs), _ptr(w2), float(w_inv), _ptr(parts), _ptr(x), M, Nn, K3 // 3, int(S),
                                          float(div), _stream()))
     return parts

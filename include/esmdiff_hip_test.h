@@ -52,8 +52,16 @@ int esmdiff_gemm_f32(const float* A, int32_t lda, const float* W, float* out, co
  *   esmdiff_split_weight  src f32 [N,K] -> w3 f16 [N_pad,3K] = [lo | hi | hi] of src * 2^k (rows N..N_pad-1 zero-filled,
  *                         N_pad a multiple of 256 >= N), *inv_scale_out [host] = 2^-k; synchronous
  *   esmdiff_gemm_split    out f32 [M,ldc] = epi(rs[m] * w_inv_scale * A . W^T [+ bias[N]]); N (= N_pad) % 256 == 0,
- *                         K % 128 == 0, ldc >= N: whole padded rows are written (the kernel carries no column bound);
- *                         epilogue ESMDIFF_F32EPI_STORE (bias optional) or ESMDIFF_F32EPI_RESID_DIV. */
+ *                         K % 128 == 0, ldc % 4 == 0, ldc >= N: whole padded rows are written (the kernel carries no column
+ *                         bound); rows >= M and columns N .. ldc-1 are never written.  rs NULL: no row scale.  epilogue:
+ *                           ESMDIFF_F32EPI_STORE      out = v; with bias != NULL the bias kernel runs (launcher code 3): v + bias[n]
+ *                           ESMDIFF_F32EPI_RESID_DIV  out = out + v / div, in place (bias ignored)
+ *                           4                         the fused SwiGLU of FFN-up: W rows interleaved gate / up in blocks of 32
+ *                                                     (rows 64t .. 64t+31 gate 32t .., rows 64t+32 .. 64t+63 up 32t ..: what
+ *                                                     esmdiff_interleave_swiglu makes), out f32 [M, N / 2] = silu(g) * u with
+ *                                                     g, u the scaled products, as g * rcp(1 + exp2(-g log2 e)) * u; ldc >= N / 2,
+ *                                                     columns N / 2 .. ldc-1 never written (bias ignored)
+ *                         anything else (3 included) is refused, as is every shape above, before any launch. */
 int esmdiff_split_rows(const float* src, int32_t ld, void* a2, float* rs, int32_t M, int32_t K, void* stream);
 int esmdiff_split_weight(const float* src, void* w2, int32_t N, int32_t N_pad, int32_t K, float* inv_scale_out);
 int esmdiff_gemm_split(const void* a2, const float* rs, const void* w2, float w_inv_scale, float* out, const float* bias,
@@ -193,7 +201,9 @@ int esmdiff_encoder_nearest_code(const float* z, const float* code, const uint8_
  *   esmdiff_gemm_split_k       launch_gemm256w4_splitk + launch_splitk_reduce_resid: parts f32 [S, M rounded up to 256, N]
  *                              (caller-owned) = the S K-slice products of a3 [M, 3K] . w3 [N, 3K]^T * w_inv_scale, then
  *                              x f32 [M, N] = x + ((parts[0] + parts[1]) + ...) * rs[m] / div.  S >= 2, N % 256 == 0, 3K / S a
- *                              multiple of 128 and at least 384
+ *                              multiple of 128 and at least 384.  Rows M .. of each plane are written with unspecified values
+ *                              (products of the last row, which the operand loads clamp to) and never read; nothing outside
+ *                              [S, M rounded up to 256, N] is written
  *   esmdiff_get_attention_scales  the power-of-two operand scales layer `layer` of an F32_SPLIT engine chose at create */
 int esmdiff_layernorm_f32rows(const float* x, const float* w, const float* b, int32_t split, int32_t gelu_in, const void* delta,
                               int32_t delta_dtype, void* a3, float* rs, float* y32, int32_t M, int32_t D, void* stream);
