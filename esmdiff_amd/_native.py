@@ -72,6 +72,7 @@ EXPORTS = [
     "esmdiff_backbone_torsions", "esmdiff_ramachandran",
     "esmdiff_shape_frames", "esmdiff_debye_frames",
     "esmdiff_sasa_frames", "esmdiff_cooccurrence",
+    "esmdiff_lagged_means", "esmdiff_lagged_moments", "esmdiff_lagged_project",
     "esmdiff_describe_gemm_choice", "esmdiff_gemm_workspace_floats",
     "esmdiff_dim6_to_backbone", "esmdiff_plddt_mean", "esmdiff_pair_features", "esmdiff_pae_tm",
     "esmdiff_decoder_set_pair_chunk_bytes",
@@ -93,6 +94,7 @@ SHAPE_MAX_L, SHAPE_MAX_BINS = 4096, 4096     # ESMDIFF_SHAPE_MAX_L, ESMDIFF_SHAP
 DEBYE_MAX_Q, DEBYE_Q_CHUNK = 1024, 8         # ESMDIFF_DEBYE_MAX_Q, ESMDIFF_DEBYE_Q_CHUNK
 SASA_MAX_ATOMS, SASA_MAX_POINTS = 4096, 1024    # ESMDIFF_SASA_MAX_ATOMS, ESMDIFF_SASA_MAX_POINTS
 COOCC_MAX_L = 32768                          # ESMDIFF_COOCC_MAX_L
+LAGGED_MAX_L, LAGGED_MAX_D, LAGGED_MAX_DIM, LAGGED_FRAME_CHUNK = 128, 8192, 16, 2048    # ESMDIFF_LAGGED_MAX_L, _MAX_D, _MAX_DIM, _FRAME_CHUNK
 
 CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
@@ -155,6 +157,16 @@ def shape_waves(L: int) -> int:
 def coocc_scratch_bytes(n: int, L: int) -> int:
     """ESMDIFF_COOCC_SCRATCH_BYTES: the scratch esmdiff_cooccurrence needs: a word per residue and 64 frames, in two planes."""
     return ((n + 63) // 64) * L * 16
+
+
+def lagged_features(L: int, k: int) -> int:
+    """ESMDIFF_LAGGED_FEATURES: the pairs (i, j >= i + k) of L residues."""
+    return (L - k) * (L - k + 1) // 2
+
+
+def lagged_scratch_bytes(D: int, slots: int, moments: bool) -> int:
+    """ESMDIFF_LAGGED_MOMENTS_SCRATCH_BYTES / ESMDIFF_LAGGED_MEANS_SCRATCH_BYTES: the pair table, then `slots` chunk sums."""
+    return D * 8 + slots * ((3 * D * D + 2 * D) if moments else 2 * D) * 8
 
 
 def lib_path() -> Path:
@@ -249,6 +261,9 @@ def lib():
     L.esmdiff_debye_frames.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp]
     L.esmdiff_sasa_frames.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, f64, vp, vp, vp, vp, vp, vp, vp]
     L.esmdiff_cooccurrence.argtypes = [vp, i32, i32, vp, vp, ctypes.c_int64, vp]
+    L.esmdiff_lagged_means.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, ctypes.c_int64, vp]
+    L.esmdiff_lagged_moments.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
+    L.esmdiff_lagged_project.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_encoder_create.argtypes = [i32] * 9 + [ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.esmdiff_encoder_destroy.argtypes = [vp]
     L.esmdiff_encoder_destroy.restype = None

@@ -6,6 +6,7 @@
                                            [--torsions] [--rama_bins 36]
                                            [--shape] [--pr_bins 100] [--saxs] [--saxs_qmax 0.5] [--saxs_points 51] [--saxs_data FILE]
                                            [--sasa] [--sasa_points 96] [--sasa_probe 1.4] [--sasa_threshold 0.2]
+                                           [--tica --trajectory REF] [--lagtime 20] [--tica_dim 2] [--lagtimes 5 10 20 ...]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
@@ -59,7 +60,13 @@ NACCESS / freesasa / mdtraj unpinned): the parameters (--sasa_points, --sasa_pro
 area, the mean relative exposure and the share of samples in which it is exposed, per sample the total area with its summary, per target
 its own per-residue values and exposed_jaccard (the Jaccard index of the residues the target exposes and those the samples expose in
 more than half of their frames) and, with exactly two targets, exposure_switches: the residues exposed in one target only, with the
-samples' frequency of each.  Samples and targets are read again as N / CA / C backbones, on the analysed subset."""
+samples' frequency of each.  Samples and targets are read again as N / CA / C backbones, on the analysed subset.
+--tica --trajectory REF adds a "tica" block (esmdiff_amd/kinetics.py, csrc/lagged.hip; [DEEPTIME-RECALL], parity unpinned): REF is an MD
+trajectory of the same chain, a .npy (n, L, 3) CA array (memory-mapped, uploaded --tica_chunk pairs at a time) or a multi-MODEL PDB.  A
+TICA model of its CA distances is fitted at --lagtime with --tica_dim components; the block holds the parameters, the eigenvalues,
+timescales and n_kept, the VAMP-2 score, per TIC the Jensen-Shannon distance of the samples against the trajectory (js_tic) and their
+mean (js_tica), the projections of the samples and of every target, with --lagtimes the implied-timescale table, and the trajectory's
+free-energy grid over TIC 1 x TIC 2 (-ln p, null in an empty cell)."""
 from __future__ import annotations
 
 import argparse
@@ -68,7 +75,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import accessibility, contacts, ensemble, flexibility, secondary, shape, torsions
+from . import accessibility, contacts, ensemble, flexibility, kinetics, secondary, shape, torsions
 from .pdbio import load_coords, read_pdb_backbone, read_pdb_bfactors
 
 
@@ -176,6 +183,20 @@ def sasa_report(samples_path, target_paths, keep=None, points: int = 96, probe: 
     return accessibility.report(backbones, targets, points, probe, threshold)
 
 
+def tica_report(samples_path, target_paths, trajectory_path, max_models: int = 100, seed: int = 0, lagtime: int = 20, dim: int = 2,
+                lagtimes=None, chunk: int = 65536) -> dict:
+    """The --tica block, on the samples analyze() takes for the same max_models and seed; the trajectory: a .npy (n, L, 3) array, opened
+    memory-mapped and uploaded `chunk` pairs at a time, or a multi-MODEL PDB."""
+    samples, targets, _, _ = load_ca(samples_path, target_paths, max_models, seed)
+    if str(trajectory_path).endswith(".npy"):
+        trajectory, chunk_frames = np.load(trajectory_path, mmap_mode="r"), int(chunk)
+    else:
+        trajectory, chunk_frames = load_coords(Path(trajectory_path), max_n_model=None, verbose=False), None
+    if trajectory.ndim != 3 or trajectory.shape[1:] != samples.shape[1:]:
+        raise ValueError(f"{trajectory_path} holds {trajectory.shape}, the samples {samples.shape[1:]} per frame: the correspondence is residue to residue")
+    return kinetics.report(trajectory, samples, np.stack(targets), lagtime, dim, lagtimes, chunk_frames=chunk_frames)
+
+
 def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0,
             flex: bool = False, pca_components: int = 3, dssp: bool = False) -> dict:
     samples, targets, n_all, keep = load_ca(samples_path, target_paths, max_models, seed)
@@ -228,6 +249,12 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--sasa_points", type=int, default=96, help="points on every atom's sphere of the --sasa point test (1 to 1024)")
     ap.add_argument("--sasa_probe", type=float, default=1.4, help="probe radius of --sasa (Angstrom)")
     ap.add_argument("--sasa_threshold", type=float, default=0.2, help="relative exposure above which --sasa calls a residue exposed")
+    ap.add_argument("--tica", action="store_true", help="add the slow coordinates of --trajectory: TICA eigenvalues, timescales, projections, JS")
+    ap.add_argument("--trajectory", default=None, help="the MD trajectory --tica is fitted on: a .npy (n, L, 3) CA array or a multi-MODEL PDB")
+    ap.add_argument("--lagtime", type=int, default=20, help="lag time of --tica, in frames of the trajectory")
+    ap.add_argument("--tica_dim", type=int, default=2, help="components of the --tica model (1 to 16)")
+    ap.add_argument("--lagtimes", type=int, nargs="+", default=None, help="lag times of the --tica implied-timescale table")
+    ap.add_argument("--tica_chunk", type=int, default=65536, help="frame pairs of a .npy --trajectory uploaded at a time")
     return ap
 
 
@@ -247,6 +274,11 @@ def main(argv=None) -> Path:
     if args.sasa:
         keep = load_ca(args.samples, args.targets, args.max_models, args.seed)[3]
         report["sasa"] = sasa_report(args.samples, args.targets, keep, args.sasa_points, args.sasa_probe, args.sasa_threshold)
+    if args.tica:
+        if not args.trajectory:
+            raise SystemExit("--tica needs --trajectory REF")
+        report["tica"] = tica_report(args.samples, args.targets, args.trajectory, args.max_models, args.seed, args.lagtime, args.tica_dim,
+                                     args.lagtimes, args.tica_chunk)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

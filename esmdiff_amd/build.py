@@ -57,6 +57,9 @@ UNITS = {
     "torsions": ["-ffp-contract=off"],   # float64 cross and dot products written out term by term, numpy's bits (tests/torsions_ref.py)
     "shape": ["-ffp-contract=off"],      # float64 distances, 1 / d, d / width and q d with numpy's bits, sums in a fixed order (tests/shape_ref.py)
     "sasa": ["-ffp-contract=off"],       # float64 point tests with numpy's bits (p = c + R u: a product and an add), integer counts (tests/sasa_ref.py)
+    # float64 distances with esmdiff_metrics_pwd's bits and sums in a published order (tests/kinetics_ref.py); the f64 MFMA is a builtin,
+    # untouched by the flag.  No SLP: the shipped code objects are scanned for packed float forms (tests/test_host_cpu.py)
+    "lagged": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 # The MFMA kernels, the row kernels that feed them and the weight conversion are compiled a SECOND time with f16 operands
 # (csrc/ed_half.h): -DED_F16 switches the conversion / MFMA primitives, -Ded=ed16 puts that build into namespace ed16

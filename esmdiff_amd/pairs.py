@@ -1,5 +1,5 @@
 """The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
-csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip, csrc/shape.hip and csrc/sasa.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip, csrc/shape.hip, csrc/sasa.hip and csrc/lagged.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
 on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
 host-facing layers above it.  The frame-wise layers (secondary, torsions, accessibility) share one input stage here: need_device,
 atoms and given_mask; every frame-wise entry below asserts its input through _frames.
@@ -332,6 +332,85 @@ def cooccurrence(flags):
            capacity=lambda: f"esmdiff_cooccurrence: L = {L} is beyond the entry's limit ({N.COOCC_MAX_L} residues)",
            invalid=lambda: f"esmdiff_cooccurrence: invalid argument: L = {L} (at least 1)")
     return out
+
+
+LAGGED_WORKGROUPS = 512       # the chunks one round of esmdiff_lagged_moments runs at once are chosen to give about this many workgroups (two a CU)
+LAGGED_SCRATCH_CAP = 1 << 28  # ... within this many bytes of scratch, or one slot where one slot is larger
+
+
+def _lagged_input(X, pwd_offset: int):
+    """X f64 (n, D) with pwd_offset 0 or f64 (n, L, 3) with pwd_offset >= 1, on the device -> n, L_or_D, D."""
+    assert X.dtype == torch.float64 and X.is_cuda, f"f64 frames on the device, got {X.dtype}"
+    if pwd_offset == 0:
+        assert X.dim() == 2, f"the feature form takes f64 (n, D), got {tuple(X.shape)}"
+        return X.shape[0], X.shape[1], X.shape[1]
+    assert X.dim() == 3 and X.shape[2] == 3, f"the coordinate form takes f64 (n, L, 3), got {tuple(X.shape)}"
+    return X.shape[0], X.shape[1], max(N.lagged_features(X.shape[1], pwd_offset), 0) if pwd_offset < X.shape[1] else 0
+
+
+def lagged_slots(D: int, chunks: int, moments: bool) -> int:
+    """The slots of scratch a call gets: enough chunks at once to fill the device, within LAGGED_SCRATCH_CAP bytes, at least one.  The
+    number changes no bit of the result (include/esmdiff_hip.h)."""
+    tiles = (D + 63) // 64
+    want = -(-LAGGED_WORKGROUPS // (tiles * (tiles + 1) // 2)) if moments else chunks
+    fit = LAGGED_SCRATCH_CAP // max(N.lagged_scratch_bytes(D, 1, moments) - D * 8, 1)
+    return max(1, min(chunks, want, fit))
+
+
+def _lagged_invalid(entry, n, L_or_D, pwd_offset, lag=None, dim=None):
+    lag_text = "" if lag is None else f", lag = {lag} (at least 1, below n)"
+    dim_text = "" if dim is None else f", dim = {dim} (1 to {N.LAGGED_MAX_DIM})"
+    return lambda: (f"{entry}: invalid argument: n = {n}{lag_text}{dim_text}, pwd_offset = {pwd_offset} (0: features, up to "
+                    f"{N.LAGGED_MAX_D} of them; k >= 1: CA coordinates of k < L <= {N.LAGGED_MAX_L} residues), L or D = {L_or_D}; there is no slow path")
+
+
+def _lagged_scratch(D: int, n: int, lag: int, moments: bool, slots):
+    chunks = max(-(-(n - lag) // N.LAGGED_FRAME_CHUNK), 1)
+    size = N.lagged_scratch_bytes(max(D, 1), lagged_slots(max(D, 1), chunks, moments) if slots is None else slots, moments)
+    return _new((size // 8,), torch.int64), size
+
+
+def lagged_means(X, lag: int, pwd_offset: int = 1, slots=None):
+    """One esmdiff_lagged_means call: X f64 (n, L, 3) (pwd_offset >= 1) or (n, D) (pwd_offset = 0) on the device -> mean0 (D,),
+    meant (D,): the means of the features over the frames t < n - lag and over t + lag.  slots: the chunk sums the scratch holds
+    (default: lagged_slots); no bit depends on it."""
+    n, L_or_D, D = _lagged_input(X, pwd_offset)
+    mean0, meant = _new((D,)), _new((D,))
+    scratch, size = _lagged_scratch(D, n, lag, False, slots)
+    code = N.lib().esmdiff_lagged_means(_p(X), n, L_or_D, int(pwd_offset), int(lag), _p(mean0), _p(meant), _p(scratch), size, _stream())
+    _check("esmdiff_lagged_means", code, invalid=_lagged_invalid("esmdiff_lagged_means", n, L_or_D, pwd_offset, lag))
+    return mean0, meant
+
+
+def lagged_moments(X, lag: int, center, pwd_offset: int = 1, slots=None, out=None) -> dict:
+    """One esmdiff_lagged_moments call: X as lagged_means takes it, center f64 (D,) on the device -> {S00, S0t, Stt: (D, D), r0, rt:
+    (D,)}, the raw sums of a a^T, a b^T, b b^T, a and b with a = f(x_t) - center, b = f(x_{t + lag}) - center over t < n - lag.
+    out: {name: tensor} to write into instead of allocating."""
+    n, L_or_D, D = _lagged_input(X, pwd_offset)
+    assert center is not None and center.dtype == torch.float64 and center.is_cuda and tuple(center.shape) == (D,), f"the centre is f64 ({D},) on the device"
+    shapes = {"S00": (D, D), "S0t": (D, D), "Stt": (D, D), "r0": (D,), "rt": (D,)}
+    res = {k: out[k] if out and k in out else _new(s) for k, s in shapes.items()}
+    assert all(tuple(v.shape) == shapes[k] and v.dtype == torch.float64 for k, v in res.items()), f"the call writes f64 {shapes}"
+    scratch, size = _lagged_scratch(D, n, lag, True, slots)
+    code = N.lib().esmdiff_lagged_moments(_p(X), n, L_or_D, int(pwd_offset), int(lag), _p(center), *[_p(res[k]) for k in shapes],
+                                          _p(scratch), size, _stream())
+    _check("esmdiff_lagged_moments", code, invalid=_lagged_invalid("esmdiff_lagged_moments", n, L_or_D, pwd_offset, lag))
+    return res
+
+
+def lagged_project(X, mean, W, pwd_offset: int = 1):
+    """One esmdiff_lagged_project call: X as lagged_means takes it, mean f64 (D,), W f64 (D, dim) on the device -> Y (n, dim) =
+    (f(x_t) - mean) W, every frame's row in the same fixed tree."""
+    n, L_or_D, D = _lagged_input(X, pwd_offset)
+    assert mean.dtype == torch.float64 and mean.is_cuda and tuple(mean.shape) == (D,), f"the mean is f64 ({D},) on the device"
+    assert W.dim() == 2 and W.dtype == torch.float64 and W.is_cuda and W.shape[0] == D, f"the directions are f64 ({D}, dim) on the device"
+    dim = W.shape[1]
+    Y = _new((n, dim))
+    size = max(D, 1) * 8
+    scratch = _new((size // 8,), torch.int64)
+    code = N.lib().esmdiff_lagged_project(_p(X), n, L_or_D, int(pwd_offset), _p(mean), _p(W), dim, _p(Y), _p(scratch), size, _stream())
+    _check("esmdiff_lagged_project", code, invalid=_lagged_invalid("esmdiff_lagged_project", n, L_or_D, pwd_offset, dim=dim))
+    return Y
 
 
 def adjacency(n: int) -> torch.Tensor:

@@ -855,6 +855,53 @@ int esmdiff_sasa_frames(const double* X, int32_t n, int32_t L, int32_t A, const 
                         int32_t* exposed_count, int32_t* present_count, void* stream);
 int esmdiff_cooccurrence(const uint8_t* flags, int32_t n, int32_t L, int32_t* out, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* The time-lagged moments of a trajectory's features, fused from the coordinates: what a TICA / VAMP fit needs of n frames in
+ * O(D^2) memory (float64, device pointers in and out; each call synchronises `stream`): DESIGN.md §3.27, restated in numpy by
+ * tests/kinetics_ref.py.  (An addition; the ABI number stays.)  csrc/lagged.hip; the layer above is esmdiff_amd/kinetics.py.
+ *
+ * INPUT, the same in the three entries: pwd_offset = 0: X is a feature matrix f64 [n, D] and L_or_D is D (up to
+ * ESMDIFF_LAGGED_MAX_D).  pwd_offset = k >= 1: X is CA coordinates f64 [n, L, 3], L_or_D is L (k < L <= ESMDIFF_LAGGED_MAX_L), and
+ * the D = ESMDIFF_LAGGED_FEATURES(L, k) features are the distances of the pairs (i, j >= i + k) in numpy.triu_indices order, each
+ * sqrt((dx dx + dy dy) + dz dz) with no FMA: the bits of esmdiff_metrics_pwd.  The distances are recomputed inside the kernels; no
+ * [n, D] array exists.  Non-finite input is not looked for (esmdiff_amd/kinetics.py refuses it).
+ *
+ * With m = n - lag, a_t = f(x_t) - c and b_t = f(x_{t + lag}) - c for t < m.  The t are cut into chunks of
+ * ESMDIFF_LAGGED_FRAME_CHUNK; a chunk's sums go to a slot of `scratch` and the slots are added to the outputs in increasing chunk
+ * index, starting from chunk 0's own sums.  scratch (device, 8-byte aligned, need not be zeroed) holds the pair table
+ * (ESMDIFF_LAGGED_TABLE_BYTES(D)) and then as many slots as fit, at least one: ESMDIFF_LAGGED_MEANS_SCRATCH_BYTES(D, slots) /
+ * ESMDIFF_LAGGED_MOMENTS_SCRATCH_BYTES(D, slots).  More slots let more chunks run at once and change no bit: every output is a
+ * function of (X, c, n, lag) alone, the same on every run and every device.
+ *
+ * esmdiff_lagged_means: mean0[D], meant[D] = the means of f over t < m and over t + lag.  A chunk's sum is s = 0, s = s + f(x_t)
+ * in increasing t; the total of the chunks (in order) is divided by m once.
+ * esmdiff_lagged_moments: center c[D] (required) -> S00 = sum a a^T, S0t = sum a b^T, Stt = sum b b^T (f64 [D, D] each, raw sums,
+ * undivided) and r0 = sum a, rt = sum b ([D], summed as the means are, a_t = f(x_t) - c the summand).  A chunk's matrix sums are
+ * accumulated by v_mfma_f64_16x16x4_f64 over its t in increasing order, four t to an instruction.  S00 and Stt are computed for
+ * column tile >= row tile only and mirrored: they are exactly symmetric.
+ * esmdiff_lagged_project: Y[n, dim] = (f(x_t) - mean) W with W f64 [D, dim], 1 <= dim <= ESMDIFF_LAGGED_MAX_DIM.  Per frame and
+ * column, p_l = 0 then p_l = p_l + (f_d - mean_d) * W[d][k] for d = l, l + 64, ... (l = 0 .. 63), then p_l = p_l + p_{l ^ s} for
+ * s = 32, 16, 8, 4, 2, 1: a tree that depends on D alone, so a frame's row does not depend on the batch.  scratch: the pair table
+ * only (may be NULL when pwd_offset = 0); n = 0 is allowed and writes nothing.
+ *
+ * ESMDIFF_E_INVALID, before anything is launched or written: a NULL pointer (center included), lag < 1, n <= lag, pwd_offset < 0 or
+ * >= L, L > ESMDIFF_LAGGED_MAX_L, D > ESMDIFF_LAGGED_MAX_D in the feature form, dim outside 1 .. ESMDIFF_LAGGED_MAX_DIM, a scratch
+ * smaller than one slot's. */
+#define ESMDIFF_LAGGED_MAX_L 128
+#define ESMDIFF_LAGGED_MAX_D 8192
+#define ESMDIFF_LAGGED_MAX_DIM 16
+#define ESMDIFF_LAGGED_FRAME_CHUNK 2048
+#define ESMDIFF_LAGGED_FEATURES(L, k) ((((int64_t)(L) - (k)) * ((int64_t)(L) - (k) + 1)) / 2)
+#define ESMDIFF_LAGGED_TABLE_BYTES(D) ((int64_t)(D) * 8)
+#define ESMDIFF_LAGGED_MEANS_SCRATCH_BYTES(D, slots) (ESMDIFF_LAGGED_TABLE_BYTES(D) + (int64_t)(slots) * 2 * (int64_t)(D) * 8)
+#define ESMDIFF_LAGGED_MOMENTS_SCRATCH_BYTES(D, slots) \
+  (ESMDIFF_LAGGED_TABLE_BYTES(D) + (int64_t)(slots) * (3 * (int64_t)(D) * (int64_t)(D) + 2 * (int64_t)(D)) * 8)
+int esmdiff_lagged_means(const double* X, int32_t n, int32_t L_or_D, int32_t pwd_offset, int32_t lag, double* mean0, double* meant,
+                         void* scratch, int64_t scratch_bytes, void* stream);
+int esmdiff_lagged_moments(const double* X, int32_t n, int32_t L_or_D, int32_t pwd_offset, int32_t lag, const double* center, double* S00,
+                           double* S0t, double* Stt, double* r0, double* rt, void* scratch, int64_t scratch_bytes, void* stream);
+int esmdiff_lagged_project(const double* X, int32_t n, int32_t L_or_D, int32_t pwd_offset, const double* mean, const double* W, int32_t dim,
+                           double* Y, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
