@@ -73,6 +73,7 @@ EXPORTS = [
     "esmdiff_shape_frames", "esmdiff_debye_frames",
     "esmdiff_sasa_frames", "esmdiff_cooccurrence",
     "esmdiff_lagged_means", "esmdiff_lagged_moments", "esmdiff_lagged_project",
+    "esmdiff_kmeans_assign", "esmdiff_kmeans_step", "esmdiff_transition_counts",
     "esmdiff_describe_gemm_choice", "esmdiff_gemm_workspace_floats",
     "esmdiff_dim6_to_backbone", "esmdiff_plddt_mean", "esmdiff_pair_features", "esmdiff_pae_tm",
     "esmdiff_decoder_set_pair_chunk_bytes",
@@ -95,8 +96,10 @@ DEBYE_MAX_Q, DEBYE_Q_CHUNK = 1024, 8         # ESMDIFF_DEBYE_MAX_Q, ESMDIFF_DEBY
 SASA_MAX_ATOMS, SASA_MAX_POINTS = 4096, 1024    # ESMDIFF_SASA_MAX_ATOMS, ESMDIFF_SASA_MAX_POINTS
 COOCC_MAX_L = 32768                          # ESMDIFF_COOCC_MAX_L
 LAGGED_MAX_L, LAGGED_MAX_D, LAGGED_MAX_DIM, LAGGED_FRAME_CHUNK = 128, 8192, 16, 2048    # ESMDIFF_LAGGED_MAX_L, _MAX_D, _MAX_DIM, _FRAME_CHUNK
+KMEANS_MAX_K, KMEANS_CENTRE_TILE, KMEANS_FRAME_CHUNK = 4096, 128, 1024    # ESMDIFF_KMEANS_MAX_K, _CENTRE_TILE, _FRAME_CHUNK
+TRANSITION_FRAME_CHUNK, TRANSITION_LDS_MAX_K, TRANSITION_SCRATCH_BYTES = 4096, 128, 8    # ESMDIFF_TRANSITION_FRAME_CHUNK, _LDS_MAX_K, _SCRATCH_BYTES
 
-CLUSTER_MAX_N = 16384                        # ESMDIFF_CLUSTER_MAX_N
+CLUSTER_MAX_N = 16384                       # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
 OPT_STREAMS, OPT_DUAL_MIN_TOKENS, OPT_NEEDED_ROWS = 1, 2, 3      # esmdiff_option
 
@@ -167,6 +170,21 @@ def lagged_features(L: int, k: int) -> int:
 def lagged_scratch_bytes(D: int, slots: int, moments: bool) -> int:
     """ESMDIFF_LAGGED_MOMENTS_SCRATCH_BYTES / ESMDIFF_LAGGED_MEANS_SCRATCH_BYTES: the pair table, then `slots` chunk sums."""
     return D * 8 + slots * ((3 * D * D + 2 * D) if moments else 2 * D) * 8
+
+
+def kmeans_chunks(n: int) -> int:
+    """ESMDIFF_KMEANS_CHUNKS: the chunks esmdiff_kmeans_step cuts n frames into; its sums add them in increasing index."""
+    return (n + KMEANS_FRAME_CHUNK - 1) // KMEANS_FRAME_CHUNK
+
+
+def kmeans_slot_bytes(k: int, d: int) -> int:
+    """ESMDIFF_KMEANS_SLOT_BYTES: one chunk's sums (k, d), counts (k,) and inertia."""
+    return (k * d + k + 1) * 8
+
+
+def kmeans_step_scratch_bytes(k: int, d: int, slots: int) -> int:
+    """ESMDIFF_KMEANS_STEP_SCRATCH_BYTES: `slots` chunk sums."""
+    return slots * kmeans_slot_bytes(k, d)
 
 
 def lib_path() -> Path:
@@ -264,6 +282,9 @@ def lib():
     L.esmdiff_lagged_means.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_lagged_moments.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_lagged_project.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, ctypes.c_int64, vp]
+    L.esmdiff_kmeans_assign.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp]
+    L.esmdiff_kmeans_step.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
+    L.esmdiff_transition_counts.argtypes = [vp, i32, i32, i32, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_encoder_create.argtypes = [i32] * 9 + [ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.esmdiff_encoder_destroy.argtypes = [vp]
     L.esmdiff_encoder_destroy.restype = None

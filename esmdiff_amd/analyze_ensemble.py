@@ -7,6 +7,7 @@
                                            [--shape] [--pr_bins 100] [--saxs] [--saxs_qmax 0.5] [--saxs_points 51] [--saxs_data FILE]
                                            [--sasa] [--sasa_points 96] [--sasa_probe 1.4] [--sasa_threshold 0.2]
                                            [--tica --trajectory REF] [--lagtime 20] [--tica_dim 2] [--lagtimes 5 10 20 ...]
+                                           [--msm] [--msm_states 100] [--msm_lagtime LAG] [--msm_metastable 2] [--msm_seed 0]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
@@ -66,7 +67,15 @@ trajectory of the same chain, a .npy (n, L, 3) CA array (memory-mapped, uploaded
 TICA model of its CA distances is fitted at --lagtime with --tica_dim components; the block holds the parameters, the eigenvalues,
 timescales and n_kept, the VAMP-2 score, per TIC the Jensen-Shannon distance of the samples against the trajectory (js_tic) and their
 mean (js_tica), the projections of the samples and of every target, with --lagtimes the implied-timescale table, and the trajectory's
-free-energy grid over TIC 1 x TIC 2 (-ln p, null in an empty cell)."""
+free-energy grid over TIC 1 x TIC 2 (-ln p, null in an empty cell).
+--msm (with --tica --trajectory REF) adds an "msm" block (esmdiff_amd/states.py, csrc/msm.hip; [DEEPTIME-RECALL], parity unpinned): the
+trajectory's TICA coordinates are clustered into --msm_states microstates by k-means (kmeans++ from --msm_seed), the transitions are
+counted at --msm_lagtime frames (default: --lagtime) and a reversible Markov state model is estimated on the largest connected set.  The
+block holds the parameters, the inertia and the iterations, the size of the active set and the total of the count matrix, the leading
+eigenvalues and timescales, the stationary distribution over the microstates, --msm_metastable metastable sets (the inner-simplex step
+of PCCA+) with their weights and mean TIC position, the microstate of every sample and of every target, and compare_populations: the
+Jensen-Shannon distance of the samples' microstate histogram against the stationary distribution, the populations per metastable set
+beside the model's and the share of the samples outside the active set."""
 from __future__ import annotations
 
 import argparse
@@ -75,7 +84,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import accessibility, contacts, ensemble, flexibility, kinetics, secondary, shape, torsions
+from . import accessibility, contacts, ensemble, flexibility, kinetics, secondary, shape, states, torsions
 from .pdbio import load_coords, read_pdb_backbone, read_pdb_bfactors
 
 
@@ -183,18 +192,33 @@ def sasa_report(samples_path, target_paths, keep=None, points: int = 96, probe: 
     return accessibility.report(backbones, targets, points, probe, threshold)
 
 
-def tica_report(samples_path, target_paths, trajectory_path, max_models: int = 100, seed: int = 0, lagtime: int = 20, dim: int = 2,
-                lagtimes=None, chunk: int = 65536) -> dict:
-    """The --tica block, on the samples analyze() takes for the same max_models and seed; the trajectory: a .npy (n, L, 3) array, opened
-    memory-mapped and uploaded `chunk` pairs at a time, or a multi-MODEL PDB."""
-    samples, targets, _, _ = load_ca(samples_path, target_paths, max_models, seed)
+def _trajectory(trajectory_path, samples, chunk: int):
+    """-> the trajectory and the frame pairs it is uploaded in at a time: a .npy (n, L, 3) array, opened memory-mapped, or a multi-MODEL
+    PDB (whole)."""
     if str(trajectory_path).endswith(".npy"):
         trajectory, chunk_frames = np.load(trajectory_path, mmap_mode="r"), int(chunk)
     else:
         trajectory, chunk_frames = load_coords(Path(trajectory_path), max_n_model=None, verbose=False), None
     if trajectory.ndim != 3 or trajectory.shape[1:] != samples.shape[1:]:
         raise ValueError(f"{trajectory_path} holds {trajectory.shape}, the samples {samples.shape[1:]} per frame: the correspondence is residue to residue")
+    return trajectory, chunk_frames
+
+
+def tica_report(samples_path, target_paths, trajectory_path, max_models: int = 100, seed: int = 0, lagtime: int = 20, dim: int = 2,
+                lagtimes=None, chunk: int = 65536) -> dict:
+    """The --tica block, on the samples analyze() takes for the same max_models and seed; the trajectory: a .npy (n, L, 3) array, opened
+    memory-mapped and uploaded `chunk` pairs at a time, or a multi-MODEL PDB."""
+    samples, targets, _, _ = load_ca(samples_path, target_paths, max_models, seed)
+    trajectory, chunk_frames = _trajectory(trajectory_path, samples, chunk)
     return kinetics.report(trajectory, samples, np.stack(targets), lagtime, dim, lagtimes, chunk_frames=chunk_frames)
+
+
+def msm_report(samples_path, target_paths, trajectory_path, max_models: int = 100, seed: int = 0, lagtime: int = 20, dim: int = 2,
+               n_states: int = 100, msm_lagtime=None, metastable: int = 2, msm_seed: int = 0, chunk: int = 65536) -> dict:
+    """The --msm block, on the same samples and the same trajectory as the --tica block."""
+    samples, targets, _, _ = load_ca(samples_path, target_paths, max_models, seed)
+    trajectory, chunk_frames = _trajectory(trajectory_path, samples, chunk)
+    return states.report(trajectory, samples, np.stack(targets), lagtime, dim, n_states, msm_lagtime, metastable, msm_seed, chunk_frames=chunk_frames)
 
 
 def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0,
@@ -255,11 +279,19 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--tica_dim", type=int, default=2, help="components of the --tica model (1 to 16)")
     ap.add_argument("--lagtimes", type=int, nargs="+", default=None, help="lag times of the --tica implied-timescale table")
     ap.add_argument("--tica_chunk", type=int, default=65536, help="frame pairs of a .npy --trajectory uploaded at a time")
+    ap.add_argument("--msm", action="store_true", help="add the metastable states of --trajectory: k-means on the TICA coordinates, a Markov state model, populations")
+    ap.add_argument("--msm_states", type=int, default=100, help="microstates (k-means centres) of --msm (1 to 4096)")
+    ap.add_argument("--msm_lagtime", type=int, default=None, help="lag time of the --msm transition counts, in frames (default: --lagtime)")
+    ap.add_argument("--msm_metastable", type=int, default=2, help="metastable sets of --msm (below 2: none)")
+    ap.add_argument("--msm_seed", type=int, default=0, help="seed of the kmeans++ initialisation of --msm")
     return ap
 
 
 def main(argv=None) -> Path:
-    args = parser().parse_args(argv)
+    ap = parser()
+    args = ap.parse_args(argv)
+    if args.msm and not (args.tica and args.trajectory):
+        ap.error("--msm needs --tica --trajectory REF")
     report = analyze(args.samples, args.targets, args.max_models, args.seed, args.lddt, args.plddt_scale, args.flex, args.pca_components,
                      args.dssp)
     if args.contacts:
@@ -279,6 +311,9 @@ def main(argv=None) -> Path:
             raise SystemExit("--tica needs --trajectory REF")
         report["tica"] = tica_report(args.samples, args.targets, args.trajectory, args.max_models, args.seed, args.lagtime, args.tica_dim,
                                      args.lagtimes, args.tica_chunk)
+    if args.msm:
+        report["msm"] = msm_report(args.samples, args.targets, args.trajectory, args.max_models, args.seed, args.lagtime, args.tica_dim,
+                                   args.msm_states, args.msm_lagtime, args.msm_metastable, args.msm_seed, args.tica_chunk)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

@@ -1,5 +1,5 @@
 """The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
-csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip, csrc/shape.hip, csrc/sasa.hip and csrc/lagged.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip, csrc/shape.hip, csrc/sasa.hip, csrc/lagged.hip and csrc/msm.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
 on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
 host-facing layers above it.  The frame-wise layers (secondary, torsions, accessibility) share one input stage here: need_device,
 atoms and given_mask; every frame-wise entry below asserts its input through _frames.
@@ -411,6 +411,69 @@ def lagged_project(X, mean, W, pwd_offset: int = 1):
     code = N.lib().esmdiff_lagged_project(_p(X), n, L_or_D, int(pwd_offset), _p(mean), _p(W), dim, _p(Y), _p(scratch), size, _stream())
     _check("esmdiff_lagged_project", code, invalid=_lagged_invalid("esmdiff_lagged_project", n, L_or_D, pwd_offset, dim=dim))
     return Y
+
+
+KMEANS_SCRATCH_CAP = 1 << 28  # the chunk sums one round of esmdiff_kmeans_step keeps, in bytes, or one slot where one slot is larger
+
+
+def _kmeans_input(Y, centres):
+    """Y f64 (n, d) and centres f64 (k, d) on the device -> n, d, k."""
+    assert Y.dim() == 2 and Y.dtype == torch.float64 and Y.is_cuda, f"f64 (n, d) frames on the device, got {Y.dtype} {tuple(Y.shape)}"
+    assert centres.dim() == 2 and centres.dtype == torch.float64 and centres.is_cuda and centres.shape[1] == Y.shape[1], \
+        f"f64 (k, {Y.shape[1]}) centres on the device, got {centres.dtype} {tuple(centres.shape)}"
+    return Y.shape[0], Y.shape[1], centres.shape[0]
+
+
+def _kmeans_text(entry, n, d, k):
+    invalid = lambda: f"{entry}: invalid argument: n = {n}, d = {d}, k = {k} (at least one component and one centre)"
+    capacity = lambda: (f"{entry}: d = {d} components (up to {N.LAGGED_MAX_DIM}) or k = {k} centres (up to {N.KMEANS_MAX_K}) are beyond the "
+                        f"entry's limits, or the scratch is smaller than one chunk's sums; there is no slow path")
+    return {"invalid": invalid, "capacity": capacity}
+
+
+def kmeans_slots(k: int, d: int, chunks: int) -> int:
+    """The slots of scratch a step gets: every chunk at once within KMEANS_SCRATCH_CAP bytes, at least one.  The number changes no bit of
+    the result (include/esmdiff_hip.h)."""
+    return max(1, min(chunks, KMEANS_SCRATCH_CAP // N.kmeans_slot_bytes(k, d)))
+
+
+def kmeans_assign(Y, centres, dist2: bool = True):
+    """One esmdiff_kmeans_assign call: Y f64 (n, d), centres f64 (k, d) on the device -> labels i32 (n,) (the smallest index of a nearest
+    centre, -1 for a frame with a non-finite component or when no centre is finite) and dist2 f64 (n,) (None with dist2=False)."""
+    n, d, k = _kmeans_input(Y, centres)
+    labels, d2 = _new((n,), torch.int32), _new((n,)) if dist2 else None
+    code = N.lib().esmdiff_kmeans_assign(_p(Y), n, d, _p(centres), k, _p(labels), _p(d2), _stream())
+    _check("esmdiff_kmeans_assign", code, **_kmeans_text("esmdiff_kmeans_assign", n, d, k))
+    return labels, d2
+
+
+def kmeans_step(Y, centres, labels: bool = True, slots=None) -> dict:
+    """One esmdiff_kmeans_step call: Y f64 (n, d), centres f64 (k, d) on the device -> {labels: i32 (n,) (absent with labels=False),
+    counts: i64 (k,), sums: f64 (k, d), inertia: f64 (1,)}.  slots: the chunk sums the scratch holds (default: kmeans_slots); no bit
+    depends on it."""
+    n, d, k = _kmeans_input(Y, centres)
+    res = {"labels": _new((n,), torch.int32)} if labels else {}
+    res.update(counts=_new((k,), torch.int64), sums=_new((k, d)), inertia=_new((1,)))
+    size = N.kmeans_step_scratch_bytes(max(k, 1), max(d, 1), kmeans_slots(max(k, 1), max(d, 1), N.kmeans_chunks(n)) if slots is None else slots)
+    scratch = _new((size // 8,), torch.int64)
+    code = N.lib().esmdiff_kmeans_step(_p(Y), n, d, _p(centres), k, _p(res.get("labels")), _p(res["counts"]), _p(res["sums"]), _p(res["inertia"]),
+                                       _p(scratch), size, _stream())
+    _check("esmdiff_kmeans_step", code, **_kmeans_text("esmdiff_kmeans_step", n, d, k))
+    return res
+
+
+def transition_counts(labels, k: int, lag: int):
+    """One esmdiff_transition_counts call: labels i32 (n,) on the device -> counts i64 (k, k): the pairs (labels[t], labels[t + lag]),
+    t < n - lag, both >= 0.  A label >= k is refused."""
+    assert labels.dim() == 1 and labels.dtype == torch.int32 and labels.is_cuda, f"i32 (n,) labels on the device, got {labels.dtype} {tuple(labels.shape)}"
+    n = labels.shape[0]
+    counts = _new((max(int(k), 0), max(int(k), 0)), torch.int64)
+    scratch = _new((N.TRANSITION_SCRATCH_BYTES // 8,), torch.int64)
+    code = N.lib().esmdiff_transition_counts(_p(labels), n, int(k), int(lag), _p(counts), _p(scratch), N.TRANSITION_SCRATCH_BYTES, _stream())
+    _check("esmdiff_transition_counts", code,
+           capacity=lambda: f"esmdiff_transition_counts: k = {k} states are beyond the entry's limit ({N.KMEANS_MAX_K})",
+           invalid=lambda: f"esmdiff_transition_counts: invalid argument: k = {k} (at least 1), lag = {lag} (at least 1), or a label >= k")
+    return counts
 
 
 def adjacency(n: int) -> torch.Tensor:

@@ -902,6 +902,54 @@ int esmdiff_lagged_moments(const double* X, int32_t n, int32_t L_or_D, int32_t p
 int esmdiff_lagged_project(const double* X, int32_t n, int32_t L_or_D, int32_t pwd_offset, const double* mean, const double* W, int32_t dim,
                            double* Y, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* The discrete side of the kinetics pipeline: k-means on the slow coordinates and the lagged transition counts of the labels, what a
+ * Markov state model needs of n frames in O(k d + k^2) memory (float64 and integers, device pointers in and out; each call
+ * synchronises `stream`): DESIGN.md §3.28, restated in numpy by tests/states_ref.py.  (An addition; the ABI number stays.)
+ * csrc/msm.hip; the layer above is esmdiff_amd/states.py.
+ *
+ * INPUT.  Y is f64 [n, d] with 1 <= d <= ESMDIFF_LAGGED_MAX_DIM (what esmdiff_lagged_project writes), centres f64 [k, d] with
+ * 1 <= k <= ESMDIFF_KMEANS_MAX_K.  The squared distance of a frame to centre j is s = 0, then s = s + (y_c - c_jc) * (y_c - c_jc)
+ * for c = 0 ... d - 1, a product and an add, no FMA.  The label is the SMALLEST j that attains the minimum: the running (minimum,
+ * index) starts as (+inf, -1) and centre j, taken in increasing j through LDS tiles of ESMDIFF_KMEANS_CENTRE_TILE, replaces it when
+ * s < minimum, strictly.  A distance that is not finite (a non-finite component of the centre or of the frame, or squares that
+ * overflow) is never below the minimum: such a centre is never chosen, a frame with a non-finite component is labelled -1, and so is
+ * every frame when no centre is finite.  The dist2 of a frame labelled -1 is NaN.
+ *
+ * esmdiff_kmeans_assign: labels i32 [n], dist2 f64 [n] (may be NULL).  n = 0 writes nothing.
+ * esmdiff_kmeans_step: one Lloyd step in one pass over Y: labels (may be NULL) as above, counts i64 [k] (the frames of every label),
+ * sums f64 [k, d] and inertia f64 [1].  The frames are cut into ESMDIFF_KMEANS_CHUNKS(n) chunks of ESMDIFF_KMEANS_FRAME_CHUNK.  Within
+ * a chunk cluster j's sum in component c is s = +0.0, then s = s + y_tc over the chunk's frames labelled j in increasing t, and the
+ * chunk's inertia is the same running sum of dist2 over its frames labelled >= 0.  A chunk's sums go to a slot of `scratch`
+ * (ESMDIFF_KMEANS_SLOT_BYTES(k, d)) and the slots are added to the outputs in increasing chunk index, starting from chunk 0's own
+ * sums: an empty cluster gives +0.0 and count 0.  Frames labelled -1 contribute to nothing.  scratch (device, 8-byte aligned, need not
+ * be zeroed) holds as many slots as fit, at least one: ESMDIFF_KMEANS_STEP_SCRATCH_BYTES(k, d, slots).  More slots let more chunks run
+ * at once and change no bit: every output is a function of (Y, centres) alone, the same on every run and every device.  n = 0 gives
+ * zeros.  No float atomics.
+ * esmdiff_transition_counts: labels i32 [n], lag >= 1 -> counts i64 [k, k], counts[a][b] = the number of t < n - lag with
+ * labels[t] = a and labels[t + lag] = b, both >= 0 (the sliding-window count; a negative label takes part in no pair); lag >= n gives
+ * zeros.  The entry zeroes counts itself.  A label >= k is looked for by a pass of its own, whose flag (scratch, at least
+ * ESMDIFF_TRANSITION_SCRATCH_BYTES) the entry reads back before anything is written.  Integer atomics: a workgroup-private LDS
+ * histogram over ESMDIFF_TRANSITION_FRAME_CHUNK values of t while k <= ESMDIFF_TRANSITION_LDS_MAX_K (k * k i32 in 64 KiB), added to
+ * counts with 64-bit global atomics; above that one 64-bit global atomic per pair.
+ *
+ * Before anything is launched or written: ESMDIFF_E_INVALID for a NULL pointer (scratch included; not the optional outputs, nor the frames' arrays of n = 0), n < 0,
+ * d < 1, k < 1, lag < 1, and, after the check pass alone, for a label >= k; ESMDIFF_E_CAPACITY for d > ESMDIFF_LAGGED_MAX_DIM,
+ * k > ESMDIFF_KMEANS_MAX_K and a scratch smaller than one slot's (the flag's). */
+#define ESMDIFF_KMEANS_MAX_K 4096
+#define ESMDIFF_KMEANS_CENTRE_TILE 128
+#define ESMDIFF_KMEANS_FRAME_CHUNK 1024
+#define ESMDIFF_KMEANS_CHUNKS(n) (((int64_t)(n) + ESMDIFF_KMEANS_FRAME_CHUNK - 1) / ESMDIFF_KMEANS_FRAME_CHUNK)
+#define ESMDIFF_KMEANS_SLOT_BYTES(k, d) (((int64_t)(k) * (int64_t)(d) + (int64_t)(k) + 1) * 8)
+#define ESMDIFF_KMEANS_STEP_SCRATCH_BYTES(k, d, slots) ((int64_t)(slots) * ESMDIFF_KMEANS_SLOT_BYTES(k, d))
+#define ESMDIFF_TRANSITION_FRAME_CHUNK 4096
+#define ESMDIFF_TRANSITION_LDS_MAX_K 128
+#define ESMDIFF_TRANSITION_SCRATCH_BYTES 8
+int esmdiff_kmeans_assign(const double* Y, int32_t n, int32_t d, const double* centres, int32_t k, int32_t* labels, double* dist2, void* stream);
+int esmdiff_kmeans_step(const double* Y, int32_t n, int32_t d, const double* centres, int32_t k, int32_t* labels, int64_t* counts, double* sums,
+                        double* inertia, void* scratch, int64_t scratch_bytes, void* stream);
+int esmdiff_transition_counts(const int32_t* labels, int32_t n, int32_t k, int32_t lag, int64_t* counts, void* scratch, int64_t scratch_bytes,
+                              void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
