@@ -66,7 +66,8 @@ EXPORTS = [
     "esmdiff_superpose_pairs", "esmdiff_tm_pairs",
     "esmdiff_cluster_threshold", "esmdiff_cluster_gromos",
     "esmdiff_lddt_pairs",
-    "esmdiff_flex_pair_msf", "esmdiff_flex_fit", "esmdiff_flex_moments",
+    "esmdiff_flex_pair_msf", "esmdiff_flex_fit", "esmdiff_flex_moments", "esmdiff_flex_transforms",
+    "esmdiff_aligned_moments", "esmdiff_aligned_project",
     "esmdiff_dssp",
     "esmdiff_contact_map", "esmdiff_native_contacts",
     "esmdiff_backbone_torsions", "esmdiff_ramachandran",
@@ -96,7 +97,8 @@ DEBYE_MAX_Q, DEBYE_Q_CHUNK = 1024, 8         # ESMDIFF_DEBYE_MAX_Q, ESMDIFF_DEBY
 SASA_MAX_ATOMS, SASA_MAX_POINTS = 4096, 1024    # ESMDIFF_SASA_MAX_ATOMS, ESMDIFF_SASA_MAX_POINTS
 COOCC_MAX_L = 32768                          # ESMDIFF_COOCC_MAX_L
 LAGGED_MAX_L, LAGGED_MAX_D, LAGGED_MAX_DIM, LAGGED_FRAME_CHUNK = 128, 8192, 16, 2048    # ESMDIFF_LAGGED_MAX_L, _MAX_D, _MAX_DIM, _FRAME_CHUNK
-KMEANS_MAX_K, KMEANS_CENTRE_TILE, KMEANS_FRAME_CHUNK = 4096, 128, 1024    # ESMDIFF_KMEANS_MAX_K, _CENTRE_TILE, _FRAME_CHUNK
+ALIGNED_MAX_L, ALIGNED_MAX_DIM, ALIGNED_FRAME_CHUNK = 1280, 16, 128    # ESMDIFF_ALIGNED_MAX_L, _MAX_DIM, _FRAME_CHUNK
+KMEANS_MAX_K, KMEANS_CENTRE_TILE, KMEANS_FRAME_CHUNK = 4096, 128, 1024   # ESMDIFF_KMEANS_MAX_K, _CENTRE_TILE, _FRAME_CHUNK
 TRANSITION_FRAME_CHUNK, TRANSITION_LDS_MAX_K, TRANSITION_SCRATCH_BYTES = 4096, 128, 8    # ESMDIFF_TRANSITION_FRAME_CHUNK, _LDS_MAX_K, _SCRATCH_BYTES
 
 CLUSTER_MAX_N = 16384                       # ESMDIFF_CLUSTER_MAX_N
@@ -170,6 +172,11 @@ def lagged_features(L: int, k: int) -> int:
 def lagged_scratch_bytes(D: int, slots: int, moments: bool) -> int:
     """ESMDIFF_LAGGED_MOMENTS_SCRATCH_BYTES / ESMDIFF_LAGGED_MEANS_SCRATCH_BYTES: the pair table, then `slots` chunk sums."""
     return D * 8 + slots * ((3 * D * D + 2 * D) if moments else 2 * D) * 8
+
+
+def aligned_scratch_bytes(L: int, slots: int) -> int:
+    """ESMDIFF_ALIGNED_MOMENTS_SCRATCH_BYTES: `slots` chunk sums, each S (3L, 3L) then r (3L,)."""
+    return slots * (9 * L * L + 3 * L) * 8
 
 
 def kmeans_chunks(n: int) -> int:
@@ -270,6 +277,9 @@ def lib():
     L.esmdiff_flex_pair_msf.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_flex_fit.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.esmdiff_flex_moments.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+    L.esmdiff_flex_transforms.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.esmdiff_aligned_moments.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
+    L.esmdiff_aligned_project.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp]
     L.esmdiff_dssp.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.esmdiff_contact_map.argtypes = [vp, i32, i32, vp, f64, i32, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_native_contacts.argtypes = [vp, i32, vp, i32, i32, vp, vp, f64, i32, f64, f64, vp, vp, vp, vp, vp, vp]

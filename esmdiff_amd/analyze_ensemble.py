@@ -8,6 +8,7 @@
                                            [--sasa] [--sasa_points 96] [--sasa_probe 1.4] [--sasa_threshold 0.2]
                                            [--tica --trajectory REF] [--lagtime 20] [--tica_dim 2] [--lagtimes 5 10 20 ...]
                                            [--msm] [--msm_states 100] [--msm_lagtime LAG] [--msm_metastable 2] [--msm_seed 0]
+                                           [--compare --trajectory REF] [--compare_ref target|first] [--compare_modes 2]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
@@ -75,7 +76,14 @@ block holds the parameters, the inertia and the iterations, the size of the acti
 eigenvalues and timescales, the stationary distribution over the microstates, --msm_metastable metastable sets (the inner-simplex step
 of PCCA+) with their weights and mean TIC position, the microstate of every sample and of every target, and compare_populations: the
 Jensen-Shannon distance of the samples' microstate histogram against the stationary distribution, the populations per metastable set
-beside the model's and the share of the samples outside the active set."""
+beside the model's and the share of the samples outside the active set.
+--compare --trajectory REF adds a "compare" block (esmdiff_amd/covariance.py, csrc/aligned.hip; [ALPHAFLOW-RECALL], parity unpinned):
+the samples against the trajectory in Cartesian space, both superposed on --compare_ref (the first target, or the trajectory's first
+frame) and reduced to their mean and 3L x 3L covariance on the device.  The block holds per residue the Gaussian W2 distance with its
+translation and variance parts, their root means (rmwd), the W2 distance in the trajectory's and in the joint PCA space of
+--compare_modes modes and in all 3L dimensions, the per-component W2 of the projections, RMSIP and the mode cosines, the Pearson
+correlations of the two cross-correlation maps and of the two RMSF profiles, the frames that entered and were dropped, and the
+projections of the samples and of every target on the trajectory's modes.  A .npy trajectory is read --tica_chunk frames at a time."""
 from __future__ import annotations
 
 import argparse
@@ -84,7 +92,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import accessibility, contacts, ensemble, flexibility, kinetics, secondary, shape, states, torsions
+from . import accessibility, contacts, covariance, ensemble, flexibility, kinetics, secondary, shape, states, torsions
 from .pdbio import load_coords, read_pdb_backbone, read_pdb_bfactors
 
 
@@ -221,6 +229,15 @@ def msm_report(samples_path, target_paths, trajectory_path, max_models: int = 10
     return states.report(trajectory, samples, np.stack(targets), lagtime, dim, n_states, msm_lagtime, metastable, msm_seed, chunk_frames=chunk_frames)
 
 
+def compare_report(samples_path, target_paths, trajectory_path, max_models: int = 100, seed: int = 0, ref: str = "target", modes: int = 2,
+                   chunk: int = 65536) -> dict:
+    """The --compare block, on the samples analyze() takes for the same max_models and seed and the trajectory --tica takes; ref:
+    "target" (the first target) or "first" (the trajectory's first frame) is the structure both ensembles are superposed on."""
+    samples, targets, _, _ = load_ca(samples_path, target_paths, max_models, seed)
+    trajectory, chunk_frames = _trajectory(trajectory_path, samples, chunk)
+    return covariance.compare(trajectory, samples, targets[0] if ref == "target" else None, modes, chunk_frames, targets=np.stack(targets))
+
+
 def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0,
             flex: bool = False, pca_components: int = 3, dssp: bool = False) -> dict:
     samples, targets, n_all, keep = load_ca(samples_path, target_paths, max_models, seed)
@@ -284,6 +301,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--msm_lagtime", type=int, default=None, help="lag time of the --msm transition counts, in frames (default: --lagtime)")
     ap.add_argument("--msm_metastable", type=int, default=2, help="metastable sets of --msm (below 2: none)")
     ap.add_argument("--msm_seed", type=int, default=0, help="seed of the kmeans++ initialisation of --msm")
+    ap.add_argument("--compare", action="store_true", help="add the Cartesian comparison with --trajectory: per-residue W2, RMWD, PCA W2, RMSIP, DCCM and RMSF correlations")
+    ap.add_argument("--compare_ref", choices=("target", "first"), default="target", help="the structure --compare superposes both ensembles on: the first target or the trajectory's first frame")
+    ap.add_argument("--compare_modes", type=int, default=2, help="modes of the --compare PCA distances and projections (1 to 16)")
     return ap
 
 
@@ -292,6 +312,8 @@ def main(argv=None) -> Path:
     args = ap.parse_args(argv)
     if args.msm and not (args.tica and args.trajectory):
         ap.error("--msm needs --tica --trajectory REF")
+    if args.compare and not args.trajectory:
+        ap.error("--compare needs --trajectory REF")
     report = analyze(args.samples, args.targets, args.max_models, args.seed, args.lddt, args.plddt_scale, args.flex, args.pca_components,
                      args.dssp)
     if args.contacts:
@@ -314,6 +336,9 @@ def main(argv=None) -> Path:
     if args.msm:
         report["msm"] = msm_report(args.samples, args.targets, args.trajectory, args.max_models, args.seed, args.lagtime, args.tica_dim,
                                    args.msm_states, args.msm_lagtime, args.msm_metastable, args.msm_seed, args.tica_chunk)
+    if args.compare:
+        report["compare"] = compare_report(args.samples, args.targets, args.trajectory, args.max_models, args.seed, args.compare_ref,
+                                           args.compare_modes, args.tica_chunk)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

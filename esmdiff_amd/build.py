@@ -63,6 +63,9 @@ UNITS = {
     # float64 squared distances as a product then an add, and sums in a published order, numpy's bits (tests/states_ref.py).  No SLP:
     # the padded component loops invite packed forms, and the shipped code objects are scanned for them (tests/test_host_cpu.py)
     "msm": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # the transformed coordinate as two products and three adds in a published order, sums in a published order (tests/aligned_ref.py);
+    # the f64 MFMA as in lagged.  No SLP: the 3x3 rotation rows invite packed forms, and the shipped code objects are scanned for them
+    "aligned": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 # The MFMA kernels, the row kernels that feed them and the weight conversion are compiled a SECOND time with f16 operands
 # (csrc/ed_half.h): -DED_F16 switches the conversion / MFMA primitives, -Ded=ed16 puts that build into namespace ed16

@@ -7,6 +7,8 @@
 //                          redundantly in every lane.  A pair's deviations live in registers only.
 //   flex_reduce_kernel     the second pass: the partials of all waves, summed per residue.
 //   flex_fit_kernel        one WAVE per structure: the fit onto one common reference, the whole structure transformed.
+//   flex_transforms_kernel the same fit, one WAVE per structure: rot and tr written out (what csrc/aligned.hip applies inside its
+//                          kernels), no moved structure.
 //   flex_moments_kernel    one WAVE per residue: the mean position over the structures valid there, then (second pass) the mean
 //                          squared distance from it.
 //
@@ -165,6 +167,53 @@ __global__ __launch_bounds__(256) void flex_fit_kernel(const double* __restrict_
   if (lane == 0 && rmsd) rmsd[i] = sqrt(acc / cnt);
 }
 
+// flex_fit_kernel's fit and rmsd (the same statements: the same bits), the transform written out instead of the moved structure
+__global__ __launch_bounds__(256) void flex_transforms_kernel(const double* __restrict__ A, const uint8_t* __restrict__ maskA,
+                                                              const double* __restrict__ ref, const uint8_t* __restrict__ mask_ref,
+                                                              int n, int L, double* __restrict__ T, double* __restrict__ rmsd,
+                                                              uint8_t* __restrict__ ok) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;                                      // the whole wave leaves; the kernel has no barrier
+  const double* a = A + i * L * 3;
+  const uint8_t* ma = maskA ? maskA + i * L : nullptr;
+  auto valid = [&](int l) { return (!ma || ma[l]) && (!mask_ref || mask_ref[l]); };
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  int cnt;
+  double rot[9], tr[3];
+  wave_fit(a, ref, L, lane, valid, cnt, rot, tr);
+  if (cnt < 2) {
+    if (lane < 12) T[i * 12 + lane] = nan;
+    if (lane == 0 && rmsd) rmsd[i] = nan;
+    if (lane == 0) ok[i] = 0;
+    return;
+  }
+  double acc = 0;
+  for (int l = lane; l < L; l += 64) {
+    double x[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) x[r] = rot[3 * r] * a[3 * l] + rot[3 * r + 1] * a[3 * l + 1] + rot[3 * r + 2] * a[3 * l + 2] + tr[r];
+    if (valid(l)) {
+      double d2 = 0;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const double e = x[r] - ref[3 * l + r];
+        d2 += e * e;
+      }
+      acc += d2;
+    }
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) T[i * 12 + k] = rot[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) T[i * 12 + 9 + k] = tr[k];
+    ok[i] = 1;
+    if (rmsd) rmsd[i] = sqrt(acc / cnt);
+  }
+}
+
 __global__ __launch_bounds__(256) void flex_moments_kernel(const double* __restrict__ X, const uint8_t* __restrict__ mask, int n, int L,
                                                            double* __restrict__ mean, double* __restrict__ msf,
                                                            int32_t* __restrict__ count) {
@@ -232,6 +281,14 @@ int esmdiff_flex_fit(const double* A, int32_t n, int32_t L, const uint8_t* maskA
   if (!A || !ref || n < 1 || L < 2) return ESMDIFF_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(flex_fit_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, A, maskA, ref, mask_ref, n, L, aligned, rmsd);
+  return finish_entry(st);
+}
+
+int esmdiff_flex_transforms(const double* A, int32_t n, int32_t L, const uint8_t* maskA, const double* ref, const uint8_t* mask_ref,
+                            double* T, double* rmsd, uint8_t* ok, void* stream) {
+  if (!A || !ref || !T || !ok || n < 1 || L < 2) return ESMDIFF_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(flex_transforms_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, A, maskA, ref, mask_ref, n, L, T, rmsd, ok);
   return finish_entry(st);
 }
 

@@ -1,5 +1,5 @@
 """The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
-csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip, csrc/shape.hip, csrc/sasa.hip, csrc/lagged.hip and csrc/msm.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip, csrc/shape.hip, csrc/sasa.hip, csrc/lagged.hip, csrc/msm.hip and csrc/aligned.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
 on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
 host-facing layers above it.  The frame-wise layers (secondary, torsions, accessibility) share one input stage here: need_device,
 atoms and given_mask; every frame-wise entry below asserts its input through _frames.
@@ -528,6 +528,78 @@ def fit(A, ma, ref, mref):
     code = N.lib().esmdiff_flex_fit(_p(A), n, L, _p(ma), _p(ref), _p(mref), _p(aligned), _p(rmsd), _stream())
     _check("esmdiff_flex_fit", code, invalid=_flex_invalid("esmdiff_flex_fit", n, L))
     return aligned, rmsd
+
+
+def flex_transforms(A, ma, ref, mref):
+    """One esmdiff_flex_transforms call: fit's fit with the transform written out -> T f64 (n, 12) (row-major rot, then tr, with
+    rot a + tr ~ ref), rmsd f64 (n,) (fit's bits), ok u8 (n,).  Fewer than 2 common residues: ok = 0 and NaN in T and rmsd."""
+    n, L = _frames(A, ma, (3,))
+    assert ref.dtype == torch.float64 and tuple(ref.shape) == (L, 3), f"the reference is f64 ({L}, 3), got {tuple(ref.shape)}"
+    assert mref is None or (mref.dtype == torch.uint8 and tuple(mref.shape) == (L,)), "the reference's mask is u8 (L,)"
+    T, rmsd, ok = _new((n, 12)), _new((n,)), _new((n,), torch.uint8)
+    code = N.lib().esmdiff_flex_transforms(_p(A), n, L, _p(ma), _p(ref), _p(mref), _p(T), _p(rmsd), _p(ok), _stream())
+    _check("esmdiff_flex_transforms", code, invalid=_flex_invalid("esmdiff_flex_transforms", n, L))
+    return T, rmsd, ok
+
+
+ALIGNED_WORKGROUPS = 2048      # the chunks one round of esmdiff_aligned_moments runs at once are chosen to give about this many workgroups (eight a CU)
+ALIGNED_SCRATCH_CAP = 1 << 28  # ... within this many bytes of scratch, or one slot where one slot is larger
+
+
+def aligned_slots(L: int, chunks: int) -> int:
+    """The slots of scratch a call gets: enough chunks at once to fill the device, within ALIGNED_SCRATCH_CAP bytes, at least one.  The
+    number changes no bit of the result (include/esmdiff_hip.h)."""
+    tiles = (3 * L + 63) // 64
+    want = -(-ALIGNED_WORKGROUPS // (tiles * (tiles + 1) // 2))
+    return max(1, min(chunks, want, ALIGNED_SCRATCH_CAP // N.aligned_scratch_bytes(L, 1)))
+
+
+def _aligned_input(X, T):
+    assert X.dim() == 3 and X.shape[2] == 3 and X.dtype == torch.float64 and X.is_cuda, f"f64 (n, L, 3) frames on the device, got {X.dtype} {tuple(X.shape)}"
+    n, L = X.shape[:2]
+    assert T is None or (T.dtype == torch.float64 and T.is_cuda and tuple(T.shape) == (n, 12)), f"the transforms are f64 ({n}, 12) on the device"
+    return n, L
+
+
+def _aligned_text(entry, n, L, dim=None):
+    dim_text = "" if dim is None else f", dim = {dim} (1 to {N.ALIGNED_MAX_DIM})"
+    return {"invalid": lambda: f"{entry}: invalid argument: n = {n} (at least 1), L = {L} (at least 1){dim_text}",
+            "capacity": lambda: f"{entry}: L = {L} is beyond the kernel's limit ({N.ALIGNED_MAX_L} residues); there is no slow path"}
+
+
+def aligned_moments(X, T, use, center, slots=None, out=None) -> dict:
+    """One esmdiff_aligned_moments call: X f64 (n, L, 3), T f64 (n, 12) or None (the identity), use u8 (n,) or None (every frame),
+    center f64 (3L,), all on the device -> {S: (3L, 3L), r: (3L,), count: i64 (1,)}: the raw sums of a a^T and a over the used frames,
+    a = (rot x + tr) - center.  slots: the chunk sums the scratch holds (default: aligned_slots); no bit depends on it.  out: {name:
+    tensor} to write into instead of allocating."""
+    n, L = _aligned_input(X, T)
+    D = 3 * L
+    assert use is None or (use.dtype == torch.uint8 and use.is_cuda and tuple(use.shape) == (n,)), f"the flags are u8 ({n},) on the device"
+    assert center is not None and center.dtype == torch.float64 and center.is_cuda and tuple(center.shape) == (D,), f"the centre is f64 ({D},) on the device"
+    shapes = {"S": ((D, D), torch.float64), "r": ((D,), torch.float64), "count": ((1,), torch.int64)}
+    res = {k: out[k] if out and k in out else _new(*s) for k, s in shapes.items()}
+    assert all(tuple(v.shape) == shapes[k][0] and v.dtype == shapes[k][1] for k, v in res.items()), f"the call writes {shapes}"
+    chunks = max(-(-n // N.ALIGNED_FRAME_CHUNK), 1)
+    size = N.aligned_scratch_bytes(max(L, 1), aligned_slots(max(L, 1), chunks) if slots is None else slots)
+    scratch = _new((size // 8,), torch.int64)
+    code = N.lib().esmdiff_aligned_moments(_p(X), n, L, _p(T), _p(use), _p(center), _p(res["S"]), _p(res["r"]), _p(res["count"]),
+                                           _p(scratch), size, _stream())
+    _check("esmdiff_aligned_moments", code, **_aligned_text("esmdiff_aligned_moments", n, L))
+    return res
+
+
+def aligned_project(X, T, mean, W):
+    """One esmdiff_aligned_project call: X f64 (n, L, 3), T f64 (n, 12) or None, mean f64 (3L,), W f64 (3L, dim) on the device ->
+    Y (n, dim) = ((rot x + tr) - mean) W, every frame's row in the same fixed tree."""
+    n, L = _aligned_input(X, T)
+    D = 3 * L
+    assert mean.dtype == torch.float64 and mean.is_cuda and tuple(mean.shape) == (D,), f"the mean is f64 ({D},) on the device"
+    assert W.dim() == 2 and W.dtype == torch.float64 and W.is_cuda and W.shape[0] == D, f"the directions are f64 ({D}, dim) on the device"
+    dim = W.shape[1]
+    Y = _new((n, dim))
+    code = N.lib().esmdiff_aligned_project(_p(X), n, L, _p(T), _p(mean), _p(W), dim, _p(Y), _stream())
+    _check("esmdiff_aligned_project", code, **_aligned_text("esmdiff_aligned_project", n, L, dim))
+    return Y
 
 
 def moments(X, mask):

@@ -608,6 +608,12 @@ int esmdiff_lddt_pairs(const double* A, int32_t n, const double* B, int32_t m, i
  * aligned f64 [n, L, 3] (or NULL): the whole transformed structure, masked residues included (a NaN coordinate stays NaN);
  * rmsd f64 [n] (or NULL): over the common residues.  Fewer than 2 common residues: NaN everywhere for that structure.
  *
+ * esmdiff_flex_transforms: esmdiff_flex_fit's fit with the transform written out instead of the moved structure (required): T f64
+ * [n, 12], row-major rot[9] then tr[3] with rot a + tr ~ ref, what esmdiff_aligned_moments and esmdiff_aligned_project apply inside
+ * their kernels; rmsd f64 [n] (or NULL), esmdiff_flex_fit's bit for bit; ok u8 [n] (required): 1 where the fit had at least 2
+ * common residues, else 0 with NaN in T[i] and rmsd[i].  The argument checks and error codes of esmdiff_flex_fit, and a NULL T or ok
+ * is ESMDIFF_E_INVALID.
+ *
  * esmdiff_flex_moments: per residue l, over the structures i with mask[i, l] (NULL: all): mean f64 [L, 3] the mean position,
  * msf f64 [L] the mean squared distance from that mean (two passes: the mean first, then the deviations), count i32 [L] the number
  * of structures; count = 0 gives NaN in mean and msf. */
@@ -617,6 +623,8 @@ int esmdiff_flex_pair_msf(const double* A, int32_t n, int32_t L, const uint8_t* 
                           int64_t scratch_bytes, void* stream);
 int esmdiff_flex_fit(const double* A, int32_t n, int32_t L, const uint8_t* maskA, const double* ref, const uint8_t* mask_ref,
                      double* aligned, double* rmsd, void* stream);
+int esmdiff_flex_transforms(const double* A, int32_t n, int32_t L, const uint8_t* maskA, const double* ref, const uint8_t* mask_ref,
+                            double* T, double* rmsd, uint8_t* ok, void* stream);
 int esmdiff_flex_moments(const double* X, int32_t n, int32_t L, const uint8_t* mask, double* mean, double* msf, int32_t* count,
                          void* stream);
 
@@ -949,6 +957,45 @@ int esmdiff_kmeans_step(const double* Y, int32_t n, int32_t d, const double* cen
                         double* inertia, void* scratch, int64_t scratch_bytes, void* stream);
 int esmdiff_transition_counts(const int32_t* labels, int32_t n, int32_t k, int32_t lag, int64_t* counts, void* scratch, int64_t scratch_bytes,
                               void* stream);
+
+/* The mean and the 3L x 3L covariance of an ensemble's frames superposed on a reference, as raw sums, and the projection of the
+ * superposed frames: what a comparison of two ensembles in Cartesian space needs of n frames in O(L^2) memory (float64, device
+ * pointers in and out; each call synchronises `stream`): DESIGN.md §3.29, restated in numpy by tests/aligned_ref.py.  (An addition;
+ * the ABI number stays.)  csrc/aligned.hip; the layer above is esmdiff_amd/covariance.py.
+ *
+ * INPUT, the same in both entries: X f64 [n, L, 3] CA coordinates, 1 <= L <= ESMDIFF_ALIGNED_MAX_L; T f64 [n, 12] (row-major rot[9],
+ * then tr[3]: what esmdiff_flex_transforms writes) or NULL (the identity).  With D = 3 L, d = 3 l + c and (x, y, z) = X[t][l] the
+ * feature is f_d(t) = (((R[c][0] x + R[c][1] y) + R[c][2] z) + tr[c]), products and adds in that order with no FMA; T == NULL:
+ * f_d(t) = X[t][l][c] exactly.  The transform is applied inside the kernels; no moved [n, L, 3] array exists.  Non-finite input is
+ * not looked for (esmdiff_amd/covariance.py leaves such frames out through `use`).
+ *
+ * esmdiff_aligned_moments: center c f64 [D] (required), use u8 [n] or NULL (every frame) -> with a(t) = f(t) - c over the t with
+ * use[t] != 0: S f64 [D, D] = sum a a^T and r f64 [D] = sum a (raw sums, undivided), count i64 [1] = the number of those t.  A frame
+ * with use[t] == 0 is staged as zeros and not counted; its coordinates and its T row are never read (they may be NaN) and it changes
+ * no bit of any sum.  The t are cut into chunks of ESMDIFF_ALIGNED_FRAME_CHUNK; a chunk's sums go to a slot of `scratch` and the
+ * slots are added to the outputs in increasing chunk index, starting from chunk 0's own sums.  Within a chunk S is accumulated by
+ * v_mfma_f64_16x16x4_f64 over its t in increasing order, four t to an instruction, for column tile >= row tile only and mirrored: S
+ * is exactly symmetric; r_d is s = +0.0, then s = s + a_d(t) in increasing t.  scratch (device, 8-byte aligned, need not be zeroed)
+ * holds as many slots as fit, at least one: ESMDIFF_ALIGNED_MOMENTS_SCRATCH_BYTES(L, slots).  More slots let more chunks run at once
+ * and change no bit: every output is a function of (X, T, use, c, n, L) alone, the same on every run and every device.  No float
+ * atomics.
+ * esmdiff_aligned_project: Y[n, dim] = (f(t) - mean) W with mean f64 [D], W f64 [D, dim], 1 <= dim <= ESMDIFF_ALIGNED_MAX_DIM.  Per
+ * frame and column, p_l = 0 then p_l = p_l + (f_d - mean_d) * W[d][k] for d = l, l + 64, ... (l = 0 .. 63), then p_l = p_l + p_{l ^ s}
+ * for s = 32, 16, 8, 4, 2, 1 (esmdiff_lagged_project's order): a tree that depends on D alone, so a frame's row does not depend on
+ * the batch.  n = 0 is allowed and writes nothing.
+ *
+ * Before anything is launched or written: ESMDIFF_E_INVALID for a NULL required pointer (center and scratch included), n < 1 (the
+ * projection: n < 0), L < 1, dim outside 1 .. ESMDIFF_ALIGNED_MAX_DIM, a scratch smaller than one slot's; ESMDIFF_E_CAPACITY for
+ * L > ESMDIFF_ALIGNED_MAX_L (the TM kernel's cap: D = 3840, a slot of 118 MB). */
+#define ESMDIFF_ALIGNED_MAX_L 1280
+#define ESMDIFF_ALIGNED_MAX_DIM 16
+#define ESMDIFF_ALIGNED_FRAME_CHUNK 128
+#define ESMDIFF_ALIGNED_MOMENTS_SCRATCH_BYTES(L, slots) \
+  ((int64_t)(slots) * (9 * (int64_t)(L) * (int64_t)(L) + 3 * (int64_t)(L)) * 8)
+int esmdiff_aligned_moments(const double* X, int32_t n, int32_t L, const double* T, const uint8_t* use, const double* center, double* S,
+                            double* r, int64_t* count, void* scratch, int64_t scratch_bytes, void* stream);
+int esmdiff_aligned_project(const double* X, int32_t n, int32_t L, const double* T, const double* mean, const double* W, int32_t dim,
+                            double* Y, void* stream);
 
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
