@@ -68,6 +68,7 @@ EXPORTS = [
     "esmdiff_lddt_pairs",
     "esmdiff_flex_pair_msf", "esmdiff_flex_fit", "esmdiff_flex_moments", "esmdiff_flex_transforms",
     "esmdiff_aligned_moments", "esmdiff_aligned_project",
+    "esmdiff_rmsd_prepare", "esmdiff_rmsd_nearest",
     "esmdiff_dssp",
     "esmdiff_contact_map", "esmdiff_native_contacts",
     "esmdiff_backbone_torsions", "esmdiff_ramachandran",
@@ -100,6 +101,8 @@ LAGGED_MAX_L, LAGGED_MAX_D, LAGGED_MAX_DIM, LAGGED_FRAME_CHUNK = 128, 8192, 16, 
 ALIGNED_MAX_L, ALIGNED_MAX_DIM, ALIGNED_FRAME_CHUNK = 1280, 16, 128    # ESMDIFF_ALIGNED_MAX_L, _MAX_DIM, _FRAME_CHUNK
 KMEANS_MAX_K, KMEANS_CENTRE_TILE, KMEANS_FRAME_CHUNK = 4096, 128, 1024   # ESMDIFF_KMEANS_MAX_K, _CENTRE_TILE, _FRAME_CHUNK
 TRANSITION_FRAME_CHUNK, TRANSITION_LDS_MAX_K, TRANSITION_SCRATCH_BYTES = 4096, 128, 8    # ESMDIFF_TRANSITION_FRAME_CHUNK, _LDS_MAX_K, _SCRATCH_BYTES
+RMSD_NN_TILE, RMSD_NN_RECT, RMSD_NN_MAX_CUTOFFS, RMSD_NN_MAX_BINS = 32, 128, 8, 2048    # ESMDIFF_RMSD_NN_TILE, _RECT, _MAX_CUTOFFS, _MAX_BINS
+RMSD_NN_STATE_BYTES, RMSD_NN_SLOT_BYTES = 96, 2 * 128 * 56    # ESMDIFF_RMSD_NN_STATE_BYTES, _SLOT_BYTES
 
 CLUSTER_MAX_N = 16384                       # ESMDIFF_CLUSTER_MAX_N
 QXT_PHILOX_COLUMN = 4104                     # ESMDIFF_QXT_PHILOX_COLUMN (the header lists the reserved Philox columns)
@@ -177,6 +180,16 @@ def lagged_scratch_bytes(D: int, slots: int, moments: bool) -> int:
 def aligned_scratch_bytes(L: int, slots: int) -> int:
     """ESMDIFF_ALIGNED_MOMENTS_SCRATCH_BYTES: `slots` chunk sums, each S (3L, 3L) then r (3L,)."""
     return slots * (9 * L * L + 3 * L) * 8
+
+
+def rmsd_nn_padded(n_sel: int) -> int:
+    """ESMDIFF_RMSD_NN_PADDED: the row length of a prepared frame's component, the selected count rounded up to a multiple of 4."""
+    return (n_sel + 3) // 4 * 4
+
+
+def rmsd_nn_scratch_bytes(n: int, m: int, slots: int) -> int:
+    """ESMDIFF_RMSD_NN_SCRATCH_BYTES: the per-frame state of both sides (m = 0 for an ensemble against itself), then `slots` rectangles' partials."""
+    return (n + m) * RMSD_NN_STATE_BYTES + slots * RMSD_NN_SLOT_BYTES
 
 
 def kmeans_chunks(n: int) -> int:
@@ -280,6 +293,8 @@ def lib():
     L.esmdiff_flex_transforms.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.esmdiff_aligned_moments.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_aligned_project.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp]
+    L.esmdiff_rmsd_prepare.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    L.esmdiff_rmsd_nearest.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, i32, f64] + [vp] * 13 + [vp, ctypes.c_int64, vp]
     L.esmdiff_dssp.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.esmdiff_contact_map.argtypes = [vp, i32, i32, vp, f64, i32, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
     L.esmdiff_native_contacts.argtypes = [vp, i32, vp, i32, i32, vp, vp, f64, i32, f64, f64, vp, vp, vp, vp, vp, vp]

@@ -9,6 +9,7 @@
                                            [--tica --trajectory REF] [--lagtime 20] [--tica_dim 2] [--lagtimes 5 10 20 ...]
                                            [--msm] [--msm_states 100] [--msm_lagtime LAG] [--msm_metastable 2] [--msm_seed 0]
                                            [--compare --trajectory REF] [--compare_ref target|first] [--compare_modes 2]
+                                           [--coverage --trajectory REF] [--coverage_cutoffs 1 2 3]
 
 Two targets: the apo / holo (or CoDNaS) row of the reference's analysis/apo_analysis.py:222-272 — esmdiff_amd.ensemble.apo_report.
 Any other number K: the BPTI-style evaluation of analysis/bpti_analysis.py:116-129 — tm_n_ensemble's per-target lists and the
@@ -83,7 +84,13 @@ frame) and reduced to their mean and 3L x 3L covariance on the device.  The bloc
 translation and variance parts, their root means (rmwd), the W2 distance in the trajectory's and in the joint PCA space of
 --compare_modes modes and in all 3L dimensions, the per-component W2 of the projections, RMSIP and the mode cosines, the Pearson
 correlations of the two cross-correlation maps and of the two RMSF profiles, the frames that entered and were dropped, and the
-projections of the samples and of every target on the trajectory's modes.  A .npy trajectory is read --tica_chunk frames at a time."""
+projections of the samples and of every target on the trajectory's modes.  A .npy trajectory is read --tica_chunk frames at a time.
+--coverage --trajectory REF adds a "coverage" block (esmdiff_amd/neighbours.py, csrc/rmsd_nn.hip): nearest neighbours under the Kabsch
+RMSD between the samples and every frame of the trajectory, on the residues resolved in the first sample, the first frame and every
+target.  Per --coverage_cutoffs value the recall (the share of trajectory frames with a sample within it) and the precision (the share of
+samples within it of some frame), the mean nearest RMSD each way (mat_r, mat_p), for each sample its nearest frame and RMSD, the samples
+beyond the largest cutoff of every frame (novel), per target the nearest sample and the nearest frame, the mean pairwise RMSD of the
+samples and of the trajectory, and the frames used and dropped.  A .npy trajectory is read --tica_chunk frames at a time."""
 from __future__ import annotations
 
 import argparse
@@ -92,7 +99,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import accessibility, contacts, covariance, ensemble, flexibility, kinetics, secondary, shape, states, torsions
+from . import accessibility, contacts, covariance, ensemble, flexibility, kinetics, neighbours, secondary, shape, states, torsions
 from .pdbio import load_coords, read_pdb_backbone, read_pdb_bfactors
 
 
@@ -238,6 +245,26 @@ def compare_report(samples_path, target_paths, trajectory_path, max_models: int 
     return covariance.compare(trajectory, samples, targets[0] if ref == "target" else None, modes, chunk_frames, targets=np.stack(targets))
 
 
+def coverage_report(samples_path, target_paths, trajectory_path, max_models: int = 100, seed: int = 0, cutoffs=(1.0, 2.0, 3.0),
+                    chunk: int = 65536) -> dict:
+    """The --coverage block, on the samples analyze() takes for the same max_models and seed and the trajectory --tica takes."""
+    samples, targets, _, _ = load_ca(samples_path, target_paths, max_models, seed)
+    trajectory, chunk_frames = _trajectory(trajectory_path, samples, chunk)
+    cutoffs = tuple(float(c) for c in cutoffs)
+    select = np.isfinite(samples[0]).all(-1) & np.isfinite(np.asarray(trajectory[0])).all(-1) & np.isfinite(np.stack(targets)).all((0, 2))
+    cov = neighbours.coverage(samples, trajectory, cutoffs, select=select, chunk_frames=chunk_frames)
+    by_target = neighbours.nearest(np.stack(targets), samples, select)
+    in_trajectory = neighbours.nearest(np.stack(targets), trajectory, select, chunk_frames=chunk_frames)
+    out = {"cutoffs": list(cutoffs), "n_residues": int(select.sum()), "reflection": False}
+    out.update({k: cov[k] for k in ("recall", "precision", "mat_r", "mat_p", "nearest_frame", "nearest_frame_rmsd", "novel", "samples_used",
+                                    "samples_dropped", "frames_used", "frames_dropped")})
+    out["targets"] = {"nearest_sample": by_target.index_a, "nearest_sample_rmsd": by_target.rmsd_a,
+                      "nearest_frame": in_trajectory.index_a, "nearest_frame_rmsd": in_trajectory.rmsd_a}
+    out["mean_pairwise_rmsd"] = {"samples": neighbours.mean_pairwise_rmsd(samples, select),
+                                 "trajectory": neighbours.mean_pairwise_rmsd(trajectory, select, chunk_frames=chunk_frames)}
+    return out
+
+
 def analyze(samples_path, target_paths, max_models: int = 100, seed: int = 0, lddt: bool = False, plddt_scale: float = 1.0,
             flex: bool = False, pca_components: int = 3, dssp: bool = False) -> dict:
     samples, targets, n_all, keep = load_ca(samples_path, target_paths, max_models, seed)
@@ -304,6 +331,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--compare", action="store_true", help="add the Cartesian comparison with --trajectory: per-residue W2, RMWD, PCA W2, RMSIP, DCCM and RMSF correlations")
     ap.add_argument("--compare_ref", choices=("target", "first"), default="target", help="the structure --compare superposes both ensembles on: the first target or the trajectory's first frame")
     ap.add_argument("--compare_modes", type=int, default=2, help="modes of the --compare PCA distances and projections (1 to 16)")
+    ap.add_argument("--coverage", action="store_true", help="add the nearest-neighbour coverage of --trajectory by the samples: recall, precision, nearest pairs, mean pairwise RMSD")
+    ap.add_argument("--coverage_cutoffs", type=float, nargs="+", default=[1.0, 2.0, 3.0], help="RMSD cutoffs of --coverage (Angstrom, at most 8)")
     return ap
 
 
@@ -314,6 +343,8 @@ def main(argv=None) -> Path:
         ap.error("--msm needs --tica --trajectory REF")
     if args.compare and not args.trajectory:
         ap.error("--compare needs --trajectory REF")
+    if args.coverage and not args.trajectory:
+        ap.error("--coverage needs --trajectory REF")
     report = analyze(args.samples, args.targets, args.max_models, args.seed, args.lddt, args.plddt_scale, args.flex, args.pca_components,
                      args.dssp)
     if args.contacts:
@@ -339,6 +370,9 @@ def main(argv=None) -> Path:
     if args.compare:
         report["compare"] = compare_report(args.samples, args.targets, args.trajectory, args.max_models, args.seed, args.compare_ref,
                                            args.compare_modes, args.tica_chunk)
+    if args.coverage:
+        report["coverage"] = coverage_report(args.samples, args.targets, args.trajectory, args.max_models, args.seed, args.coverage_cutoffs,
+                                             args.tica_chunk)
     out = Path(args.output)
     out.mkdir(parents=True, exist_ok=True)
     path = out / f"{Path(args.samples).stem}.ensemble.json"

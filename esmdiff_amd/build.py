@@ -66,6 +66,9 @@ UNITS = {
     # the transformed coordinate as two products and three adds in a published order, sums in a published order (tests/aligned_ref.py);
     # the f64 MFMA as in lagged.  No SLP: the 3x3 rotation rows invite packed forms, and the shipped code objects are scanned for them
     "aligned": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # centroids, G and the msd as products and adds in a published order (tests/neighbours_ref.py); the f64 MFMA as in aligned.  No SLP:
+    # the 3x3 Jacobi rotations invite packed forms, and the shipped code objects are scanned for them
+    "rmsd_nn": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 # The MFMA kernels, the row kernels that feed them and the weight conversion are compiled a SECOND time with f16 operands
 # (csrc/ed_half.h): -DED_F16 switches the conversion / MFMA primitives, -Ded=ed16 puts that build into namespace ed16

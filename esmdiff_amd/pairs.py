@@ -1,5 +1,5 @@
 """The device side of the all-pairs layer: input preparation and one function per C entry of csrc/superpose.hip, csrc/lddt.hip,
-csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip, csrc/shape.hip, csrc/sasa.hip, csrc/lagged.hip, csrc/msm.hip and csrc/aligned.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
+csrc/cluster.hip, csrc/flex.hip, csrc/dssp.hip, csrc/contacts.hip, csrc/torsions.hip, csrc/shape.hip, csrc/sasa.hip, csrc/lagged.hip, csrc/msm.hip, csrc/aligned.hip and csrc/rmsd_nn.hip.  Each function owns its entry's argument list, output allocation and error text; tensors on the device in, tensors
 on the device out, no host transfer.  esmdiff_amd/ensemble.py, esmdiff_amd/clustering.py and esmdiff_amd/flexibility.py are the
 host-facing layers above it.  The frame-wise layers (secondary, torsions, accessibility) share one input stage here: need_device,
 atoms and given_mask; every frame-wise entry below asserts its input through _frames.
@@ -600,6 +600,80 @@ def aligned_project(X, T, mean, W):
     code = N.lib().esmdiff_aligned_project(_p(X), n, L, _p(T), _p(mean), _p(W), dim, _p(Y), _stream())
     _check("esmdiff_aligned_project", code, **_aligned_text("esmdiff_aligned_project", n, L, dim))
     return Y
+
+
+RMSD_NN_WORKGROUPS = 2048         # the rectangles one round of esmdiff_rmsd_nearest runs at once (eight a CU) ...
+RMSD_NN_SCRATCH_CAP = 1 << 28     # ... within this many bytes of slots
+
+
+def rmsd_nn_slots(rectangles: int) -> int:
+    """The slots of scratch a call gets: enough rectangles at once to fill the device, within RMSD_NN_SCRATCH_CAP bytes, at least one.
+    The number changes no bit of the result (include/esmdiff_hip.h)."""
+    return max(1, min(rectangles, RMSD_NN_WORKGROUPS, RMSD_NN_SCRATCH_CAP // N.RMSD_NN_SLOT_BYTES))
+
+
+def rmsd_prepare(X, sel=None, n_sel=None) -> dict:
+    """One esmdiff_rmsd_prepare call: X f64 (n, L, 3) on the device, sel u8 (L,) on the device or None (every residue), n_sel the
+    number of nonzero sel (counted here when not given: one read-back) -> {P: (n, 3, K) the centred, compacted, zero-padded frames
+    with K = N.rmsd_nn_padded(n_sel), info: (n, 4) centroid and G, use: u8 (n,), n_sel}."""
+    assert X.dim() == 3 and X.shape[2] == 3 and X.dtype == torch.float64 and X.is_cuda, f"f64 (n, L, 3) frames on the device, got {X.dtype} {tuple(X.shape)}"
+    n, L = X.shape[:2]
+    assert sel is None or (sel.dtype == torch.uint8 and sel.is_cuda and tuple(sel.shape) == (L,)), f"the selection is u8 ({L},) on the device"
+    if n_sel is None:
+        n_sel = L if sel is None else int((sel != 0).sum())
+    K = N.rmsd_nn_padded(max(n_sel, 0))
+    P, info, use = _new((n, 3, K)), _new((n, 4)), _new((n,), torch.uint8)
+    code = N.lib().esmdiff_rmsd_prepare(_p(X), n, L, _p(sel), n_sel, _p(P), _p(info), _p(use), _stream())
+    _check("esmdiff_rmsd_prepare", code,
+           invalid=lambda: f"esmdiff_rmsd_prepare: invalid argument: n = {n} (at least 1), L = {L}, {n_sel} selected residues (2 to L)")
+    return {"P": P, "info": info, "use": use, "n_sel": n_sel}
+
+
+RMSD_NN_OUTPUTS = ("rmsd", "index", "sum", "pairs", "count")
+
+
+def rmsd_nearest(a: dict, b: Optional[dict] = None, reflection: bool = False, cutoffs=(), bins: int = 0, width: float = 1.0,
+                 want=("row", "col"), dense=(), slots=None, scratch_bytes=None) -> dict:
+    """One esmdiff_rmsd_nearest call on prepared sides (rmsd_prepare's dicts; b None: a against itself over pairs i != j) ->
+    {row_rmsd (n,), row_index i32 (n,), row_sum (n,), row_pairs i64 (n,), row_count i64 (n, T), col_* the same for b (not for b None),
+    hist i64 (bins,) when bins > 0, msd (n, m) / cross (n, m, 9) for the names in `dense`}.  cutoffs: up to N.RMSD_NN_MAX_CUTOFFS
+    host numbers.  slots: the rectangles' partials the scratch holds (default: rmsd_nn_slots); no bit depends on it."""
+    n, n_sel = a["P"].shape[0], a["n_sel"]
+    m = n if b is None else b["P"].shape[0]
+    for side in (a,) + (() if b is None else (b,)):
+        k = side["P"].shape[0]
+        assert side["n_sel"] == n_sel and tuple(side["P"].shape) == (k, 3, N.rmsd_nn_padded(n_sel)), "both sides are prepared on one residue set"
+        assert side["P"].dtype == torch.float64 and tuple(side["info"].shape) == (k, 4) and side["info"].dtype == torch.float64
+        assert tuple(side["use"].shape) == (k,) and side["use"].dtype == torch.uint8
+    cut = np.ascontiguousarray(np.asarray(cutoffs, np.float64).reshape(-1))
+    T = len(cut)
+    res = {}
+    for side, k in (("row", n),) + ((("col", m),) if b is not None else ()):
+        if side in want:
+            res.update({f"{side}_rmsd": _new((k,)), f"{side}_index": _new((k,), torch.int32), f"{side}_sum": _new((k,)),
+                        f"{side}_pairs": _new((k,), torch.int64), f"{side}_count": _new((k, T), torch.int64)})
+    if bins > 0:
+        res["hist"] = _new((bins,), torch.int64)
+    if "msd" in dense:
+        res["msd"] = _new((n, m))
+    if "cross" in dense:
+        res["cross"] = _new((n, m, 9))
+    blocks = lambda k: -(-k // N.RMSD_NN_RECT)
+    rectangles = blocks(n) * (blocks(n) + 1) // 2 if b is None else blocks(n) * blocks(m)
+    if scratch_bytes is None:
+        scratch_bytes = N.rmsd_nn_scratch_bytes(n, 0 if b is None else m, rmsd_nn_slots(rectangles) if slots is None else slots)
+    scratch = _new((max(scratch_bytes, 8) // 8,), torch.int64)
+    g = res.get
+    outs = [g(f"{s}_{k}") for s in ("row", "col") for k in RMSD_NN_OUTPUTS]
+    code = N.lib().esmdiff_rmsd_nearest(_p(a["P"]), _p(a["info"]), _p(a["use"]), n, _p(b and b["P"]), _p(b and b["info"]), _p(b and b["use"]),
+                                        m, n_sel, int(bool(reflection)), ctypes.c_void_p(cut.ctypes.data if T else 0), T, bins, float(width),
+                                        *[_p(t) for t in outs], _p(g("hist")), _p(g("msd")), _p(g("cross")), _p(scratch), scratch_bytes, _stream())
+    _check("esmdiff_rmsd_nearest", code,
+           invalid=lambda: (f"esmdiff_rmsd_nearest: invalid argument: n = {n}, m = {m} (at least 1), {n_sel} selected residues (at least 2), "
+                            f"{T} cutoffs (0 to {N.RMSD_NN_MAX_CUTOFFS}), bins = {bins} (0 or more, with a positive width: {width})"),
+           capacity=lambda: (f"esmdiff_rmsd_nearest: bins = {bins} is beyond the kernel's limit ({N.RMSD_NN_MAX_BINS}), or the scratch "
+                             f"({scratch_bytes} bytes) is smaller than one slot's ({N.rmsd_nn_scratch_bytes(n, 0 if b is None else m, 1)})"))
+    return res
 
 
 def moments(X, mask):

@@ -997,6 +997,54 @@ int esmdiff_aligned_moments(const double* X, int32_t n, int32_t L, const double*
 int esmdiff_aligned_project(const double* X, int32_t n, int32_t L, const double* T, const double* mean, const double* W, int32_t dim,
                             double* Y, void* stream);
 
+/* Nearest neighbours between two ensembles under the least-squares RMSD, with neither a rotation nor an (n, m) matrix (float64, device
+ * pointers in and out; each call synchronises `stream`): DESIGN.md §3.30, restated in numpy by tests/neighbours_ref.py.  (An addition;
+ * the ABI number stays.)  csrc/rmsd_nn.hip; the layer above is esmdiff_amd/neighbours.py.  With both sides centred on ONE set of N
+ * residues: msd(i, j) = max(0, ((G_a[i] + G_b[j]) - 2 ((s1 + s2) + sigma s3)) / N), G = sum |x - c|^2, s1 >= s2 >= s3 the singular
+ * values of H_ij = sum_l a_il b_jl^T; sigma = -1 when allow_reflection == 0 and det H_ij < 0, else +1.
+ *
+ * esmdiff_rmsd_prepare: X f64 [n, L, 3]; sel u8 [L] or NULL (every residue); n_sel = the number of nonzero sel (L when NULL), which the
+ * caller counts.  Per frame over the selected residues: info f64 [n, 4] = the centroid, then G about it; use u8 [n] = 0 when a selected
+ * coordinate is non-finite or G is not finite (then info = 0 and the frame's P is zeros), else 1; P f64 [n, 3, K] with
+ * K = ESMDIFF_RMSD_NN_PADDED(n_sel): P[t][c][k] = component c of the k-th selected residue minus the centroid, k >= n_sel zero.  The
+ * sums: lane l of a wave adds the selected residues among l, l + 64, ... in increasing order from +0.0, then s_l = s_l + s_{l ^ d} for
+ * d = 32, 16, 8, 4, 2, 1; the centroid is that sum / n_sel, G the same walk over ((dx dx + dy dy) + dz dz).  ESMDIFF_E_INVALID before
+ * any launch for a NULL pointer, n < 1, L < 1, n_sel < 2, n_sel > L, sel == NULL with n_sel != L.
+ *
+ * esmdiff_rmsd_nearest: the prepared sides (P, info, use) of A (n frames) and B (m frames) with the same n_sel.  PB == NULL: A against
+ * itself over pairs i != j (m, infoB, useB ignored; the col_* outputs are not written).  A frame with use == 0 is never read and takes
+ * part in no pair.  Outputs, each may be NULL: row_rmsd f64 [n] = sqrt of the minimum msd over j and row_index i32 [n] the lowest j that
+ * attains it (NaN and -1 without a pair); row_sum f64 [n] = sum_j sqrt(msd) and row_pairs i64 [n] the pairs in it; row_count i64
+ * [n, n_cutoffs] the j with sqrt(msd) <= cutoffs[t] (cutoffs: a HOST array of n_cutoffs <= ESMDIFF_RMSD_NN_MAX_CUTOFFS values, read
+ * before the call returns); col_* the same for the frames of B; hist i64 [bins], bin min(bins - 1, floor(sqrt(msd) / width)) over
+ * every pair (PB == NULL: every unordered pair once), bins <= ESMDIFF_RMSD_NN_MAX_BINS, bins == 0: no histogram; msd f64 [n, m] (NaN
+ * where a frame is unused; PB == NULL: [n, n], symmetric, diagonal 0) and cross f64 [n, m, 9] the raw H_ij, for tests and small
+ * problems.  msd(i, j) is a pure function of the two frames' P rows and G.  The pairs are cut into rectangles of ESMDIFF_RMSD_NN_RECT
+ * frames a side, numbered row-major (PB == NULL: column block >= row block); within a rectangle a row's pairs are taken in increasing j
+ * and a column's in increasing i (sum = sum + sqrt(msd) from +0.0, minimum by strict <), a rectangle's partials go to a slot of
+ * `scratch`, and a frame's partials are folded in increasing rectangle number (PB == NULL: its pairs j < i before its pairs j > i).
+ * scratch (device, 8-byte aligned, need not be zeroed): ESMDIFF_RMSD_NN_SCRATCH_BYTES(n, m, slots) with m = 0 for PB == NULL and at
+ * least one slot; more slots let more rectangles run at once and change no bit.  No float atomics.
+ * Before anything is launched or written: ESMDIFF_E_INVALID for a NULL required pointer, n < 1, m < 1 with PB, n_sel < 2, n_cutoffs
+ * outside 0 .. ESMDIFF_RMSD_NN_MAX_CUTOFFS, bins < 0, bins > 0 without hist or a positive width; ESMDIFF_E_CAPACITY for
+ * bins > ESMDIFF_RMSD_NN_MAX_BINS and for a NULL or too small scratch. */
+#define ESMDIFF_RMSD_NN_TILE 32
+#define ESMDIFF_RMSD_NN_RECT 128
+#define ESMDIFF_RMSD_NN_MAX_CUTOFFS 8
+#define ESMDIFF_RMSD_NN_MAX_BINS 2048
+#define ESMDIFF_RMSD_NN_PADDED(n_sel) (((n_sel) + 3) / 4 * 4)
+#define ESMDIFF_RMSD_NN_STATE_BYTES 96
+#define ESMDIFF_RMSD_NN_SLOT_BYTES (2 * ESMDIFF_RMSD_NN_RECT * 56)
+#define ESMDIFF_RMSD_NN_SCRATCH_BYTES(n, m, slots) \
+  (((int64_t)(n) + (int64_t)(m)) * ESMDIFF_RMSD_NN_STATE_BYTES + (int64_t)(slots) * ESMDIFF_RMSD_NN_SLOT_BYTES)
+int esmdiff_rmsd_prepare(const double* X, int32_t n, int32_t L, const uint8_t* sel, int32_t n_sel, double* P, double* info, uint8_t* use,
+                         void* stream);
+int esmdiff_rmsd_nearest(const double* PA, const double* infoA, const uint8_t* useA, int32_t n, const double* PB, const double* infoB,
+                         const uint8_t* useB, int32_t m, int32_t n_sel, int32_t allow_reflection, const double* cutoffs, int32_t n_cutoffs,
+                         int32_t bins, double width, double* row_rmsd, int32_t* row_index, double* row_sum, int64_t* row_pairs,
+                         int64_t* row_count, double* col_rmsd, int32_t* col_index, double* col_sum, int64_t* col_pairs, int64_t* col_count,
+                         int64_t* hist, double* msd, double* cross, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* Per-kernel entry points of the parity tests, the per-section profiler of bench.py's roofline leg and the -DED_DEBUG
  * measurement aids are declared in esmdiff_hip_test.h: they are exported by the same library but are not part of the surface a
  * binding of the reference's call sites needs. */
