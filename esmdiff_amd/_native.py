@@ -39,6 +39,8 @@ class Weight(ctypes.Structure):
 
 # esmdiff_sample_step as a numpy record (one per sample; uploaded as raw bytes)
 SAMPLE_STEP_DTYPE = [("sample_index", "<u8"), ("move_chance_t", "<f4"), ("move_chance_s", "<f4"), ("step", "<i4"), ("final", "<i4")]
+# esmdiff_math_eval_philox (kind 3 of esmdiff_math_eval)
+MATH_EVAL_PHILOX_DTYPE = [("seed", "<u8"), ("sample", "<u8"), ("step", "<u4"), ("l", "<u4"), ("v", "<u4"), ("reserved", "<u4")]
 # esmdiff_gibbs_sample_step
 GIBBS_STEP_DTYPE = [("sample_index", "<u8"), ("step", "<i4"), ("n_unmask", "<i4")]
 
@@ -87,6 +89,7 @@ EXPORTS = [
     "esmdiff_embed_rows", "esmdiff_gather_table_rows", "esmdiff_sigma_mlp", "esmdiff_layernorm_16in",
     "esmdiff_mask_row_list", "esmdiff_gather_rows16", "esmdiff_add_layernorm_rows", "esmdiff_copy_masked_logits",
     "esmdiff_ddpm_step_mapped", "esmdiff_move_token_rows", "esmdiff_samples_with_mask", "esmdiff_rows_identical",
+    "esmdiff_math_eval",
 ]
 LDDT_MAX_L, LDDT_MAX_THRESHOLDS = 4096, 8    # ESMDIFF_LDDT_MAX_L, ESMDIFF_LDDT_MAX_THRESHOLDS
 DSSP_MAX_L = 4096                            # ESMDIFF_DSSP_MAX_L
@@ -362,6 +365,7 @@ def lib():
     L.esmdiff_move_token_rows.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     L.esmdiff_samples_with_mask.argtypes = [vp, i32, i32, vp, vp]
     L.esmdiff_rows_identical.argtypes = [vp, vp, i32, i32, vp, vp]
+    L.esmdiff_math_eval.argtypes = [i32, i32, vp, vp, ctypes.c_int64, vp]
     for n in EXPORTS:
         if n not in ("esmdiff_engine_destroy", "esmdiff_last_error", "esmdiff_encoder_destroy", "esmdiff_encoder_last_error"):
             getattr(L, n).restype = ctypes.c_int

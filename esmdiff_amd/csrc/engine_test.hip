@@ -572,4 +572,17 @@ int esmdiff_rows_identical(const int64_t* seq, const int64_t* x, int32_t B, int3
   return launched(nullptr, launch_rows_identical(seq, x, B, L, flag, (hipStream_t)stream), "rows_identical");
 }
 
+// ---- csrc/ed_math.h as one of the three units compiled it (the kernel is csrc/ed_math_eval.inc inside that unit, not here: this unit
+// carries no -ffp-contract=off) ----
+int esmdiff_math_eval(int32_t unit, int32_t kind, const void* in, void* out, int64_t n, void* stream) {
+  if (unit < 0 || unit > 2 || kind < 0 || kind > 3)
+    return fail(nullptr, ESMDIFF_E_INVALID, "math_eval: unit %d (0 sampler, 1 score, 2 gibbs), kind %d (0 exp, 1 log, 2 noise, 3 philox)", unit, kind);
+  if (n < 0 || ((!in || !out) && n > 0)) return fail(nullptr, ESMDIFF_E_INVALID, "math_eval: n=%lld must not be negative, in and out not null", (long long)n);
+  const hipStream_t st = (hipStream_t)stream;
+  float* o = (float*)out;
+  return launched(nullptr, unit == 0 ? launch_math_eval_sampler(kind, in, o, n, st)
+                         : unit == 1 ? launch_math_eval_score(kind, in, o, n, st)
+                                     : launch_math_eval_gibbs(kind, in, o, n, st), "math_eval");
+}
+
 }  // extern "C"

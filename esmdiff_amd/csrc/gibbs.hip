@@ -451,4 +451,9 @@ hipError_t launch_gibbs_step_rows(int64_t* x, const int64_t* seq, const float* l
   return hipGetLastError();
 }
 
+// this unit's compiled copy of csrc/ed_math.h, one element at a time (esmdiff_math_eval, unit 2)
+#define ED_MATH_EVAL_UNIT gibbs
+#include "ed_math_eval.inc"
+#undef ED_MATH_EVAL_UNIT
+
 }  // namespace ed

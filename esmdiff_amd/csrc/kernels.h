@@ -83,6 +83,13 @@ hipError_t launch_gather_rows16(const uint16_t* src, const int32_t* list, uint16
 hipError_t launch_copy_masked_logits(const int64_t* x, const float* logits, int ld, const int32_t* map, float* out, int ld_out,
                                      int V, int rows, hipStream_t stream);
 
+// ---- sampler.hip, score.hip, gibbs.hip: csrc/ed_math_eval.inc, one instance per unit ----
+// out f32 [n] = ed_expf / ed_logf / the race's noise of in f32 [n] (kind 0 / 1 / 2), or ed_philox_uniform of n records (kind 3), as
+// the unit of the name compiled csrc/ed_math.h
+hipError_t launch_math_eval_sampler(int kind, const void* in, float* out, int64_t n, hipStream_t stream);
+hipError_t launch_math_eval_score(int kind, const void* in, float* out, int64_t n, hipStream_t stream);
+hipError_t launch_math_eval_gibbs(int kind, const void* in, float* out, int64_t n, hipStream_t stream);
+
 // ---- score.hip -----------------------------------------------------------------------------
 // xt = (u < move_chance[b] and not non_moving and l < lens[b]) ? MASK : x0, and seq_out likewise with the sequence MASK when not
 // null; u: explicit uniforms [B,L], or null for Philox(seed, sample_index[b], draw[b], l, ESMDIFF_QXT_PHILOX_COLUMN)

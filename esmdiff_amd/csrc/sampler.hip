@@ -478,4 +478,9 @@ hipError_t launch_rows_identical(const int64_t* seq, const int64_t* x, int B, in
   return hipGetLastError();
 }
 
+// this unit's compiled copy of csrc/ed_math.h, one element at a time (esmdiff_math_eval, unit 0)
+#define ED_MATH_EVAL_UNIT sampler
+#include "ed_math_eval.inc"
+#undef ED_MATH_EVAL_UNIT
+
 }  // namespace ed

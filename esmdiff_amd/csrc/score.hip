@@ -178,4 +178,9 @@ hipError_t launch_nelbo_rows(const float* logits, int ld, int V, const int64_t* 
   return hipGetLastError();
 }
 
+// this unit's compiled copy of csrc/ed_math.h, one element at a time (esmdiff_math_eval, unit 1)
+#define ED_MATH_EVAL_UNIT score
+#include "ed_math_eval.inc"
+#undef ED_MATH_EVAL_UNIT
+
 }  // namespace ed

@@ -1316,6 +1316,25 @@ def rows_identical(seq: torch.Tensor, x: torch.Tensor, flag: torch.Tensor) -> No
                                            _ptr(_dev(flag, torch.int32)), _stream()))
 
 
+MATH_EVAL_UNITS = {"sampler": 0, "score": 1, "gibbs": 2}
+MATH_EVAL_KINDS = {"exp": 0, "log": 1, "noise": 2, "philox": 3}
+
+
+def math_eval(unit: str, kind: str, src: torch.Tensor) -> torch.Tensor:
+    """esmdiff_math_eval: csrc/ed_math.h as `unit` ("sampler", "score", "gibbs") compiled it, one element at a time.  kind "exp",
+    "log", "noise" (1e-10f - ed_logf(u + 1e-10f)): src f32 [n]; "philox": src u8 [n, 32], the bytes of records of
+    _native.MATH_EVAL_PHILOX_DTYPE.  Returns f32 [n]."""
+    _require_gpu()
+    if kind == "philox":
+        assert _dev(src, torch.uint8).dim() == 2 and src.shape[1] == 32
+        n = src.shape[0]
+    else:
+        n = _dev(src, torch.float32).numel()
+    out = torch.empty(n, dtype=torch.float32, device=src.device)
+    N.check(N.lib().esmdiff_math_eval(MATH_EVAL_UNITS[unit], MATH_EVAL_KINDS[kind], _ptr(src), _ptr(out), n, _stream()))
+    return out
+
+
 GEOM_DTYPES = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}
 
 

@@ -117,7 +117,10 @@ typedef struct {
 
 /* Counter-based noise source (performance mode).  Uniform for (sample, step, position l,
  * vocabulary id v) = Philox4x32-10(key = seed, counter = {v>>2, l, sample, step})[v&3] >> 8 · 2^-24,
- * so results do not depend on batch composition or on how samples are sharded over GPUs. */
+ * so results do not depend on batch composition or on how samples are sharded over GPUs.  In words of 32 bits: key = (seed's low
+ * word, seed's high word); counter = (v >> 2, l, sample's low word, step ^ (sample's high word << 16)).  Two draws share a
+ * uniform only if they share all of it: distinct for step < 2^16 and sample < 2^48 (csrc/ed_math.h: ed_philox_uniform;
+ * restated in tests/shared_math_ref.py). */
 typedef struct {
   uint64_t seed;
   uint64_t sample_offset; /* global index of batch row 0 */

@@ -301,6 +301,26 @@ int esmdiff_move_token_rows(const int64_t* src, int64_t* dst, const int32_t* idx
 int esmdiff_samples_with_mask(const int64_t* x, int32_t B, int32_t L, int32_t* has, void* stream);
 int esmdiff_rows_identical(const int64_t* seq, const int64_t* x, int32_t B, int32_t L, int32_t* flag, void* stream);
 
+/* ---- The shared math of csrc/ed_math.h as ONE unit compiled it (tests/test_gpu_shared_math.py against the C oracle and float64).
+ * sampler.hip, score.hip and gibbs.hip each inline their own copy of that header under the unit's own flags, and every bit-exact
+ * test of those units rests on each copy giving the host's bits.  The kernel body is csrc/ed_math_eval.inc, instantiated inside each
+ * of the three units.  No engine; enqueued on `stream` without a wait; every argument is checked before the first HIP call
+ * (ESMDIFF_E_INVALID, nothing touched).  (An addition; the ABI number stays.)
+ *   unit  0: sampler.hip, 1: score.hip, 2: gibbs.hip
+ *   kind  0: out f32 [n] = ed_expf of in f32 [n]          1: ed_logf, likewise
+ *         2: 1e-10f - ed_logf(in + 1e-10f), the noise of the race as the three kernels write it
+ *         3: ed_philox_uniform of in = n records of 32 bytes, esmdiff_math_eval_philox -> out f32 [n]
+ *   n >= 0 (0 launches nothing); in and out do not overlap. */
+typedef struct {
+  uint64_t seed;
+  uint64_t sample;
+  uint32_t step;
+  uint32_t l;
+  uint32_t v;
+  uint32_t reserved;   /* the C layout's tail padding, named: not read */
+} esmdiff_math_eval_philox;
+int esmdiff_math_eval(int32_t unit, int32_t kind, const void* in, void* out, int64_t n, void* stream);
+
 /* Accumulated per-section device time of the esmdiff_forward_logits/ddpm_sample calls since profiling was
  * enabled: esmdiff_set_profiling(eng, 1) brackets every launch with HIP events on the launch stream (no sync);
  * mode 2 brackets only the dominant kernel (FFN-up GEMM, section 6), cheap enough for a timed region; 0 = off. sections: 0 embed, 1 layernorm, 2 gemm_qkv,

@@ -401,6 +401,12 @@ def _kernel_case(name, tiny, alt):
     elif name == "interleave_swiglu":
         mk = lambda k: [_randn(128, 64, seed=1 + k)]
         call = lambda b: E.interleave_swiglu(b[0], BF16)
+    elif name == "math_eval":
+        def mk(k):
+            rec = torch.randint(0, 256, (5000, 32), generator=_gen(3 + k), dtype=torch.uint8)
+            return [torch.rand(100000, generator=_gen(1 + k)) * (20 + k) + 1e-3, rec]
+        call = lambda b: [E.math_eval("sampler", "exp", b[0]), E.math_eval("score", "log", b[0]), E.math_eval("gibbs", "noise", b[0]),
+                          E.math_eval("gibbs", "philox", b[1])]
     else:
         raise KeyError(name)
     return _pair(mk) + (call,)
@@ -409,7 +415,7 @@ def _kernel_case(name, tiny, alt):
 KERNEL_ENTRIES = ["gemm_bf16", "gemm_f16", "gemm_f32", "split_rows+gemm_split", "gemm_split_k", "branch_linear_layernorm",
                   "layernorm_bf16", "layernorm_16in", "add_layernorm", "layernorm_f32rows", "swiglu_f32", "qk_norm_rope",
                   "qk_norm_rope_f32", "v_split", "attention_L65", "attention_f32_parts", "attention_16_parts", "embed_rows",
-                  "gather_table_rows", "sigma_mlp", "convert_weight", "interleave_swiglu"]
+                  "gather_table_rows", "sigma_mlp", "convert_weight", "interleave_swiglu", "math_eval"]
 
 
 @pytest.mark.parametrize("name", KERNEL_ENTRIES)
